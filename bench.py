@@ -15,7 +15,11 @@ exactly `--steps` steps), inputs resident in HBM.  Multi-GPU: one process per GP
 (torch.distributed.run), one weight replica per device, tasks sharded across devices with no
 data-path collective ("scaling": "weak").
 
-Also reported (rank 0, single GPU):
+A plain run sets up, warms up, times the `--steps` steps and prints the result line;
+`--dump-outputs DIR` also writes every worker's output buffer of the last timed step to
+DIR/<name>.npy (seeded inputs: two builds can be compared output for output).
+
+Also reported with `--full` (rank 0, single GPU):
 * `e2e`: the SURVEY 8(d) serving metric -- the mini-runtime (pinned slot pools, H2D/D2H, pipelined
   workers) driven by the C++ client loop: inf/s = inferences / (last response - first request)
   (inference_client.cpp:259-270), p50/p95/p99 request latency incl. H2D + D2H
@@ -550,8 +554,15 @@ def main():
     ap.add_argument("--roofline-reps", type=int, default=200)
     ap.add_argument("--loop-only", action="store_true",
                     help="only the timed loop (the rocprofv3 trace command of tools/trace_round.sh)")
-    ap.add_argument("--detail-out", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="rank 0 writes the full record here (the printed line is its compact summary)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else: re-timed regions, loaded task "
+                         "latency, roofline, the e2e serving legs, the CPU baseline and the extras (minutes)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write each worker's output buffer of the last step to "
+                         "DIR/<name>.npy (float32)")
+    ap.add_argument("--detail-out", default=None,
+                    help="rank 0 writes the full record here (the printed line is its compact summary); "
+                         "default: bench_out/bench_detail.json with --full, none without")
     ap.add_argument("--launch-table", default="",
                     help="write one eager forward's kernel launches (op, kernel, grid) here as TSV (rank 0)")
     ap.add_argument("--control-plane-only", action="store_true",
@@ -560,6 +571,8 @@ def main():
                          "a host-side stand-in for the GPU work")
     args = ap.parse_args()
     args.precision = args.precision or DEFAULT_PRECISION[args.model]
+    if args.detail_out is None:
+        args.detail_out = os.path.join("bench_out", "bench_detail.json") if args.full else ""
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -622,10 +635,8 @@ def main():
     elapsed = h.throughput(args.steps, args.warmup, args.tasks_per_step, world, dist)
     per_step = args.workers * args.tasks_per_step * args.batch
     value = world * per_step * args.steps / elapsed
-    # stability evidence: the same K-step region re-timed (not `value`, which is the first region)
-    repeats = [world * per_step * args.steps / h.throughput(args.steps, 0, args.tasks_per_step, world, dist)
-               for _ in range(args.repeats)]
-    task_lat = h.loaded_latency(20)
+    if args.dump_outputs:
+        dump_outputs(h, args.dump_outputs, rank, world)
 
     result = {
         "metric": BASELINE_METRIC,
@@ -660,10 +671,25 @@ def main():
             "hip_hw_queues": queues,
             "parallelism": f"replicas x{world} (request sharding, no collective)",
         },
-        "value_repeats": [round(v, 1) for v in repeats],
-        "p50_task_latency_ms": round(percentile(task_lat, 50), 4),
-        "p95_task_latency_ms": round(percentile(task_lat, 95), 4),
     }
+    if args.full:
+        full_measurements(args, spi, zoo, rtmod, dist, h, model, replica, result, value, per_step, dev, rank, world)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        emit(result, args.detail_out)
+
+
+def full_measurements(args, spi, zoo, rtmod, dist, h, model, replica, result, value, per_step, dev, rank, world):
+    """`--full`: everything the benchmark reports beside the headline figure, added to `result`."""
+    # stability evidence: the same K-step region re-timed (not `value`, which is the first region)
+    repeats = [world * per_step * args.steps / h.throughput(args.steps, 0, args.tasks_per_step, world, dist)
+               for _ in range(args.repeats)]
+    task_lat = h.loaded_latency(20)
+    result["value_repeats"] = [round(v, 1) for v in repeats]
+    result["p50_task_latency_ms"] = round(percentile(task_lat, 50), 4)
+    result["p95_task_latency_ms"] = round(percentile(task_lat, 95), 4)
     if rank == 0:
         result["model_gflop_per_inference"] = round(replica.flops(1) / 1e9, 4)
         result["model_tflops_per_gpu"] = round(replica.flops(1) * value / world / 1e12, 3)
@@ -727,11 +753,14 @@ def main():
                                       tasks_per_step=args.tasks_per_step)
         result["extras"] = extras
 
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        emit(result, args.detail_out)
+
+def dump_outputs(h, out_dir, rank, world):
+    """What the timed path handed its callers in the last step: every worker's output buffer
+    (the codelet's W buffer) as <out_dir>/output[_rank<r>]_worker<w>.npy, float32."""
+    os.makedirs(out_dir, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for w, out in enumerate(h.d_out):
+        np.save(os.path.join(out_dir, f"output{tag}_worker{w}.npy"), out.float().cpu().numpy())
 
 
 def _r(x, nd=4):
@@ -767,7 +796,8 @@ def compact_line(full: dict) -> dict:
     if e2e:
         out["e2e"] = {"value": e2e.get("value"), "p50_ms": e2e.get("p50_latency_ms"),
                       "p99_ms": e2e.get("p99_latency_ms")}
-    out["p50_task_latency_ms"] = full.get("p50_task_latency_ms")
+    if "p50_task_latency_ms" in full:
+        out["p50_task_latency_ms"] = full["p50_task_latency_ms"]
     ex = full.get("extras", {})
     b1 = ex.get("resnet18_bs1_tasks")
     if b1:

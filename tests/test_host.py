@@ -146,3 +146,40 @@ def test_bench_compact_line_fits_the_driver_tail(tmp_path):
     assert line["resnet18_bs1"]["p50_task_ms"] == 0.1946 and line["c3_bert"]["value"] == 24288.12
     assert line["ci_perf"]["tuned_p50_ms"] == 1.7066 and line["cpu_baseline"]["nproc"] == 256
     assert json.loads(detail.read_text())["data"] == long
+
+
+def test_bench_dump_outputs_writes_every_worker_buffer_as_float32(tmp_path):
+    """bench.dump_outputs: one float32 .npy per worker output buffer, values unchanged; the rank
+    goes into the name only when there are several."""
+    class H:
+        d_out = [torch.arange(6, dtype=torch.float32).reshape(2, 3) + w for w in range(2)]
+    bench.dump_outputs(H, str(tmp_path / "d"), 0, 1)
+    bench.dump_outputs(H, str(tmp_path / "d"), 1, 2)
+    assert sorted(os.listdir(tmp_path / "d")) == ["output_rank1_worker0.npy", "output_rank1_worker1.npy",
+                                                  "output_worker0.npy", "output_worker1.npy"]
+    for w in range(2):
+        a = np.load(tmp_path / "d" / f"output_worker{w}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, H.d_out[w].numpy())
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR`: the line carries the contract's
+    keys with steps as given and nothing that only `--full` measures; every worker ran the same
+    seeded batch, so the dumped (8, 1000) float32 outputs are finite and equal."""
+    import json
+    import subprocess
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup",
+                          "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=120, cwd=tmp_path)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "inferences/s" and line["higher_is_better"] is True and line["dtype"] == "fp16m"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - 256 / (line["ms_per_step"] * 1e-3)) < 1e-2 * line["value"]
+    for k in ("roofline", "e2e", "cpu_baseline", "p50_task_latency_ms", "detail"):
+        assert k not in line
+    assert sorted(os.listdir(tmp_path)) == ["dump"]  # a plain run writes nothing else
+    outs = [np.load(d / f"output_worker{w}.npy") for w in range(4)]
+    assert all(a.dtype == np.float32 and a.shape == (8, 1000) and np.isfinite(a).all() for a in outs)
+    assert np.abs(outs[0]).max() > 0 and all(np.array_equal(outs[0], a) for a in outs[1:])

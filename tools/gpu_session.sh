@@ -5,7 +5,7 @@
 # OUT is a directory under gpurun_out/.  Steps:
 #   tests[=PYTEST_K]        the GPU suite (or the tests matching -k PYTEST_K), one process
 #   smoke                   __graft_entry__.smoke()
-#   bench                   the default bench line (bench.py), summary printed
+#   bench                   the full bench line (bench.py --full), summary printed
 #   loop=MODEL:B:PREC       the timed loop only (bench.py --loop-only)
 #   sweep=MODEL:B:PREC:POL;POL;...   tools/policy_sweep.py, POL = NAME=KEY=VAL[&KEY=VAL] (3 rounds)
 #   ab=MODEL:B:PREC:LIB,LIB,...  timed loops of several library builds (tools/build_variant.sh;
@@ -40,7 +40,7 @@ for step in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$log" 2>&1 || fail "$step" "$log"
       tail -1 "$log" ;;
     bench)
-      timeout -k 10 600 python -u bench.py --detail-out "$O/bench_detail.json" > "$O/bench.json" 2> "$log" || fail "$step" "$log"
+      timeout -k 10 600 python -u bench.py --full --detail-out "$O/bench_detail.json" > "$O/bench.json" 2> "$log" || fail "$step" "$log"
       tail -c 2000 "$O/bench.json"; echo ;;
     loop)
       IFS=: read -r m b p <<< "$val"
