@@ -26,6 +26,7 @@
 // rows, 16-byte chunk c of row r at slot c ^ (r & 7), swizzle applied on the
 // DMA source address (rule 21), conflict-free ds_read_b128 fragment reads.
 #include "device_math.hpp"
+#include "gemm_plan.hpp"
 #include "ln_fold.hpp"
 #include "spi_kernels.hpp"
 
@@ -73,8 +74,8 @@ struct G256Args {
 };
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kMaxSplits = 4;     // split-K slices (gemm256_splits)
-constexpr int kMinSliceKt = 16;   // k-tiles per slice at least (ViT-L out-proj, K = 1024, 2 x 8: 52.9 us b2b vs 40.2 unsplit)
+constexpr int kMaxSplits = 4;     // split-K slices (gemm256_splits, gemm_plan.cpp)
+static_assert(kMaxSplits == kG256MaxSplits, "gemm_plan.hpp: the planner's slice cap is the reduction's");
 // diagnostic build -DSPI_G256_EPI_CALLS: leave the epilogue instances to the inliner (A/B)
 #ifdef SPI_G256_EPI_CALLS
 #define SPI_G256_EPI_INLINE
@@ -869,36 +870,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const G256Args g) {
 
 }  // namespace
 
-void gemm256_reload_env() {}
-
 #ifdef SPI_G256_TIMELINE
 extern "C" int spi_debug_g256_timeline(unsigned long long* host, size_t n) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_g256_tl), n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
 }
 #endif
-
-int gemm256_splits(const GemmDesc& d, int target, int max_split, int bm) {
-  const int tiles = (d.M + bm - 1) / bm * (d.N / 256), kt = d.K / 64;
-  if (tiles >= target || max_split == 1) return 1;
-  int s = std::min({(target + tiles - 1) / tiles, kt / kMinSliceKt, kMaxSplits});
-  if (max_split > 0) s = std::min(s, max_split);
-  if (s <= 1) return 1;
-  const int ktp = (kt + s - 1) / s;
-  return (kt + ktp - 1) / ktp;
-}
-
-bool gemm256_eligible(const GemmDesc& d, Prec prec, int min_tiles, int bm) {
-  if (min_tiles <= 0 || prec != Prec::F16 || d.conv || d.krep != 1 || d.a_split || d.out_split || d.pool_rows ||
-      d.out_f16)
-    return false;
-  if (d.res_planes != d.out_planes) return false;  // two planes: residual and output together (RES = 3)
-  if ((d.res_f32 || d.res_planes) && d.act != Act::None) return false;  // RES >= 2: no activation instances
-  if (d.N % 256 || d.K % 64 || d.Kpad != d.K || d.lda % 8 || d.M < 1) return false;
-  // no post-LN residual epilogue here (BERT's out-proj / FFN2 under the LayerNorm fold keep the
-  // general kernel at every size; gemm256() rejects them)
-  if (d.res_ln_chunks > 0) return false;
-  return (d.M + bm - 1) / bm * (d.N / 256) >= min_tiles;
-}
 
 void gemm256(const GemmDesc& d, const GemmPtrs& p, int splits, hipStream_t s, int bm, int nbuf, int n_fast) {
   if (d.N % 256 || d.K % 64 || d.Kpad != d.K) throw std::invalid_argument("gemm256: N % 256, K % 64, Kpad == K");
@@ -936,6 +912,8 @@ void gemm256(const GemmDesc& d, const GemmPtrs& p, int splits, hipStream_t s, in
   g.c16 = p.ln.c16;
   if ((d.ln_in_chunks > 0 || d.ln_out) && !g.vec_ok)
     throw std::invalid_argument("gemm256: the LayerNorm fold needs the vector epilogue");
+  if (!gemm256_ln_chunks_ok(d.ln_in_chunks))
+    throw std::invalid_argument("gemm256: the LayerNorm consumer fold reads an even number of chunks, 2 to 16");
   if (d.ln_in_chunks > 0 && (p.res || d.out_f32))
     throw std::invalid_argument("gemm256: the LayerNorm consumer fold is for fp16 outputs without a residual");
   const bool planes = d.res_planes || d.out_planes;

@@ -5,6 +5,7 @@
 // inside the codelet (src/core/starpu_setup.cpp:610), and the model graphs the
 // reference exports (models/import_resnet.py:25-73, models/import_vit.py:10-62,
 // models/import_bert-base-uncased.py:8-39).
+#include "gemm_plan.hpp"
 #include "model.hpp"
 #include "pack.hpp"
 
@@ -821,7 +822,7 @@ Model::ConvCall Model::conv_call(const ConvW& c, const void* x, int B, int H, in
 void Model::run_conv(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW,
                      Act act, const void* res, Workspace& ws, hipStream_t s, bool out_f32, bool res_f32) {
   const ConvCall k = conv_call(c, x, B, H, W, y, OH, OW, act, res, ws, out_f32, res_f32);
-  if (gemm_partial_floats(k.d, k.prec) > ws.partial_floats || gemm_counter_slots(k.d, k.prec) > kCounterSlots)
+  if (!gemm_workspace_fits(k.d, k.prec, ws.partial_floats, kCounterSlots))
     throw std::runtime_error("split-K workspace too small");
   const int nrep = !prof_ ? 1 : op_begin(s, k.name, k.flops, k.bytes);
   for (int r = 0; r < nrep; ++r) gemm(k.d, k.p, k.prec, s);
@@ -840,8 +841,7 @@ void Model::run_conv_pair(const ConvW& c0, const void* x, int B, int H, int W, v
     run_conv(c1, x, B, H, W, y1, OH1, OW1, Act::None, nullptr, ws, s, out1_f32);
     return;
   }
-  if (gemm_partial_floats(k0.d, k0.prec) + gemm_partial_floats(k1.d, k1.prec) > ws.partial_floats ||
-      gemm_counter_slots(k0.d, k0.prec) + gemm_counter_slots(k1.d, k1.prec) > kCounterSlots)
+  if (!gemm_workspace_fits(k0.d, k0.prec, ws.partial_floats, kCounterSlots, &k1.d))
     throw std::runtime_error("split-K workspace too small");
   const int nrep = !prof_ ? 1 : op_begin(s, k0.name + "+" + k1.name, k0.flops + k1.flops, k0.bytes + k1.bytes);
   for (int r = 0; r < nrep; ++r) gemm_pair(k0.d, k0.p, k1.d, k1.p, k0.prec, s);
@@ -900,7 +900,7 @@ void Model::run_gemm(const LinearW& L, const void* A, int M, int lda, void* C, i
   p.counters = ws.counters;
   p.zeros = dblob_;  // the blob starts with a zeroed 256-byte line
   p.ln = lp;
-  if (gemm_partial_floats(d, L.prec) > ws.partial_floats || gemm_counter_slots(d, L.prec) > kCounterSlots)
+  if (!gemm_workspace_fits(d, L.prec, ws.partial_floats, kCounterSlots))
     throw std::runtime_error("split-K workspace too small");
   for (int r = 0; r < nrep; ++r) gemm(d, p, L.prec, s);
   if (prof_) op_end(s);
@@ -947,7 +947,7 @@ GemmDesc Model::pooled_fc_desc(int B, int hw) const {
 
 void Model::run_pooled_fc(const void* act, int B, int hw, void* out, Workspace& ws, hipStream_t s) {
   const GemmDesc d = pooled_fc_desc(B, hw);
-  if (gemm_partial_floats(d, fc_.prec) > ws.partial_floats || gemm_counter_slots(d, fc_.prec) > kCounterSlots)
+  if (!gemm_workspace_fits(d, fc_.prec, ws.partial_floats, kCounterSlots))
     throw std::runtime_error("split-K workspace too small");
   const size_t es = f16_ ? 2 : 4;
   const int nrep = !prof_ ? 1 : op_begin(s, "avgpool_fc_M" + std::to_string(B * hw) + "_N" + std::to_string(classes_) + "_K" +

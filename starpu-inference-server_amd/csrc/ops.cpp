@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/spi_ops.h"
+#include "gemm_plan.hpp"
 #include "pack.hpp"
 #include "spi_kernels.hpp"
 
@@ -93,7 +94,7 @@ int spi_op_gemm(int32_t precision, const void* A, int32_t M, int32_t K, int32_t 
       return fail("split gemm needs K, N and strides multiples of 32, no fp32 operands");
     d.a_split = d.out_split = true;
   }
-  if (spi::gemm_partial_floats(d, p) > kSlabFloats || spi::gemm_counter_slots(d, p) > kTickets)
+  if (!spi::gemm_workspace_fits(d, p, kSlabFloats, kTickets))
     return fail("gemm too large for the op workspace");
   spi::GemmPtrs ptrs = scratch(workspace);
   ptrs.A = A;
@@ -139,7 +140,7 @@ int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_
       return fail("split conv needs Cin >= 32, Cout a multiple of 32 and <= 31 filter taps");
     d.a_split = d.out_split = true;
   }
-  if (spi::gemm_partial_floats(d, p) > kSlabFloats || spi::gemm_counter_slots(d, p) > kTickets)
+  if (!spi::gemm_workspace_fits(d, p, kSlabFloats, kTickets))
     return fail("conv too large for the op workspace");
   spi::GemmPtrs ptrs = scratch(workspace);
   ptrs.A = x;

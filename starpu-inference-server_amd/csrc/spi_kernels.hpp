@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "gemm_desc.hpp"
+
 namespace spi {
 
 // Every kernel launch goes through SPI_LAUNCH.  While a forward is profiled
@@ -29,79 +31,6 @@ inline const char* kernel_id() {
       spi_log_->push_back({::spi::kernel_id<F>(), dim3(G).x, dim3(G).y, dim3(G).z, dim3(B).x});          \
     hipLaunchKernelGGL(F, G, B, SH, S, __VA_ARGS__);                                                     \
   } while (0)
-
-enum class Act : int { None = 0, Relu = 1, Gelu = 2 };
-
-// Contraction precision.  F16X3 = split fp16 (fp32 activations, hi/lo fp16
-// operands, three MFMAs per fragment): fp32-grade results at the fp16 rate.
-enum class Prec : int { F32 = 0, F16 = 1, F16X3 = 2 };
-
-// C[M,N] = act(A[M,K] . W[N,K]^T + bias[N] + residual[M,N])
-//
-// A is either a dense row-major activation (lda) or, for conv-as-implicit-GEMM,
-// an NHWC image gathered on the fly: row m = (img, oh, ow), column
-// k = (kh*KW + kw)*Cin + c.  W is pre-packed [Npad][Kpad] (K contiguous,
-// zero padded), so both MFMA operands are K-contiguous 16-byte chunks.  For
-// Prec::F16X3 each W row is Kpad/32 blocks of [32 hi fp16 | 32 lo fp16].
-struct GemmDesc {
-  int M = 0, N = 0, K = 0;  // logical sizes
-  int Kpad = 0;             // W row stride (multiple of 64)
-  size_t wplane = 0;        // elements between the hi and lo weight planes (F16X3)
-  int lda = 0;              // dense A row stride (elements)
-  int ldc = 0;              // C row stride (elements)
-  int ldr = 0;              // residual row stride (elements)
-  // conv geometry (conv == true)
-  bool conv = false;
-  int H = 0, W = 0, Cin = 0, OH = 0, OW = 0, KH = 1, KW = 1, stride = 1, pad = 0;
-  Act act = Act::None;
-  bool out_f32 = false;  // C is float (else the compute type)
-  bool out_f16 = false;  // C is fp16 although the mode's output type is fp32 (F16X3, plain stores)
-  bool res_f32 = false;  // residual is float (else the compute type)
-  // F16X3 activation split layout: per row, blocks of 32 elements stored as
-  // [32 hi fp16 | 32 lo fp16] (128 bytes, the size of 32 fp32), hi = fp16(x),
-  // lo = fp16(x - hi).  a_split: A and the residual are split (conv Cin >= 32);
-  // out_split: C is written split.
-  bool a_split = false;
-  bool out_split = false;
-  // Fused global average pool + linear layer (ResNet avgpool + fc): A holds
-  // pool_rows consecutive rows (pixels) per image; output row b of C is
-  // act(mean over image b's rows of A . W^T + bias).  Linearity lets the GEMM
-  // run over every pixel and average its own C tile (64 x 64 tiles, one image
-  // per tile row, pool_rows <= 64).  M = images x pool_rows.
-  int pool_rows = 0;
-  // krep = 2 (F16, dense or one-tap-per-step conv A): the packed W holds two k-steps per A
-  // k-step -- fp16(w) then fp16(w - fp16(w)) for the same 64 k-values -- and each A k-step is
-  // staged twice, so one launch accumulates x.w_hi + x.w_lo (~22-bit weights on fp16 MFMAs).
-  // Kpad is the packed (W) row length; K stays the logical A length.
-  int krep = 1;
-  // W came from pack_matrix_into of an fp16 64 x 576 matrix, whose padding rows 64..127
-  // hold the weight-resident conv's LDS image (pack.hpp); conv_wres requires it.
-  bool w_image = false;
-  // LayerNorm folded across GEMMs (transformer fp16 path; dense F16 A, the
-  // vector epilogue only).  Row statistics travel as per-64-column-chunk partials
-  // (mean, M2) -- [rows][chunks][2] fp32 -- combined by Chan's formula where they are used.
-  //  ln_in_chunks > 0: A holds the rows x BEFORE a LayerNorm (an fp16 copy), W was packed
-  //    with the gain folded in (W' = W diag(gamma)), and the epilogue applies
-  //    y = rstd[m] * (acc - mean[m] * c1[n]) + bias[n] (bias = b + W beta, c1 = W' 1).
-  //  res_ln_chunks > 0: the residual is LN(R) computed on the fly from the fp32 rows R and
-  //    their statistics: (R - mean) * rstd * g + b (a post-LN block's input).
-  //  ln_out: write the output rows' chunk statistics (N / 64 chunks) and an fp16 copy of
-  //    the output (C16, row stride ld16) for the next, folding GEMM.
-  int ln_in_chunks = 0;
-  float ln_in_eps = 0.f;
-  int res_ln_chunks = 0;
-  float res_ln_eps = 0.f;
-  bool ln_out = false;
-  int ld16 = 0;
-  // Two-plane fp16 residual stream (round 6, the transformer fold path): a row-major [rows][ld]
-  // tensor x kept as hi = fp16(x) at the pointer and lo = fp16(x - hi) `plane` elements further on
-  // -- ~22-bit values in the bytes of fp32, and the hi plane is already the fp16 operand the next
-  // folding GEMM reads, so a producer writes no separate fp16 copy (LnPtrs::c16 may be null).
-  // res_planes: the residual is such a pair; out_planes: C is written as one.
-  bool res_planes = false;
-  bool out_planes = false;
-  size_t plane = 0;
-};
 
 // Pointers of the LayerNorm fold (GemmDesc::ln_in_chunks / res_ln_chunks / ln_out).
 struct LnPtrs {
@@ -126,11 +55,8 @@ struct GemmPtrs {
   LnPtrs ln;
 };
 
-// Workspace needed by a GEMM with the chosen split-K (0 when not split).
-size_t gemm_partial_floats(const GemmDesc& d, Prec prec);
-size_t gemm_counter_slots(const GemmDesc& d, Prec prec);
-// k-values per staged step (W rows must be padded to a multiple of it).
-int gemm_kstep(Prec prec);
+// Plans, routing and workspace sizing (gemm_partial_floats / gemm_counter_slots / gemm_kstep /
+// gemm_workspace_fits) are host-only: gemm_plan.hpp.
 void gemm(const GemmDesc& d, const GemmPtrs& p, Prec prec, hipStream_t s);
 // Two independent problems of one precision in a single launch when their plans
 // share a kernel instance (else two launches); problem 1's split-K slabs and
@@ -141,15 +67,9 @@ void gemm_pair(const GemmDesc& d0, const GemmPtrs& p0, const GemmDesc& d1, const
 
 // 8-wave phased fp16 GEMM (gemm256.hip), tiles of bm x 256 (bm = 256 or 128) for the dense
 // F16 contractions; gemm() routes a desc to it when gemm256_eligible (N % 256 == 0,
-// K % 64 == 0, at least min_tiles tiles of bm x 256; routing rule in gemm.hip).
-bool gemm256_eligible(const GemmDesc& d, Prec prec, int min_tiles, int bm = 256);
-// Split-K slices for a gemm256 problem: 1 with >= target tiles, else enough slices of >= 16
-// k-tiles (at most 4, at most max_split when > 0) to reach ~target workgroups (ViT-L's
-// N = 1024 GEMMs: 52 tiles -> FFN2 3 slices, out-proj none).
-int gemm256_splits(const GemmDesc& d, int target, int max_split, int bm = 256);
+// K % 64 == 0, at least min_tiles tiles of bm x 256; routing rule in gemm_plan.cpp).
 void gemm256(const GemmDesc& d, const GemmPtrs& p, int splits, hipStream_t s, int bm = 256, int nbuf = 2,
              int n_fast = 0);
-void gemm256_reload_env();  // no knobs left (kept for spi_debug_gemm_reload_env)
 
 // Fused QKV projection + attention for S <= 128 (qkv_attn.hip): one workgroup per (sequence,
 // head) runs the head's q | k | v GEMM (A rows lda apart, packed W rows ldw apart; with

@@ -32,7 +32,7 @@ def packed(prec, n, k):
 
 
 def plan_blocks(M, N, K, estep, T=128):
-    """Workgroups of the default plan rule (gemm.hip choose_plan, tput:T, default 128)."""
+    """Workgroups of the default plan rule (gemm_plan.cpp choose_plan, tput:T, default 128)."""
     tiles = lambda bm, bn: -(-M // bm) * -(-N // bn)
     ks = -(-K // 64) * 64 // estep
     if N > 64 and tiles(128, 128) >= T:
