@@ -85,6 +85,54 @@ int spi_op_attention(int32_t precision, const void* qkv, const float* mask_bias,
 int spi_op_layernorm(int32_t precision, const float* x, const float* gamma, const float* beta,
                      float* yf, void* yt, int32_t rows, int32_t D, float eps, void* stream);
 
+/* ---- LayerNorm folded across GEMMs (transformer fp16 path) ----
+ * Row statistics travel as per-64-column-chunk partials, fp32 [rows][D / 64][2] of (mean, M2 = sum of
+ * squared deviations from the chunk's mean), combined by Chan's formula where they are read.  A two-plane
+ * tensor is a row-major [rows][ld] fp32-grade tensor kept as hi = fp16(x) at the pointer and
+ * lo = fp16(x - hi) `plane` elements (a multiple of 8) further on. */
+
+/* Host arithmetic of the fold for y = LN(x) W^T + b: w_folded [N][K] = W diag(gamma) (fp32),
+ * bias_out [N] = b + W beta, c1_out [N] = sum_k of w_folded as packed -- rounded to fp16 for precision
+ * fp16 (hi + lo when hilo), else the fp32 values.  b may be null.  All host fp32 arrays; pack w_folded
+ * with spi_op_pack_weight. */
+int spi_op_fold_linear(int32_t precision, const float* w_host, const float* b_host, int32_t N, int32_t K,
+                       const float* gamma_host, const float* beta_host, int32_t hilo, float* w_folded_out,
+                       float* bias_out, float* c1_out);
+
+/* Element kinds of spi_op_gemm_ln's residual and output. */
+#define SPI_KIND_NONE 0   /* (residual only) no residual */
+#define SPI_KIND_F16 1
+#define SPI_KIND_F32 2
+#define SPI_KIND_PLANES 3 /* two fp16 planes, `plane` elements apart */
+
+/* The dense fp16 GEMM C = act(A . W^T + bias + residual) with every fold field settable (N % 128 == 0;
+ * bias, C, residual, c1, res_g, res_b, c16 16-byte aligned; ldc, ldr, ld16 multiples of 8):
+ *   consumer (in_stats and c1 non-null; K % 64 == 0): A holds the fp16 rows x before a LayerNorm, in_stats
+ *     their statistics [M][K / 64][2], W / bias / c1 come from spi_op_fold_linear, and the epilogue
+ *     computes rstd (acc - mean c1) + bias;
+ *   residual: res_kind says how it is stored; a two-plane output takes an fp16-typed residual as planes;
+ *   residual LayerNorm (res_stats, res_g, res_b non-null; fp32 or two-plane residual): the residual added
+ *     is LN(R) g + b, from R's statistics [M][N / 64][2];
+ *   producer (out_stats non-null): writes the output rows' statistics [M][N / 64][2] and, when c16 is not
+ *     null, an fp16 copy of the output (row stride ld16); c16 may be null only for a two-plane output.
+ * eps serves both LayerNorms.  residual == C (in place) is allowed. */
+int spi_op_gemm_ln(const void* A, int32_t M, int32_t K, int32_t lda, const void* W_packed, int32_t N,
+                   const float* bias, const float* in_stats, const float* c1, const void* residual,
+                   int32_t res_kind, int32_t ldr, const float* res_stats, const float* res_g, const float* res_b,
+                   float eps, void* C, int32_t out_kind, int32_t ldc, size_t plane, float* out_stats, void* c16,
+                   int32_t ld16, int32_t act, void* workspace, void* stream);
+
+/* Row LayerNorm over rows held in two fp16 planes (x = hi + lo), D <= 1024, input row stride ldx:
+ * yf fp32 and/or yt (fp16 when precision fp16, else fp32), row stride ldy. */
+int spi_op_layernorm_planes(int32_t precision, const void* xh, size_t plane, int32_t ldx, const float* gamma,
+                            const float* beta, float* yf, void* yt, int32_t ldy, int32_t rows, int32_t D,
+                            float eps, void* stream);
+
+/* ViT stream assembly into two planes: row (b, 0) = cls + pos[0], row (b, 1 + p) = patches[b][p] + pos[1 + p]
+ * (all fp32, D % 64 == 0), plus the rows' chunk statistics [B (P + 1)][D / 64][2] when stats is not null. */
+int spi_op_vit_assemble_planes(const float* patches, const float* cls, const float* pos, void* xh, size_t plane,
+                               float* stats, int32_t B, int32_t P, int32_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,17 @@ _PROTOS = {
                                    C.c_float, C.c_void_p]),
     "spi_op_layernorm": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "spi_op_fold_linear": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spi_op_gemm_ln": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p,
+                                 C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spi_op_layernorm_planes": (C.c_int, [C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                          C.c_void_p]),
+    "spi_op_vit_assemble_planes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 

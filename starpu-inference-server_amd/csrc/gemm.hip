@@ -1936,13 +1936,21 @@ void gemm(const GemmDesc& d, const GemmPtrs& p, Prec prec, hipStream_t s) {
     if (prec != Prec::F16 || d.conv || d.pool_rows || d.plane % 8 || (d.res_planes && (!p.res || d.res_f32)) ||
         (d.out_planes && (d.out_f32 || d.out_f16)))
       throw std::invalid_argument("two-plane residual / output: dense fp16 GEMM, plane offset a multiple of 8");
+    // a two-plane output keeps an fp16-typed residual in two planes too (Model::run_gemm's rule; an
+    // fp32 residual -- the stream's first block -- is the one other kind)
+    if (d.out_planes && p.res && !d.res_f32 && !d.res_planes)
+      throw std::invalid_argument("two-plane output: the residual is fp32 or two planes");
   }
   const GemmPlan g = plan_gemm(d, prec);
+  // gemm256's producer epilogue exists over an fp32 residual into fp32 and over two planes in place
+  // of form (the transformers' out-proj / FFN2); any other producer keeps the general kernel, as the
+  // plan cannot tell: it does not see the residual pointer
+  const bool g256_producer_ok = !d.ln_out || (p.res && ((d.res_f32 && d.out_f32) || (d.res_planes && d.out_planes)));
   switch (prec) {
     case Prec::F16:
       if (conv_wres_eligible(d, prec, p))
         conv_wres(d, p, s);
-      else if (g.g256_bm && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 &&
+      else if (g.g256_bm && g256_producer_ok && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 &&
                (reinterpret_cast<uintptr_t>(p.W) & 15) == 0)  // 16-byte LDS-DMA pieces
         gemm256(d, p, g.g256_splits, s, g.g256_bm, g.g256_nbuf, g.g256_order);
       else

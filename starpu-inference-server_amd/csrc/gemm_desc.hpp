@@ -73,7 +73,8 @@ struct GemmDesc {
   // tensor x kept as hi = fp16(x) at the pointer and lo = fp16(x - hi) `plane` elements further on
   // -- ~22-bit values in the bytes of fp32, and the hi plane is already the fp16 operand the next
   // folding GEMM reads, so a producer writes no separate fp16 copy (LnPtrs::c16 may be null).
-  // res_planes: the residual is such a pair; out_planes: C is written as one.
+  // res_planes: the residual is such a pair; out_planes: C is written as one, and then the
+  // residual, if any, is either fp32 (res_f32) or such a pair -- never a plain fp16 tensor.
   bool res_planes = false;
   bool out_planes = false;
   size_t plane = 0;

@@ -6,6 +6,7 @@
 // reference exports (models/import_resnet.py:25-73, models/import_vit.py:10-62,
 // models/import_bert-base-uncased.py:8-39).
 #include "gemm_plan.hpp"
+#include "ln_fold_pack.hpp"
 #include "model.hpp"
 #include "pack.hpp"
 
@@ -255,23 +256,7 @@ LinearW pack_linear_folded(const float* w, const float* b, int N, int K, Prec pr
                            const float* beta, bool hilo = false) {
   std::vector<float> wf((size_t)N * K), bf(N);
   std::vector<float> c1(N);
-  for (int n = 0; n < N; ++n) {
-    double bb = b ? b[n] : 0.0, cc = 0.0;
-    for (int k = 0; k < K; ++k) {
-      const float v = w[(size_t)n * K + k];
-      const float f = v * gamma[k];
-      wf[(size_t)n * K + k] = f;
-      bb += (double)beta[k] * v;
-      if (prec == Prec::F16) {
-        const float hi = static_cast<float>(static_cast<_Float16>(f));
-        cc += hilo ? (double)hi + (double)static_cast<float>(static_cast<_Float16>(f - hi)) : (double)hi;
-      } else {
-        cc += (double)f;
-      }
-    }
-    bf[n] = (float)bb;
-    c1[n] = (float)cc;
-  }
+  fold_linear(w, b, N, K, gamma, beta, prec == Prec::F16, hilo, wf.data(), bf.data(), c1.data());
   LinearW L = pack_linear(wf.data(), bf.data(), N, K, prec, hilo);
   L.c1 = pack_vec(c1.data(), N);
   return L;
@@ -288,7 +273,9 @@ bool ln_fold_enabled(Prec prec, bool by_default) {
 // folded against 6.30k, profiles/r04/fixed/vit_fold_ab.txt: the producer epilogues' fp16 copy and
 // the consumers' statistics round trip + spills cost more than the 46 removed launches); on since
 // round 6 over the two-plane residual stream (no copy; statistics loaded under the last k-tile):
-// 6.68k folded against 6.59k (profiles/r06/vit_fold/)
+// 6.68k folded against 6.59k (profiles/r06/vit_fold/).  On rows whose mean exceeds their spread (the
+// folded form's cancellation case; test_vit_layernorm_fold_outliers, pos_embedding += 1) the fold
+// measures 7.2e-4 against the oracle, the separate launches 6.7e-4: both inside the 1e-3 bar
 constexpr bool kBertLnFold = true;
 constexpr bool kVitLnFold = true;
 

@@ -3,10 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <exception>
 #include <string>
 
 #include "../../include/spi_ops.h"
 #include "gemm_plan.hpp"
+#include "ln_fold_pack.hpp"
 #include "pack.hpp"
 #include "spi_kernels.hpp"
 
@@ -36,6 +38,19 @@ int fail(const std::string& m) {
 int check_launch() {
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : fail(hipGetErrorString(e));
+}
+
+// The launchers throw std::invalid_argument on a desc they cannot run; no C++ exception may
+// cross the C boundary, so every entry point that reaches one runs its body through this.
+template <typename F>
+int guarded(F&& body) {
+  try {
+    return body();
+  } catch (const std::exception& e) {
+    return fail(e.what());
+  } catch (...) {
+    return fail("unknown C++ exception");
+  }
 }
 
 spi::GemmPtrs scratch(void* ws) {
@@ -102,8 +117,10 @@ int spi_op_gemm(int32_t precision, const void* A, int32_t M, int32_t K, int32_t 
   ptrs.bias = bias;
   ptrs.res = residual;
   ptrs.C = C;
-  spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
-  return check_launch();
+  return guarded([&] {
+    spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
 }
 
 int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* Wp,
@@ -148,8 +165,10 @@ int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_
   ptrs.bias = bias;
   ptrs.res = residual;
   ptrs.C = y;
-  spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
-  return check_launch();
+  return guarded([&] {
+    spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
 }
 
 int spi_op_avgpool_fc(int32_t precision, const void* x, int32_t B, int32_t HW, int32_t C, const void* W, int32_t N,
@@ -176,8 +195,10 @@ int spi_op_avgpool_fc(int32_t precision, const void* x, int32_t B, int32_t HW, i
   ptrs.W = W;
   ptrs.bias = bias;
   ptrs.C = y;
-  spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
-  return check_launch();
+  return guarded([&] {
+    spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
 }
 
 size_t spi_op_stem_pool_bytes(void) { return spi::stem_pool_bytes(); }
@@ -197,24 +218,125 @@ int spi_op_stem_pool(int32_t precision, const float* x, int32_t B, int32_t H, in
   // stem_pool's lo: 0 fp16 weights, 1 hi + lo weights on the fp16 image (the model's fp16m stem),
   // 2 hi + lo weights on the split image (fp32-grade; fp16x3 and the split output)
   const int lo = precision == 1 ? 0 : precision == 2 ? 1 : 2;
-  spi::stem_pool(x, Wp, bias, y, B, H, W, lo, precision == 3, rows_per_block, static_cast<hipStream_t>(stream));
-  return check_launch();
+  return guarded([&] {
+    spi::stem_pool(x, Wp, bias, y, B, H, W, lo, precision == 3, rows_per_block, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
 }
 
 int spi_op_attention(int32_t precision, const void* qkv, const float* mask_bias, void* ctx, int32_t B, int32_t S,
                      int32_t heads, float scale, void* stream) {
   if ((precision != 0 && precision != 1) || !qkv || !ctx || B <= 0 || S <= 0 || heads <= 0)
     return fail("invalid attention arguments");
-  spi::attention(qkv, mask_bias, ctx, B, S, heads, 64, scale, precision == 1, static_cast<hipStream_t>(stream));
-  return check_launch();
+  return guarded([&] {
+    spi::attention(qkv, mask_bias, ctx, B, S, heads, 64, scale, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
 }
 
 int spi_op_layernorm(int32_t precision, const float* x, const float* g, const float* b, float* yf, void* yt,
                      int32_t rows, int32_t D, float eps, void* stream) {
   if (precision < 0 || precision > 2 || !x || !g || !b || rows <= 0 || D <= 0 || D > 1024 || (!yf && !yt))
     return fail("invalid layernorm arguments");
-  spi::layernorm(x, D, g, b, yf, yt, D, rows, D, eps, precision == 1, static_cast<hipStream_t>(stream));
-  return check_launch();
+  return guarded([&] {
+    spi::layernorm(x, D, g, b, yf, yt, D, rows, D, eps, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_fold_linear(int32_t precision, const float* w, const float* b, int32_t N, int32_t K, const float* gamma,
+                       const float* beta, int32_t hilo, float* w_folded, float* bias, float* c1) {
+  spi::Prec p;
+  if (!prec_of(precision, &p) || !w || !gamma || !beta || !w_folded || !bias || !c1 || N <= 0 || K <= 0)
+    return fail("invalid fold_linear arguments");
+  if (hilo && p != spi::Prec::F16) return fail("hi/lo weight packing is an fp16 layout");
+  spi::fold_linear(w, b, N, K, gamma, beta, p == spi::Prec::F16, hilo != 0, w_folded, bias, c1);
+  return 0;
+}
+
+int spi_op_gemm_ln(const void* A, int32_t M, int32_t K, int32_t lda, const void* W, int32_t N, const float* bias,
+                   const float* in_stats, const float* c1, const void* residual, int32_t res_kind, int32_t ldr,
+                   const float* res_stats, const float* res_g, const float* res_b, float eps, void* C,
+                   int32_t out_kind, int32_t ldc, size_t plane, float* out_stats, void* c16, int32_t ld16,
+                   int32_t act, void* workspace, void* stream) {
+  if (!A || !W || !C || !workspace || M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N || act < 0 || act > 2 ||
+      out_kind < SPI_KIND_F16 || out_kind > SPI_KIND_PLANES ||
+      (residual ? res_kind < SPI_KIND_F16 || res_kind > SPI_KIND_PLANES || ldr < N : res_kind != SPI_KIND_NONE))
+    return fail("invalid gemm_ln arguments");
+  const bool consumer = in_stats || c1, res_ln = res_stats || res_g || res_b, producer = out_stats || c16;
+  if ((consumer && K % 64) || ((res_ln || producer) && N % 64))
+    return fail("gemm_ln: the LayerNorm fold works on whole 64-column chunks");
+  spi::GemmDesc d;
+  d.M = M;
+  d.N = N;
+  d.K = K;
+  d.Kpad = spi::round_up_to(K, 64);
+  d.wplane = (size_t)spi::round_up_to(N, 128) * d.Kpad;
+  d.lda = lda;
+  d.ldc = ldc;
+  d.ldr = ldr;
+  d.act = static_cast<spi::Act>(act);
+  d.out_f32 = out_kind == SPI_KIND_F32;
+  d.res_f32 = res_kind == SPI_KIND_F32;
+  d.out_planes = out_kind == SPI_KIND_PLANES;
+  d.res_planes = res_kind == SPI_KIND_PLANES;
+  d.plane = plane;
+  spi::LnPtrs lp;
+  if (consumer) {
+    d.ln_in_chunks = K / 64;
+    d.ln_in_eps = eps;
+    lp.in_stats = in_stats;
+    lp.c1 = c1;
+  }
+  if (res_ln) {
+    d.res_ln_chunks = N / 64;
+    d.res_ln_eps = eps;
+    lp.res_stats = res_stats;
+    lp.res_g = res_g;
+    lp.res_b = res_b;
+  }
+  if (producer) {
+    d.ln_out = true;
+    d.ld16 = ld16;
+    lp.out_stats = out_stats;
+    lp.c16 = static_cast<_Float16*>(c16);
+  }
+  if (!spi::gemm_workspace_fits(d, spi::Prec::F16, kSlabFloats, kTickets))
+    return fail("gemm too large for the op workspace");
+  spi::GemmPtrs ptrs = scratch(workspace);
+  ptrs.A = A;
+  ptrs.W = W;
+  ptrs.bias = bias;
+  ptrs.res = residual;
+  ptrs.C = C;
+  ptrs.ln = lp;
+  return guarded([&] {
+    spi::gemm(d, ptrs, spi::Prec::F16, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_layernorm_planes(int32_t precision, const void* xh, size_t plane, int32_t ldx, const float* g,
+                            const float* b, float* yf, void* yt, int32_t ldy, int32_t rows, int32_t D, float eps,
+                            void* stream) {
+  if (precision < 0 || precision > 1 || !xh || !g || !b || rows <= 0 || D <= 0 || ldx < D || ldy < D || (!yf && !yt))
+    return fail("invalid layernorm_planes arguments");
+  return guarded([&] {
+    spi::layernorm_planes(static_cast<const _Float16*>(xh), plane, ldx, g, b, yf, yt, ldy, rows, D, eps,
+                          precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_vit_assemble_planes(const float* patches, const float* cls, const float* pos, void* xh, size_t plane,
+                               float* stats, int32_t B, int32_t P, int32_t D, void* stream) {
+  if (!patches || !cls || !pos || !xh || B <= 0 || P <= 0 || D <= 0)
+    return fail("invalid vit_assemble_planes arguments");
+  return guarded([&] {
+    spi::vit_assemble_planes(patches, cls, pos, static_cast<_Float16*>(xh), plane, stats, B, P, D,
+                             static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
 }
 
 }  // extern "C"

@@ -157,3 +157,96 @@ def stem_pool(prec, x_nchw, w_folded, bias, rows_per_block=0, stream=None):
     _check(lib.spi_op_stem_pool(STEM_PREC[prec], _ptr(x_nchw), B, H, W_, _ptr(wp), _ptr(bias), _ptr(out),
                                 rows_per_block, C.c_void_p(s)))
     return out
+
+
+# ---- LayerNorm folded across GEMMs (spi_ops.h: spi_op_fold_linear / spi_op_gemm_ln / ..._planes) ----
+
+KIND = {None: 0, "none": 0, "fp16": 1, "fp32": 2, "planes": 3}  # SPI_KIND_*
+
+
+def to_planes(x: torch.Tensor, plane: int | None = None) -> torch.Tensor:
+    """fp32 tensor -> its two-plane form in one flat fp16 buffer of 2 * plane elements:
+    hi = fp16(x) from element 0, lo = fp16(x - hi) from element `plane` (default x.numel());
+    elements past x.numel() in either plane are zero."""
+    x = x.float().contiguous()
+    n = x.numel()
+    plane = n if plane is None else plane
+    if plane < n:
+        raise ValueError("plane shorter than the tensor")
+    hi = x.half()
+    buf = torch.zeros(2 * plane, dtype=torch.float16, device=x.device)
+    buf[:n] = hi.reshape(-1)
+    buf[plane:plane + n] = (x - hi.float()).half().reshape(-1)
+    return buf
+
+
+def from_planes(buf: torch.Tensor, plane: int, shape=None) -> torch.Tensor:
+    """Inverse of to_planes: hi + lo in fp32, the first prod(shape) elements (default: the whole plane)."""
+    n = plane if shape is None else int(np.prod(shape))
+    flat = buf.reshape(-1)
+    x = flat[:n].float() + flat[plane:plane + n].float()
+    return x if shape is None else x.reshape(*shape)
+
+
+def chunk_stats(x64: np.ndarray) -> np.ndarray:
+    """float64 rows [rows][D] (D % 64 == 0) -> [rows][D / 64][2] of each 64-column chunk's
+    (mean, M2 = sum of squared deviations from that mean), float64."""
+    x64 = np.asarray(x64, dtype=np.float64)
+    rows, D = x64.shape
+    c = x64.reshape(rows, D // 64, 64)
+    mean = c.mean(-1)
+    return np.stack([mean, ((c - mean[..., None]) ** 2).sum(-1)], axis=-1)
+
+
+def combine_stats(stats: np.ndarray, eps: float):
+    """Chan's formula over [rows][chunks][2] chunk statistics, in float64 -> (row mean, row rstd)."""
+    s = np.asarray(stats, dtype=np.float64)
+    chunks = s.shape[1]
+    mean = s[..., 0].mean(-1)
+    m2 = (s[..., 1] + 64.0 * (s[..., 0] - mean[:, None]) ** 2).sum(-1)
+    return mean, 1.0 / np.sqrt(m2 / (64.0 * chunks) + eps)
+
+
+def fold_linear(prec, w, b, gamma, beta, hilo=False):
+    """Host arithmetic of the fold for y = LN(x) W^T + b: (W diag(gamma), b + W beta, c1) as fp32 numpy."""
+    f32 = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float32))  # noqa: E731
+    w, b, gamma, beta = f32(w), f32(b), f32(gamma), f32(beta)
+    n, k = w.shape
+    wf, bias, c1 = np.empty((n, k), np.float32), np.empty(n, np.float32), np.empty(n, np.float32)
+    _check(lib.spi_op_fold_linear(PREC[prec], w.ctypes.data, None if b is None else b.ctypes.data, n, k,
+                                  gamma.ctypes.data, beta.ctypes.data, int(hilo), wf.ctypes.data, bias.ctypes.data,
+                                  c1.ctypes.data))
+    return wf, bias, c1
+
+
+def gemm_ln(A, W_packed, N_, out, out_kind, M=None, K=None, lda=None, bias=None, in_stats=None, c1=None,
+            residual=None, res_kind=None, ldr=None, res_stats=None, res_g=None, res_b=None, eps=1e-5, ldc=None,
+            plane=0, out_stats=None, c16=None, ld16=None, act=None, ws=None, stream=None):
+    """spi_op_gemm_ln on caller-owned buffers (tensors used as plain HBM; strides default to N / K).
+    c1 may be a tensor or a raw device address (int)."""
+    M = A.shape[0] if M is None else M
+    K = A.shape[1] if K is None else K
+    ws = workspace(A.device) if ws is None else ws
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    c1p = C.c_void_p(c1) if isinstance(c1, int) else _ptr(c1)
+    _check(lib.spi_op_gemm_ln(_ptr(A), M, K, K if lda is None else lda, _ptr(W_packed), N_, _ptr(bias),
+                              _ptr(in_stats), c1p, _ptr(residual), KIND[res_kind], N_ if ldr is None else ldr,
+                              _ptr(res_stats), _ptr(res_g), _ptr(res_b), eps, _ptr(out), KIND[out_kind],
+                              N_ if ldc is None else ldc, plane, _ptr(out_stats), _ptr(c16),
+                              N_ if ld16 is None else ld16, ACT[act], _ptr(ws), C.c_void_p(s)))
+    return out
+
+
+def layernorm_planes(prec, xh, plane, ldx, gamma, beta, rows, D, eps, yf=None, yt=None, ldy=None, stream=None):
+    """Row LayerNorm of rows held in two fp16 planes; yt is fp16 for prec fp16, else fp32."""
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(lib.spi_op_layernorm_planes(PREC[prec], _ptr(xh), plane, ldx, _ptr(gamma), _ptr(beta), _ptr(yf), _ptr(yt),
+                                       D if ldy is None else ldy, rows, D, eps, C.c_void_p(s)))
+    return yf, yt
+
+
+def vit_assemble_planes(patches, cls, pos, xh, plane, stats, B, P, D, stream=None):
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(lib.spi_op_vit_assemble_planes(_ptr(patches), _ptr(cls), _ptr(pos), _ptr(xh), plane, _ptr(stats), B, P, D,
+                                          C.c_void_p(s)))
+    return xh

@@ -183,3 +183,40 @@ def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
     outs = [np.load(d / f"output_worker{w}.npy") for w in range(4)]
     assert all(a.dtype == np.float32 and a.shape == (8, 1000) and np.isfinite(a).all() for a in outs)
     assert np.abs(outs[0]).max() > 0 and all(np.array_equal(outs[0], a) for a in outs[1:])
+
+
+@pytest.mark.parametrize("with_b", [True, False], ids=["bias", "nobias"])
+@pytest.mark.parametrize("hilo", [False, True], ids=["f16", "hilo"])
+@pytest.mark.parametrize("N,K", [(128, 64), (384, 192), (256, 1088)])
+def test_fold_linear_packing_arithmetic(N, K, hilo, with_b):
+    """spi_op_fold_linear, the host half of the LayerNorm fold (y = LN(x) W^T + b as a GEMM on the
+    un-normalised rows), against numpy float64: W' = float32(W gamma) exactly; c1 = the sum of W' AS
+    PACKED -- rounded to fp16, hi + lo with hilo -- exactly (fp16 values summed in double are exact in
+    any order), because the epilogue's mean * c1 has to cancel what the MFMAs accumulated from the
+    rounded operands, not from the fp32 ones; bias' = b + W beta to 1e-6 relative."""
+    import importlib
+    ops = importlib.import_module("starpu-inference-server_amd.ops")
+    rng = np.random.default_rng(N * 3 + K)
+    w = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    b = rng.standard_normal(N).astype(np.float32) if with_b else None
+    gamma = (1 + 0.3 * rng.standard_normal(K)).astype(np.float32)
+    beta = (0.1 * rng.standard_normal(K)).astype(np.float32)
+    gamma[[3, K // 2, K - 1]] = 8.0
+    beta[[5, K // 3, K - 2]] = [3.0, -3.0, 3.0]
+    wf, bias, c1 = ops.fold_linear("fp16", w, b, gamma, beta, hilo=hilo)
+    wf_ref = (w.astype(np.float64) * gamma.astype(np.float64)).astype(np.float32)
+    assert np.array_equal(wf, wf_ref)
+    hi = wf_ref.astype(np.float16)
+    packed = hi.astype(np.float64)
+    if hilo:
+        packed = packed + (wf_ref - hi.astype(np.float32)).astype(np.float16).astype(np.float64)
+    assert np.array_equal(c1, packed.sum(1).astype(np.float32))
+    # the rounding matters at these sizes: the unrounded sum is a different float32 in most columns
+    assert (wf_ref.astype(np.float64).sum(1).astype(np.float32) != c1).mean() > 0.5
+    bias_ref = (0.0 if b is None else b.astype(np.float64)) + w.astype(np.float64) @ beta.astype(np.float64)
+    np.testing.assert_allclose(bias.astype(np.float64), bias_ref, rtol=1e-6, atol=0)
+    # fp32 / fp16x3 weights are not rounded: c1 sums the fp32 values; hi + lo packing is fp16 only
+    _, _, c1_f32 = ops.fold_linear("fp32", w, b, gamma, beta)
+    assert np.array_equal(c1_f32, wf_ref.astype(np.float64).sum(1).astype(np.float32))
+    with pytest.raises(ops.OpError):
+        ops.fold_linear("fp32", w, b, gamma, beta, hilo=True)
