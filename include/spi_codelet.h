@@ -304,6 +304,27 @@ int spi_model_profile_op(spi_model* model, void* stream, int64_t batch, int64_t 
  * Writes at most buflen - 1 bytes plus a NUL; returns the full length, or -1 on error. */
 int64_t spi_model_launch_table(spi_model* model, void* stream, int64_t batch, int64_t seq,
                                const void* const* inputs, void* const* outputs, char* buf, size_t buflen);
+/* 8-bit image tasks.  A ResNet / ViT replica also takes tasks whose input_types[0] is
+ * SPI_DTYPE_U8: decoded pixels, one byte per element, laid out as the task's dims say --
+ * [B,3,S,S] (NCHW) or [B,S,S,3] (NHWC, what image decoders produce), S the replica's
+ * image size.  The kernel that reads the task's buffer (the fused stem, or the layout
+ * ingest / ViT patchify) loads the bytes itself, so no fp32 image is built on the host and
+ * a quarter of the bytes cross the host link.  Pixel p of channel c enters the network as
+ *     (float)p * scale[c] + shift[c]
+ * computed as one fp32 multiply rounded to nearest, then one fp32 add rounded to nearest,
+ * never a fused multiply-add: a host that does the same two operations in float32
+ * (numpy x * s + b, ATen x.float().mul(s).add(b)) reproduces the value bit for bit, and
+ * the forward then equals the one of an fp32 task holding that image.  The conv's zero
+ * padding is zero after the transform, as in PyTorch on a normalised image.
+ * The default is scale 1, shift 0; passing NULL for both resets to it.  Returns
+ * SPI_ERR_INVALID_ARGUMENT for a non-finite value or a single NULL, SPI_ERR_UNSUPPORTED for
+ * a replica of another family.  The values travel as kernel arguments of each forward:
+ * nothing is allocated on the device or captured into a graph, and fp32 tasks ignore them,
+ * so one replica serves fp32 and 8-bit tasks interleaved.  Call it before serving: it is
+ * not synchronised with forwards being enqueued on other threads.
+ * The measurement hooks above (spi_model_profile, _profile_op, _launch_table) carry no
+ * element type and always read fp32 NCHW inputs. */
+int spi_model_set_input_transform(spi_model* model, const float scale[3], const float shift[3]);
 /* Capture launch-bound forwards into hipGraphs (per stream, per batch). */
 void spi_model_set_graphs(spi_model* model, int32_t enable);
 /* Per-worker warm-up (inference_runner.cpp:507-560): allocate `stream`'s

@@ -77,6 +77,22 @@ int spi_op_stem_pool_pack(const float* w_host, void* dst_host);
 int spi_op_stem_pool(int32_t precision, const float* x, int32_t B, int32_t H, int32_t W,
                      const void* W_packed, const float* bias, void* y, int32_t rows_per_block, void* stream);
 
+/* The same stem on 8-bit pixels: x is [B][3][H][W] (nhwc 0) or [B][H][W][3] (nhwc 1) bytes at
+ * any byte address; pixel p of channel c enters as fl(fl((float)p * scale[c]) + shift[c]) (two
+ * fp32 roundings, no FMA; spi_codelet.h: spi_model_set_input_transform) and from there is
+ * treated exactly as an fp32 image holding those values: same precision codes, same y.
+ * scale / shift: host fp32 [3]; both null = scale 1, shift 0. */
+int spi_op_stem_pool_u8(int32_t precision, const uint8_t* x, int32_t nhwc, int32_t B, int32_t H, int32_t W,
+                        const void* W_packed, const float* bias, const float* scale_host, const float* shift_host,
+                        void* y, int32_t rows_per_block, void* stream);
+
+/* ViT patchify of a 3-channel image: y [B (H/ps) (W/ps)][3 ps ps] (fp16 when out_f16, else fp32),
+ * row (b, ph, pw), column c ps ps + kh ps + kw (the conv weight's flatten order).  src_kind: 0 x is
+ * fp32 [B][3][H][W]; 1 bytes [B][3][H][W]; 2 bytes [B][H][W][3], both under the transform above
+ * (scale / shift ignored for src_kind 0).  H and W multiples of ps. */
+int spi_op_patchify(int32_t src_kind, const void* x, int32_t B, int32_t H, int32_t W, int32_t ps,
+                    const float* scale_host, const float* shift_host, void* y, int32_t out_f16, void* stream);
+
 /* Multi-head attention over packed qkv [B*S][3*D] (fp16 or fp32), head_dim 64. */
 int spi_op_attention(int32_t precision, const void* qkv, const float* mask_bias, void* ctx,
                      int32_t B, int32_t S, int32_t heads, float scale, void* stream);

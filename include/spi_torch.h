@@ -51,6 +51,15 @@ void spi_torch_free(spi_torch_module* module);
 int spi_torch_cpu_forward(void* model_cpu, const spi_tensor_view* inputs, int num_inputs,
                           spi_tensor_view* outputs, int num_outputs, char* err, size_t errlen);
 
+/* 8-bit image tasks on a CPU worker (the counterpart of spi_model_set_input_transform): once
+ * set, when input 0 of a task is a 4-D SPI_DTYPE_U8 view -- [B,3,H,W] (NCHW) or [B,H,W,3]
+ * (NHWC, permuted first) -- spi_torch_cpu_forward feeds the module the contiguous fp32 NCHW
+ * tensor x.float().mul(scale[c]).add(shift[c]): the same two fp32 roundings as the GPU
+ * codelet, so both workers see the same image bit for bit.  Without a transform (the default;
+ * NULL, NULL clears it) the byte tensor goes to the module unchanged.  Returns SPI_OK or
+ * SPI_ERR_INVALID_ARGUMENT (non-finite value, a single NULL).  Set it before serving. */
+int spi_torch_set_input_transform(spi_torch_module* module, const float scale[3], const float shift[3]);
+
 /* Floating named_parameters() then named_buffers() (first occurrence of a name
  * wins), each copied to contiguous fp32 and owned by the module handle.
  * Returns the count, or -1 on error. */

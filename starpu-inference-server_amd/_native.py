@@ -177,6 +177,7 @@ _PROTOS = {
     "spi_model_flops": (C.c_double, [C.c_void_p, C.c_int64]),
     "spi_model_describe": (C.c_char_p, [C.c_void_p]),
     "spi_model_set_graphs": (None, [C.c_void_p, C.c_int32]),
+    "spi_model_set_input_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "spi_model_warmup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
     "spi_model_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(C.c_double),
@@ -216,6 +217,11 @@ _PROTOS = {
     "spi_op_stem_pool_pack": (C.c_int, [C.c_void_p, C.c_void_p]),
     "spi_op_stem_pool": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int32, C.c_void_p]),
+    "spi_op_stem_pool_u8": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int32,
+                                      C.c_void_p]),
+    "spi_op_patchify": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int32, C.c_void_p]),
     "spi_op_attention": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_void_p]),
     "spi_op_layernorm": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -248,6 +254,16 @@ def _load() -> C.CDLL:
 
 
 lib = _load()
+
+
+def float3(values):
+    """A `const float[3]` argument (per-channel scale / shift); None stays a NULL pointer."""
+    if values is None:
+        return None
+    vals = [float(v) for v in values]
+    if len(vals) != 3:
+        raise ValueError("expected 3 per-channel values")
+    return (C.c_float * 3)(*vals)
 
 
 def last_error() -> str:

@@ -195,6 +195,14 @@ class ModelReplica:
     def set_graphs(self, on: bool) -> None:
         lib.spi_model_set_graphs(self.handle, 1 if on else 0)
 
+    def set_input_transform(self, scale=None, shift=None) -> None:
+        """The per-channel transform of 8-bit image tasks (spi_model_set_input_transform): a uint8
+        pixel p of channel c enters the network as float32(p) * scale[c] + shift[c], two float32
+        roundings.  (None, None) resets to scale 1, shift 0.  Call before serving."""
+        st = lib.spi_model_set_input_transform(self.handle, N.float3(scale), N.float3(shift))
+        if st != N.SPI_OK:
+            raise InferenceExecutionException(f"set_input_transform failed: {N.last_error()}")
+
     def warmup(self, stream: int, batch: int, seq: int = 0, with_mask: bool = True) -> None:
         """Allocate `stream`'s workspace and pre-capture its (batch, seq) graph (per-worker warm-up)."""
         if lib.spi_model_warmup(self.handle, C.c_void_p(stream), batch, seq, int(with_mask)) != N.SPI_OK:
@@ -321,16 +329,37 @@ class TorchCpuForward:
     Mirrors cpu_inference_func's body: views over the buffers, forward under
     InferenceMode, IValue flattening, then copy_output_to_buffer's checks
     (numel, dtype, contiguity, byte size) and memcpy (tensor_builder.cpp:162-190).
+
+    input_transform=(scale, shift): the 8-bit image contract of the GPU codelet
+    (spi_model_set_input_transform).  When input 0 is a 4-D uint8 view, [B,3,H,W] or [B,H,W,3],
+    the module is fed the contiguous fp32 NCHW tensor x.float().mul(scale[c]).add(shift[c]).
+    Without it the byte tensor goes to the module unchanged.
     """
 
-    def __init__(self, module: torch.nn.Module):
+    def __init__(self, module: torch.nn.Module, input_transform=None):
         self.module = module
+        self.input_transform = None
+        if input_transform is not None:
+            scale, shift = (torch.tensor([float(v) for v in t], dtype=torch.float32).reshape(1, 3, 1, 1)
+                            for t in input_transform)
+            if not (torch.isfinite(scale).all() and torch.isfinite(shift).all()):
+                raise InferenceExecutionException("input transform values must be finite")
+            self.input_transform = (scale, shift)
         self._cb = N.CPU_FORWARD_FN(self._call)
         self.handle = C.c_void_p(id(self))
 
     def _call(self, _model, inputs, n_in, outputs, n_out, err, errlen):
         try:
             xs = [_view(inputs[i]) for i in range(n_in)]
+            if self.input_transform is not None and n_in and xs[0].dtype == torch.uint8 and xs[0].dim() == 4:
+                x = xs[0]
+                if x.shape[1] != 3:
+                    if x.shape[3] != 3:
+                        raise InferenceExecutionException(
+                            "[ERROR] Tensor layout mismatch: expected [B,3,H,W] or [B,H,W,3]")
+                    x = x.permute(0, 3, 1, 2)
+                scale, shift = self.input_transform
+                xs[0] = x.float().contiguous().mul(scale).add(shift)
             with torch.inference_mode():
                 result = self.module(*xs)
             outs: list = []

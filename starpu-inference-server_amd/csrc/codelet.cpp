@@ -255,7 +255,8 @@ void spi_hip_inference_func(void** buffers, void* cl_arg) {
     a->worker_id = worker;
     a->device_id = device;
     int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur != m->device()) (void)hipSetDevice(m->device());
+    // (a host-only replica has no device to select; its forward reports that below)
+    if (m->device() >= 0 && hipGetDevice(&cur) == hipSuccess && cur != m->device()) (void)hipSetDevice(m->device());
     a->inference_start_ns = now_ns();
     size_t n_aff = 0;
     if (m->family() == SPI_FAMILY_AFFINE) {
@@ -264,7 +265,7 @@ void spi_hip_inference_func(void** buffers, void* cl_arg) {
       n_aff = (size_t)e;
     }
     const int S = a->num_dims[0] >= 2 ? (int)a->dims[0][1] : 0;
-    m->forward(stream, (int)a->dims[0][0], S, n_aff, in, out);
+    m->forward(stream, (int)a->dims[0][0], S, n_aff, in, out, m->input_kind(*a));
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) throw CodeletError(SPI_ERR_DEVICE, std::string("HIP error: ") + hipGetErrorString(err));
   } catch (const CodeletError& e) {
@@ -402,6 +403,16 @@ int64_t spi_model_launch_table(spi_model* m, void* stream, int64_t batch, int64_
 
 void spi_model_set_graphs(spi_model* m, int32_t on) {
   if (m) m->impl->set_graphs(on != 0);
+}
+
+int spi_model_set_input_transform(spi_model* m, const float scale[3], const float shift[3]) {
+  if (!m) return SPI_ERR_INVALID_ARGUMENT;
+  const int st = m->impl->set_input_transform(scale, shift);
+  if (st == SPI_ERR_UNSUPPORTED)
+    tl_last_error = "input transform: only ResNet / ViT replicas take 8-bit image tasks";
+  else if (st != SPI_OK)
+    tl_last_error = "input transform: scale and shift must both be given (or both null) and finite";
+  return st;
 }
 
 int spi_model_warmup(spi_model* m, void* stream, int64_t batch, int64_t seq, int32_t with_mask) {

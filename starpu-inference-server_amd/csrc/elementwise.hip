@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <stdexcept>
+#include <string>
 
 namespace spi {
 namespace {
@@ -23,10 +24,29 @@ int grid_for(size_t n, int block = 256, int cap = 8192) {
   return (int)std::max<size_t>(1, std::min<size_t>((n + block - 1) / block, cap));
 }
 
-// NCHW fp32 -> NHWC (T) with channel padding; one thread per pixel.
-template <typename T>
-__global__ void ingest_kernel(const float* __restrict__ x, T* __restrict__ y, int B,
-                              int C, int H, int W, int cpad) {
+// An 8-bit pixel of channel c under the input transform (spi_kernels.hpp): one fp32 multiply and
+// one fp32 add, each rounded to nearest, never fused.
+__device__ __forceinline__ float xf_pixel(unsigned char p, const InputXf& xf, int c) {
+  return input_xf_apply(p, xf, c);
+}
+
+// Element (b, c, h, w) of an image of kind SRC ([B][C][H][W] fp32 / bytes, or [B][H][W][C] bytes),
+// as the fp32 value that enters the network.  Byte loads: no alignment is assumed.
+template <int SRC>
+__device__ __forceinline__ float src_pixel(const void* __restrict__ x, const InputXf& xf, size_t b, int c, int C,
+                                           size_t hw, size_t HW) {
+  if constexpr (SRC == kSrcF32Nchw)
+    return static_cast<const float*>(x)[(b * C + c) * HW + hw];
+  else if constexpr (SRC == kSrcU8Nchw)
+    return xf_pixel(static_cast<const unsigned char*>(x)[(b * C + c) * HW + hw], xf, c);
+  else
+    return xf_pixel(static_cast<const unsigned char*>(x)[(b * HW + hw) * C + c], xf, c);
+}
+
+// Image (NCHW fp32, or 8-bit pixels NCHW / NHWC) -> NHWC (T) with channel padding; one thread per pixel.
+template <typename T, int SRC>
+__global__ void ingest_kernel(const void* __restrict__ x, T* __restrict__ y, int B,
+                              int C, int H, int W, int cpad, InputXf xf) {
   const size_t npix = (size_t)B * H * W;
   const size_t HW = (size_t)H * W;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix;
@@ -34,7 +54,7 @@ __global__ void ingest_kernel(const float* __restrict__ x, T* __restrict__ y, in
     const size_t b = i / HW, hw = i - b * HW;
     T* dst = y + i * cpad;
     for (int c = 0; c < cpad; ++c)
-      dst[c] = c < C ? cvt<T>(x[(b * C + c) * HW + hw]) : cvt<T>(0.f);
+      dst[c] = c < C ? cvt<T>(src_pixel<SRC>(x, xf, b, c, C, hw, HW)) : cvt<T>(0.f);
   }
 }
 
@@ -523,9 +543,9 @@ __global__ void mask_bias_kernel(const int64_t* mask, float* bias, int n) {
 }
 
 // ViT patchify: row (b, ph, pw), column c*ps*ps + kh*ps + kw (conv weight flatten order).
-template <typename T>
-__global__ void patchify_kernel(const float* __restrict__ x, T* __restrict__ y, int B,
-                                int C, int H, int W, int ps) {
+template <typename T, int SRC>
+__global__ void patchify_kernel(const void* __restrict__ x, T* __restrict__ y, int B,
+                                int C, int H, int W, int ps, InputXf xf) {
   const int GH = H / ps, GW = W / ps;
   const int K = C * ps * ps;
   const size_t n = (size_t)B * GH * GW * K;
@@ -538,7 +558,7 @@ __global__ void patchify_kernel(const float* __restrict__ x, T* __restrict__ y, 
     const int b = (int)(row / ((size_t)GW * GH));
     const int c = k / (ps * ps);
     const int kh = (k / ps) % ps, kw = k % ps;
-    y[i] = cvt<T>(x[(((size_t)b * C + c) * H + ph * ps + kh) * W + pw * ps + kw]);
+    y[i] = cvt<T>(src_pixel<SRC>(x, xf, (size_t)b, c, C, (size_t)(ph * ps + kh) * W + pw * ps + kw, (size_t)H * W));
   }
 }
 
@@ -570,6 +590,54 @@ __global__ __launch_bounds__(256) void patchify_vec_kernel(const float* __restri
   } else {
     reinterpret_cast<float4*>(dst)[0] = v0;
     reinterpret_cast<float4*>(dst)[1] = v1;
+  }
+}
+
+// The vector form on 8-bit pixels (ps % 8 == 0, 16-byte aligned y; C = 3): the same thread mapping
+// and 16-byte stores -- the stores are 2 or 4 times the bytes of the loads, so they are what the
+// vector form is for.  WIDE (NCHW only; the host checks x % 8 == 0 and W % 8 == 0, which make every
+// (b, c, row, pw ps + 8 seg) offset a multiple of 8): the 8 pixels as one 8-byte load.  Otherwise 8
+// byte loads, 1 (NCHW) or 3 (NHWC) bytes apart, at any alignment.
+template <typename T, int SRC, bool WIDE>
+__global__ __launch_bounds__(256) void patchify_vec_u8_kernel(const unsigned char* __restrict__ x, T* __restrict__ y,
+                                                              int H, int W, int ps, int GH, int GW, int n,
+                                                              InputXf xf) {
+  static_assert(SRC != kSrcF32Nchw && (!WIDE || SRC == kSrcU8Nchw), "8-bit sources; the wide load is NCHW's");
+  constexpr int C = 3;
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const int segs = ps >> 3;
+  const int seg = t % segs;
+  int r = t / segs;
+  const int kh = r % ps;
+  r /= ps;
+  const int c = r % C;
+  const int row = r / C;  // (b, ph, pw)
+  const int pw = row % GW, ph = (row / GW) % GH, b = row / (GW * GH);
+  const int h = ph * ps + kh, w0 = pw * ps + seg * 8;
+  unsigned char px[8];
+  if constexpr (WIDE) {
+    const uint2 raw = *reinterpret_cast<const uint2*>(x + ((size_t)(b * C + c) * H + h) * W + w0);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) px[q] = (unsigned char)((q < 4 ? raw.x : raw.y) >> (8 * (q & 3)));
+  } else {
+    const unsigned char* src = SRC == kSrcU8Nhwc ? x + (((size_t)b * H + h) * W + w0) * C + c
+                                                 : x + ((size_t)(b * C + c) * H + h) * W + w0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) px[q] = src[q * (SRC == kSrcU8Nhwc ? C : 1)];
+  }
+  float v[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) v[q] = xf_pixel(px[q], xf, c);
+  T* dst = y + (size_t)row * (C * ps * ps) + (c * ps + kh) * ps + seg * 8;
+  if constexpr (sizeof(T) == 2) {
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    const h8 o = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3],
+                  (_Float16)v[4], (_Float16)v[5], (_Float16)v[6], (_Float16)v[7]};
+    *reinterpret_cast<h8*>(dst) = o;
+  } else {
+    reinterpret_cast<float4*>(dst)[0] = float4{v[0], v[1], v[2], v[3]};
+    reinterpret_cast<float4*>(dst)[1] = float4{v[4], v[5], v[6], v[7]};
   }
 }
 
@@ -649,15 +717,60 @@ __global__ void affine_kernel(const float* x, float* y, size_t n, float scale, f
 }  // namespace
 
 
-void ingest_nchw(const float* x, void* y, int B, int C, int H, int W, int cpad, bool f16,
-                 hipStream_t s) {
+namespace {
+
+void check_src(const char* op, int src, int C) {
+  if (src < kSrcF32Nchw || src > kSrcU8Nhwc) throw std::invalid_argument(std::string(op) + ": unknown source kind");
+  if (src != kSrcF32Nchw && C != 3) throw std::invalid_argument(std::string(op) + ": 8-bit images have 3 channels");
+}
+
+template <int SRC>
+void ingest_src(const void* x, void* y, int B, int C, int H, int W, int cpad, bool f16, const InputXf& xf,
+                hipStream_t s) {
   const size_t n = (size_t)B * H * W;
   if (f16)
-    SPI_LAUNCH((ingest_kernel<_Float16>), dim3(grid_for(n)), dim3(256), 0, s, x,
-                       (_Float16*)y, B, C, H, W, cpad);
+    SPI_LAUNCH((ingest_kernel<_Float16, SRC>), dim3(grid_for(n)), dim3(256), 0, s, x,
+                       (_Float16*)y, B, C, H, W, cpad, xf);
   else
-    SPI_LAUNCH((ingest_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, x,
-                       (float*)y, B, C, H, W, cpad);
+    SPI_LAUNCH((ingest_kernel<float, SRC>), dim3(grid_for(n)), dim3(256), 0, s, x,
+                       (float*)y, B, C, H, W, cpad, xf);
+}
+
+template <int SRC>
+void patchify_scalar(const void* x, void* y, int B, int C, int H, int W, int ps, bool f16, const InputXf& xf,
+                     hipStream_t s) {
+  const size_t n = (size_t)B * C * H * W;
+  if (f16)
+    SPI_LAUNCH((patchify_kernel<_Float16, SRC>), dim3(grid_for(n)), dim3(256), 0, s, x,
+                       (_Float16*)y, B, C, H, W, ps, xf);
+  else
+    SPI_LAUNCH((patchify_kernel<float, SRC>), dim3(grid_for(n)), dim3(256), 0, s, x,
+                       (float*)y, B, C, H, W, ps, xf);
+}
+
+template <int SRC, bool WIDE>
+void patchify_vec_u8(const void* x, void* y, int H, int W, int ps, int GH, int GW, int nt, bool f16,
+                     const InputXf& xf, hipStream_t s) {
+  const unsigned char* xb = static_cast<const unsigned char*>(x);
+  if (f16)
+    SPI_LAUNCH((patchify_vec_u8_kernel<_Float16, SRC, WIDE>), dim3((nt + 255) / 256), dim3(256), 0, s, xb,
+               (_Float16*)y, H, W, ps, GH, GW, nt, xf);
+  else
+    SPI_LAUNCH((patchify_vec_u8_kernel<float, SRC, WIDE>), dim3((nt + 255) / 256), dim3(256), 0, s, xb, (float*)y, H,
+               W, ps, GH, GW, nt, xf);
+}
+
+}  // namespace
+
+void ingest_nchw(const void* x, void* y, int B, int C, int H, int W, int cpad, bool f16,
+                 hipStream_t s, int src, const InputXf& xf) {
+  check_src("ingest_nchw", src, C);
+  if (src == kSrcU8Nchw)
+    ingest_src<kSrcU8Nchw>(x, y, B, C, H, W, cpad, f16, xf, s);
+  else if (src == kSrcU8Nhwc)
+    ingest_src<kSrcU8Nhwc>(x, y, B, C, H, W, cpad, f16, xf, s);
+  else
+    ingest_src<kSrcF32Nchw>(x, y, B, C, H, W, cpad, f16, xf, s);
 }
 
 void maxpool_nhwc(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, int k,
@@ -756,13 +869,33 @@ void mask_to_bias(const int64_t* mask, float* bias, int n, hipStream_t s) {
   SPI_LAUNCH(mask_bias_kernel, dim3(grid_for(n)), dim3(256), 0, s, mask, bias, n);
 }
 
-void patchify(const float* x, void* y, int B, int C, int H, int W, int ps, bool f16,
-              hipStream_t s) {
+void patchify(const void* xv, void* y, int B, int C, int H, int W, int ps, bool f16,
+              hipStream_t s, int src, const InputXf& xf) {
+  check_src("patchify", src, C);
   const size_t n = (size_t)B * C * H * W;
   const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  const int GH = H / ps, GW = W / ps;
+  const int nt = B * GH * GW * C * ps * (ps / 8);
+  if (src != kSrcF32Nchw) {
+    // 8-bit pixels: the vector form whenever the stores allow it; its loads are one 8-byte vector
+    // per thread only for an NCHW image whose base and row pitch are multiples of 8 bytes
+    if (ps % 8 == 0 && n < (size_t)INT32_MAX && al16(y)) {
+      const bool wide = src == kSrcU8Nchw && W % 8 == 0 && (reinterpret_cast<uintptr_t>(xv) & 7) == 0;
+      if (wide)
+        patchify_vec_u8<kSrcU8Nchw, true>(xv, y, H, W, ps, GH, GW, nt, f16, xf, s);
+      else if (src == kSrcU8Nchw)
+        patchify_vec_u8<kSrcU8Nchw, false>(xv, y, H, W, ps, GH, GW, nt, f16, xf, s);
+      else
+        patchify_vec_u8<kSrcU8Nhwc, false>(xv, y, H, W, ps, GH, GW, nt, f16, xf, s);
+    } else if (src == kSrcU8Nchw) {
+      patchify_scalar<kSrcU8Nchw>(xv, y, B, C, H, W, ps, f16, xf, s);
+    } else {
+      patchify_scalar<kSrcU8Nhwc>(xv, y, B, C, H, W, ps, f16, xf, s);
+    }
+    return;
+  }
+  const float* x = static_cast<const float*>(xv);
   if (ps % 8 == 0 && W % 4 == 0 && n / 8 < (size_t)INT32_MAX && n < (size_t)INT32_MAX && al16(x) && al16(y)) {
-    const int GH = H / ps, GW = W / ps;
-    const int nt = B * GH * GW * C * ps * (ps / 8);
     if (f16)
       SPI_LAUNCH((patchify_vec_kernel<_Float16>), dim3((nt + 255) / 256), dim3(256), 0, s, x, (_Float16*)y, C, H, W,
                  ps, GH, GW, nt);
@@ -771,12 +904,7 @@ void patchify(const float* x, void* y, int B, int C, int H, int W, int ps, bool 
                  GW, nt);
     return;
   }
-  if (f16)
-    SPI_LAUNCH((patchify_kernel<_Float16>), dim3(grid_for(n)), dim3(256), 0, s, x,
-                       (_Float16*)y, B, C, H, W, ps);
-  else
-    SPI_LAUNCH((patchify_kernel<float>), dim3(grid_for(n)), dim3(256), 0, s, x,
-                       (float*)y, B, C, H, W, ps);
+  patchify_scalar<kSrcF32Nchw>(xv, y, B, C, H, W, ps, f16, xf, s);
 }
 
 void vit_assemble(const float* patches, const float* cls, const float* pos, float* x, int B,

@@ -664,11 +664,15 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
     if (in_bytes[0] < (size_t)elems(0) * 4) throw std::runtime_error("[ERROR] Input buffer too small");
     expect_out = (size_t)elems(0) * 4;
   } else if (family_ == SPI_FAMILY_RESNET || family_ == SPI_FAMILY_VIT) {
-    if (a.input_types[0] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Input type mismatch");
-    if (a.num_dims[0] != 4 || a.dims[0][1] != 3 || a.dims[0][2] != image_ || a.dims[0][3] != image_)
-      throw std::runtime_error("[ERROR] Tensor layout mismatch: expected [B,3," + std::to_string(image_) + "," +
-                               std::to_string(image_) + "]");
-    if (in_bytes[0] < (size_t)elems(0) * 4) throw std::runtime_error("[ERROR] Input buffer too small");
+    const bool u8 = a.input_types[0] == SPI_DTYPE_U8;
+    if (!u8 && a.input_types[0] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Input type mismatch");
+    const std::string sz = std::to_string(image_);
+    const bool nchw = a.num_dims[0] == 4 && a.dims[0][1] == 3 && a.dims[0][2] == image_ && a.dims[0][3] == image_;
+    const bool nhwc = a.num_dims[0] == 4 && a.dims[0][1] == image_ && a.dims[0][2] == image_ && a.dims[0][3] == 3;
+    if (!nchw && !(u8 && nhwc))
+      throw std::runtime_error("[ERROR] Tensor layout mismatch: expected [B,3," + sz + "," + sz + "]" +
+                               (u8 ? " or [B," + sz + "," + sz + ",3]" : ""));
+    if (in_bytes[0] < (size_t)elems(0) * (u8 ? 1 : 4)) throw std::runtime_error("[ERROR] Input buffer too small");
     expect_out = (size_t)B * classes_ * 4;
   } else {  // BERT: input_ids [B,S] int64, optional attention_mask [B,S] int64
     for (int i = 0; i < ni; ++i) {
@@ -684,6 +688,28 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
   }
   if (a.output_types[0] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Output type mismatch");
   if (out_bytes[0] != expect_out) throw std::runtime_error("Output buffer size mismatch in bytes");
+}
+
+int Model::input_kind(const spi_codelet_args& a) const {
+  if ((family_ != SPI_FAMILY_RESNET && family_ != SPI_FAMILY_VIT) || a.input_types[0] != SPI_DTYPE_U8)
+    return kSrcF32Nchw;
+  // [B,3,S,S] is NCHW (also when S == 3), else check_io accepted [B,S,S,3]
+  return a.dims[0][1] == 3 && a.dims[0][2] == image_ && a.dims[0][3] == image_ ? kSrcU8Nchw : kSrcU8Nhwc;
+}
+
+int Model::set_input_transform(const float* scale, const float* shift) {
+  if (family_ != SPI_FAMILY_RESNET && family_ != SPI_FAMILY_VIT) return SPI_ERR_UNSUPPORTED;
+  InputXf xf;
+  if (scale || shift) {
+    if (!scale || !shift) return SPI_ERR_INVALID_ARGUMENT;
+    for (int c = 0; c < 3; ++c) {
+      if (!std::isfinite(scale[c]) || !std::isfinite(shift[c])) return SPI_ERR_INVALID_ARGUMENT;
+      xf.scale[c] = scale[c];
+      xf.shift[c] = shift[c];
+    }
+  }
+  input_xf_ = xf;
+  return SPI_OK;
 }
 
 double Model::flops(int64_t B) const {
@@ -1055,7 +1081,10 @@ Workspace* Model::workspace(hipStream_t s) {
 // Forward: prologue (reads the task's input buffers) -> body (workspace only,
 // graph-capturable) -> epilogue (writes the task's output buffer).
 // ---------------------------------------------------------------------------
-void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStream_t s) {
+void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStream_t s, int src) {
+  // src (SrcKind): an 8-bit image task takes the same launch, which then reads bytes and applies
+  // input_xf_ at the load.  The profile hooks always pass fp32 inputs, so the op records' byte
+  // counts stay those of an fp32 image.
   if (family_ == SPI_FAMILY_RESNET && stem_fused_) {
     // the stem reads the task's NCHW buffer itself and writes the pooled map (buf 2)
     const int OH = (image_ + 6 - 7) / 2 + 1, PH = (OH + 2 - 3) / 2 + 1;
@@ -1063,14 +1092,14 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
                             : op_begin(s, "stem_pool", 2.0 * B * OH * OH * stem_.cout * 147.0,
                                        (double)B * 3 * image_ * image_ * 4 + (double)B * PH * PH * stem_.cout * (split_ ? 4 : 2));
     for (int r = 0; r < nrep; ++r)
-      stem_pool(static_cast<const float*>(in[0]), ptr<void>(stem_pool_w_), ptr<float>(stem_.b), w.bufs[2], B, image_,
-                image_, split_ ? 2 : stem_.prec != Prec::F16 ? 1 : 0, split_, stem_pr_, s);
+      stem_pool(in[0], ptr<void>(stem_pool_w_), ptr<float>(stem_.b), w.bufs[2], B, image_, image_,
+                split_ ? 2 : stem_.prec != Prec::F16 ? 1 : 0, split_, stem_pr_, s, src, input_xf_);
     if (prof_) op_end(s);
   } else if (family_ == SPI_FAMILY_RESNET) {
     const int nrep = !prof_ ? 1 : op_begin(s, "ingest_nchw", 0, (double)B * 3 * image_ * image_ * 4 * 2);
     for (int r = 0; r < nrep; ++r)
-      ingest_nchw(static_cast<const float*>(in[0]), w.bufs[0], B, 3, image_, image_, stem_.cin_pad,
-                  stem_.prec == Prec::F16, s);
+      ingest_nchw(in[0], w.bufs[0], B, 3, image_, image_, stem_.cin_pad, stem_.prec == Prec::F16, s, src,
+                  input_xf_);
     if (prof_) op_end(s);
   } else if (family_ == SPI_FAMILY_BERT) {
     const double T = (double)B * S;
@@ -1085,7 +1114,7 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
     });
   } else if (family_ == SPI_FAMILY_VIT) {
     prof_op(s, "patchify", (double)B * 3 * image_ * image_ * (4 + (f16_ ? 2 : 4)),
-            [&] { patchify(static_cast<const float*>(in[0]), w.bufs[0], B, 3, image_, image_, patch_, f16_, s); });
+            [&] { patchify(in[0], w.bufs[0], B, 3, image_, image_, patch_, f16_, s, src, input_xf_); });
   }
 }
 
@@ -1324,7 +1353,7 @@ void Model::epilogue(Workspace& w, int B, int S, void* const* out, hipStream_t s
   }
 }
 
-void Model::forward(hipStream_t s, int B, int S, size_t n, const void* const* in, void* const* out) {
+void Model::forward(hipStream_t s, int B, int S, size_t n, const void* const* in, void* const* out, int src) {
   if (device_ < 0) throw std::runtime_error("host-only replica (device < 0) cannot run a forward");
   if (family_ == SPI_FAMILY_AFFINE) {
     affine(static_cast<const float*>(in[0]), static_cast<float*>(out[0]), n, aff_scale_, aff_shift_, s);
@@ -1332,7 +1361,7 @@ void Model::forward(hipStream_t s, int B, int S, size_t n, const void* const* in
   }
   if (family_ != SPI_FAMILY_BERT) S = 0;  // only BERT's graphs depend on the sequence length
   Workspace* w = workspace(s);
-  prologue(*w, B, S, in, s);
+  prologue(*w, B, S, in, s, src);
   if (graphs_ && s != nullptr) {
     SPI_HIP(hipGraphLaunch(graph(*w, B, S, s), s));
   } else {

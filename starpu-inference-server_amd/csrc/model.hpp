@@ -75,9 +75,17 @@ class Model {
   // with the reference's message wording on mismatch.
   void check_io(const spi_codelet_args& a, const size_t* in_bytes,
                 const size_t* out_bytes) const;
+  // What input 0 of a task that passed check_io holds (SrcKind): fp32 NCHW, or for a ResNet / ViT
+  // task of SPI_DTYPE_U8 the layout its dims name ([B,3,S,S] NCHW, [B,S,S,3] NHWC).
+  int input_kind(const spi_codelet_args& a) const;
+  // The input transform of 8-bit image tasks (spi_model_set_input_transform); null pointers reset
+  // it to scale 1, shift 0.  Returns an spi_status.  Not synchronised with forwards in flight.
+  int set_input_transform(const float* scale, const float* shift);
   // Enqueue the forward on `s`; never synchronises.
-  // S: BERT sequence length (ignored otherwise); n: AFFINE element count.
-  void forward(hipStream_t s, int batch, int S, size_t n, const void* const* in, void* const* out);
+  // S: BERT sequence length (ignored otherwise); n: AFFINE element count; src: input 0's SrcKind
+  // (read by the prologue only -- the captured body does not depend on it).
+  void forward(hipStream_t s, int batch, int S, size_t n, const void* const* in, void* const* out,
+               int src = kSrcF32Nchw);
   // Allocate the stream's workspace and capture its (batch, S, mask) graph ahead of serving.
   void warmup(hipStream_t s, int batch, int S, bool mask);
 
@@ -111,7 +119,7 @@ class Model {
   Workspace* workspace(hipStream_t s);
   hipGraphExec_t graph(Workspace& w, int batch, int S, hipStream_t s);
   void body(Workspace& w, int batch, int S, hipStream_t s);
-  void prologue(Workspace& w, int batch, int S, const void* const* in, hipStream_t s);
+  void prologue(Workspace& w, int batch, int S, const void* const* in, hipStream_t s, int src = kSrcF32Nchw);
   void epilogue(Workspace& w, int batch, int S, void* const* out, hipStream_t s);
   // The LayerNorm fold of one transformer GEMM (ln_fold.hpp).
   struct LnSpec {
@@ -184,6 +192,7 @@ class Model {
   std::vector<ResBlock> blocks_;
   LinearW fc_;
   int image_ = 224, classes_ = 1000, feat_ = 512;
+  InputXf input_xf_;  // ResNet / ViT: the transform of 8-bit image tasks, passed to the prologue's kernel
   // transformers
   int D_ = 768, heads_ = 12, ffn_ = 3072, seq_ = 128, layers_ = 0, vocab_ = 0, maxpos_ = 0;
   float eps_ = 1e-12f;

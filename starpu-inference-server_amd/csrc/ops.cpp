@@ -224,6 +224,49 @@ int spi_op_stem_pool(int32_t precision, const float* x, int32_t B, int32_t H, in
   });
 }
 
+namespace {
+
+// scale / shift: host fp32 [3] each, both null = the default transform
+bool input_xf(const float* scale, const float* shift, spi::InputXf* xf) {
+  if (!scale && !shift) return true;
+  if (!scale || !shift) return false;
+  for (int c = 0; c < 3; ++c) {
+    xf->scale[c] = scale[c];
+    xf->shift[c] = shift[c];
+  }
+  return true;
+}
+
+}  // namespace
+
+int spi_op_stem_pool_u8(int32_t precision, const uint8_t* x, int32_t nhwc, int32_t B, int32_t H, int32_t W,
+                        const void* Wp, const float* bias, const float* scale, const float* shift, void* y,
+                        int32_t rows_per_block, void* stream) {
+  spi::InputXf xf;
+  if (precision < 1 || precision > 4 || !x || !Wp || !bias || !y || B <= 0 || H <= 0 || W <= 0 ||
+      rows_per_block < 0 || rows_per_block > 2 || !input_xf(scale, shift, &xf))
+    return fail("invalid stem_pool_u8 arguments");
+  if ((W + 6 - 7) / 2 + 1 > spi::kStemPoolMaxOW) return fail("stem_pool: image wider than 224");
+  const int lo = precision == 1 ? 0 : precision == 2 ? 1 : 2;  // as spi_op_stem_pool
+  return guarded([&] {
+    spi::stem_pool(x, Wp, bias, y, B, H, W, lo, precision == 3, rows_per_block, static_cast<hipStream_t>(stream),
+                   nhwc ? spi::kSrcU8Nhwc : spi::kSrcU8Nchw, xf);
+    return check_launch();
+  });
+}
+
+int spi_op_patchify(int32_t src_kind, const void* x, int32_t B, int32_t H, int32_t W, int32_t ps, const float* scale,
+                    const float* shift, void* y, int32_t out_f16, void* stream) {
+  spi::InputXf xf;
+  if (src_kind < 0 || src_kind > 2 || !x || !y || B <= 0 || H <= 0 || W <= 0 || ps <= 0 || H % ps || W % ps ||
+      !input_xf(scale, shift, &xf))
+    return fail("invalid patchify arguments");
+  return guarded([&] {
+    spi::patchify(x, y, B, 3, H, W, ps, out_f16 != 0, static_cast<hipStream_t>(stream), src_kind, xf);
+    return check_launch();
+  });
+}
+
 int spi_op_attention(int32_t precision, const void* qkv, const float* mask_bias, void* ctx, int32_t B, int32_t S,
                      int32_t heads, float scale, void* stream) {
   if ((precision != 0 && precision != 1) || !qkv || !ctx || B <= 0 || S <= 0 || heads <= 0)

@@ -89,9 +89,34 @@ void conv_wres_reload_env();
 void attention_reload_env();  // SPI_ATTN_WHOLE
 void qkv_attn_reload_env();   // SPI_QKV_HP
 
-// NCHW fp32 image -> NHWC (compute type) with channels zero-padded to cpad.
-void ingest_nchw(const float* x, void* y, int B, int C, int H, int W, int cpad,
-                 bool f16, hipStream_t s);
+// What an image task's input buffer holds (ResNet / ViT).  The kernels that read it -- the fused
+// stem, ingest_nchw, patchify -- take the kind and, for 8-bit pixels, the per-channel input
+// transform: pixel p of channel c enters the network as fl(fl((float)p * scale[c]) + shift[c]),
+// one fp32 multiply and one fp32 add, each rounded to nearest and never contracted into an FMA.
+// The transform travels as a kernel argument; an fp32 image ignores it.
+enum SrcKind : int { kSrcF32Nchw = 0, kSrcU8Nchw = 1, kSrcU8Nhwc = 2 };
+struct InputXf {
+  float scale[3] = {1.f, 1.f, 1.f};
+  float shift[3] = {0.f, 0.f, 0.f};
+};
+// The transform of one pixel of channel c.  Contraction is switched off for the two operations:
+// HIP compiles with -ffp-contract=fast, under which __fmul_rn / __fadd_rn are a plain * and + that
+// the backend may still fuse; without the contract flag it cannot.  The channel is picked by
+// selects, so the by-value kernel argument stays in scalar registers (no indexed copy in scratch).
+__device__ __forceinline__ float input_xf_apply(unsigned char p, float sc, float sh) {
+#pragma clang fp contract(off)
+  const float m = static_cast<float>(p) * sc;
+  return m + sh;
+}
+__device__ __forceinline__ float input_xf_apply(unsigned char p, const InputXf& xf, int c) {
+  const float sc = c == 0 ? xf.scale[0] : c == 1 ? xf.scale[1] : xf.scale[2];
+  const float sh = c == 0 ? xf.shift[0] : c == 1 ? xf.shift[1] : xf.shift[2];
+  return input_xf_apply(p, sc, sh);
+}
+
+// Image (3 channels for an 8-bit source) -> NHWC (compute type) with channels zero-padded to cpad.
+void ingest_nchw(const void* x, void* y, int B, int C, int H, int W, int cpad,
+                 bool f16, hipStream_t s, int src = kSrcF32Nchw, const InputXf& xf = InputXf{});
 // Fused ResNet stem (stem.hip): NCHW fp32 image [B][3][H][W] -> 7x7/s2/p3 conv
 // (64 output channels, folded BN) + ReLU -> 3x3/s2/p1 max pool -> NHWC [B][PH][PW][64]:
 // fp16 (split false) or the split layout (split true, needs lo).  lo: hi + lo
@@ -101,9 +126,10 @@ constexpr int kStemPoolMaxOW = 112;  // stem output width bound (images up to 22
 constexpr size_t stem_pool_bytes() { return (size_t)2 * 64 * 24 * 8 * sizeof(_Float16); }
 void stem_pool_pack(const float* w_folded /* [64][3][7][7] */, _Float16* dst);
 // lo: 0 fp16 weights, 1 hi + lo weights on the fp16 image (fp16m), 2 hi + lo weights on the split
-// image (fp16x3; required for the split output)
-void stem_pool(const float* x, const void* w, const float* bias, void* y, int B, int H, int W, int lo,
-               bool split, int pr, hipStream_t s);
+// image (fp16x3; required for the split output).  src / xf: the image's kind (above); an 8-bit image
+// is [B][3][H][W] or [B][H][W][3] bytes at any byte address.
+void stem_pool(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int lo,
+               bool split, int pr, hipStream_t s, int src = kSrcF32Nchw, const InputXf& xf = InputXf{});
 // 3x3/s2/p1 max pool on NHWC.
 void maxpool_nhwc(const void* x, void* y, int B, int H, int W, int C, int OH,
                   int OW, int k, int stride, int pad, bool f16, hipStream_t s);
@@ -128,9 +154,9 @@ void bert_embed(const int64_t* ids, const float* word, const float* pos,
                 hipStream_t s, const int64_t* mask = nullptr, float* mask_bias = nullptr);
 // int64 attention mask [B,S] -> additive fp32 bias [B,S] (0 or finfo.min).
 void mask_to_bias(const int64_t* mask, float* bias, int n, hipStream_t s);
-// ViT: NCHW fp32 image -> patch rows [B*P, C*ps*ps] (compute type).
-void patchify(const float* x, void* y, int B, int C, int H, int W, int ps,
-              bool f16, hipStream_t s);
+// ViT: image (NCHW fp32, or 8-bit pixels of kind src, C = 3) -> patch rows [B*P, C*ps*ps] (compute type).
+void patchify(const void* x, void* y, int B, int C, int H, int W, int ps,
+              bool f16, hipStream_t s, int src = kSrcF32Nchw, const InputXf& xf = InputXf{});
 // ViT: x[b, 0] = cls + pos[0]; x[b, 1+p] = patch[b, p] + pos[1+p]  (fp32).
 void vit_assemble(const float* patches, const float* cls, const float* pos,
                   float* x, int B, int P, int D, hipStream_t s);

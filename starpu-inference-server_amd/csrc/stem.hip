@@ -1,4 +1,5 @@
-// Fused ResNet stem for gfx950: the task's NCHW fp32 image -> 7x7/s2/p3 conv +
+// Fused ResNet stem for gfx950: the task's image (NCHW fp32, or 8-bit pixels NCHW /
+// NHWC with the per-channel input transform applied at the load) -> 7x7/s2/p3 conv +
 // folded BN + ReLU -> 3x3/s2/p1 max pool -> the first stage's NHWC activation,
 // in one launch (torchvision's conv1 / bn1 / relu / maxpool; SURVEY.md A14 "cast
 // fused into the first kernel").  It replaces three launches of the generic path
@@ -76,14 +77,21 @@ __device__ __forceinline__ half8 window(const u32x8& b) {
 }
 
 // OUT 0: fp16 NHWC [B][PH][PW][64]; 1: split NHWC (per pixel [32 hi | 32 lo] x 2).
+// SRC (SrcKind) 0: fp32 NCHW image; 1 / 2: 8-bit pixels, NCHW / NHWC -- only the plane fill differs:
+// pixel p of channel c enters as fl(fl(p * scale[c]) + shift[c]) (two fp32 roundings, never an FMA, so
+// a host reproduces it bit for bit) and is rounded to the planes exactly as an fp32 input is.  The
+// bytes are fetched as aligned dwords at any alignment of the image, of a row or of the batch stride
+// (see the fill).  Pixels outside the image enter as 0.0, not as shift[c]: the conv pads the
+// transformed image.
 // LOM 0: fp16 image x fp16 weights (one MFMA per fragment pair); 1: fp16 image x hi + lo weights
 // (two: fp16m, round 5 -- the image's own fp16 rounding costs C2 0.03e-3 of parity margin,
 // tools/prec_emulate.py, and its lo planes + third MFMA a third of the launch); 2: split image x
 // split weights (three: fp16x3, fp32-grade).
-template <int PR, int NW, int LOM, int OUT>
-__global__ __launch_bounds__(64 * NW) void stem_pool_kernel(const float* __restrict__ x, const _Float16* __restrict__ w,
+template <int PR, int NW, int LOM, int OUT, int SRC>
+__global__ __launch_bounds__(64 * NW) void stem_pool_kernel(const void* __restrict__ xv, const _Float16* __restrict__ w,
                                                             const float* __restrict__ bias, void* __restrict__ y, int H,
-                                                            int W, int OH, int OW, int PH, int PW, int diag) {
+                                                            int W, int OH, int OW, int PH, int PW, int diag,
+                                                            InputXf xf) {
   using G = Geom<PR>;
   constexpr int R = G::R, NR = G::NR, WP = G::WP, NPL = G::NPL, PD = G::PD, NT = 64 * NW;
   static_assert(NW == 4 || NW == 8, "4 waves (one per 16 channels), or 8 (x 2 pixel groups)");
@@ -115,39 +123,136 @@ __global__ __launch_bounds__(64 * NW) void stem_pool_kernel(const float* __restr
   // planes: (c, input row ir0 + r) at lds[(c * NR + r) * WP + col + 3]; zero outside
   // the image.  Unrolled: every thread's loads are in flight before the first LDS
   // store (a rolled loop waits out one memory latency per iteration).
-  const float* xb = x + (size_t)b * 3 * H * W;
-  constexpr int HALF = WP / 2, ITER = (NPL * HALF + NT - 1) / NT;
-  float v[ITER][2];
-#pragma unroll
-  for (int it = 0; it < ITER; ++it) {
-    const int e = tid + it * NT;
-    const int p = e / HALF, i = (e - p * HALF) * 2;
-    const int c = p / NR, r = ir0 + (p - c * NR);
-    v[it][0] = v[it][1] = 0.f;
-    if (e < NPL * HALF && r >= 0 && r < H && diag != 1) {
-      const float* row = xb + ((size_t)c * H + r) * W;
-      const int c0 = i - 3;
-      if (c0 >= 0 && c0 < W) v[it][0] = row[c0];
-      if (c0 + 1 >= 0 && c0 + 1 < W) v[it][1] = row[c0 + 1];
-    }
-  }
+  constexpr int HALF = WP / 2;
   unsigned* ldw = lds;
   auto pack2 = [](_Float16 a, _Float16 b) {
     return __builtin_bit_cast(unsigned short, a) | (unsigned)__builtin_bit_cast(unsigned short, b) << 16;
   };
+  if constexpr (SRC == kSrcF32Nchw) {
+    constexpr int ITER = (NPL * HALF + NT - 1) / NT;
+    float v[ITER][2];
+    const float* xb = static_cast<const float*>(xv) + (size_t)b * 3 * H * W;
 #pragma unroll
-  for (int it = 0; it < ITER; ++it) {
-    const int e = tid + it * NT;
-    if (e >= NPL * HALF) continue;
-    const _Float16 h0 = static_cast<_Float16>(v[it][0]), h1 = static_cast<_Float16>(v[it][1]);
-    const unsigned hw = pack2(h0, h1);
-    ldw[e] = hw;
-    if (e) ldw[PD + e - 1] = hw;
-    if constexpr (LO) {
-      const unsigned lw = pack2(static_cast<_Float16>(v[it][0] - static_cast<float>(h0)),
-                                static_cast<_Float16>(v[it][1] - static_cast<float>(h1)));
-      ldw[2 * PD + e] = lw;
-      if (e) ldw[3 * PD + e - 1] = lw;
+    for (int it = 0; it < ITER; ++it) {
+      const int e = tid + it * NT;
+      const int p = e / HALF, i = (e - p * HALF) * 2;
+      const int c = p / NR, r = ir0 + (p - c * NR);
+      v[it][0] = v[it][1] = 0.f;
+      if (e < NPL * HALF && r >= 0 && r < H && diag != 1) {
+        const float* row = xb + ((size_t)c * H + r) * W;
+        const int c0 = i - 3;
+        if (c0 >= 0 && c0 < W) v[it][0] = row[c0];
+        if (c0 + 1 >= 0 && c0 + 1 < W) v[it][1] = row[c0 + 1];
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+      const int e = tid + it * NT;
+      if (e >= NPL * HALF) continue;
+      const _Float16 h0 = static_cast<_Float16>(v[it][0]), h1 = static_cast<_Float16>(v[it][1]);
+      const unsigned hw = pack2(h0, h1);
+      ldw[e] = hw;
+      if (e) ldw[PD + e - 1] = hw;
+      if constexpr (LO) {
+        const unsigned lw = pack2(static_cast<_Float16>(v[it][0] - static_cast<float>(h0)),
+                                  static_cast<_Float16>(v[it][1] - static_cast<float>(h1)));
+        ldw[2 * PD + e] = lw;
+        if (e) ldw[3 * PD + e - 1] = lw;
+      }
+    }
+  } else {
+    // 8-bit pixels.  One wave fills one plane row per step; lane L owns the row's columns
+    // 4 L - 3 .. 4 L, i.e. plane dwords 2 L and 2 L + 1 (64 lanes = the 256-column plane).  Bytes
+    // are fetched as ALIGNED dwords whatever the row's address: with a0 = the row address & 3, the
+    // lane's bytes start `sh` bytes into aligned dword `idx` of the row's first aligned word, so
+    // the lane loads that dword, takes the next from lane + 1 (which loaded it) and extracts its
+    // bytes with one v_alignbyte.  A byte load costs the texture path as much as a dword load, so
+    // this is a quarter of the load instructions of a per-pixel fetch, at any alignment -- rows
+    // that start at odd addresses (W % 4 != 0, odd 3 H W, a sliced buffer) take the same path with
+    // another shift.  Every dword loaded overlaps the row's bytes, so it shares its 4-byte word,
+    // hence its page, with a byte of the image; bytes of it that belong to a neighbouring row (or
+    // lie up to 3 bytes outside the image) are discarded by the per-pixel range test, which also
+    // makes out-of-image pixels 0.0 rather than shift[c].
+    // NHWC: one step is one input row for all three channels -- the lane's 4 pixels are 12
+    // consecutive bytes (3 dwords + the next lane's first), byte k = pixel k / 3, channel k % 3.
+    constexpr bool NHWC = SRC == kSrcU8Nhwc;
+    constexpr int NROW = NHWC ? NR : NPL;  // steps: input rows (NHWC) or planes
+    constexpr int ND = NHWC ? 3 : 1;       // dwords a lane loads per step
+    constexpr int ITER = (NROW * 64 + NT - 1) / NT;
+    const unsigned char* xb = static_cast<const unsigned char*>(xv) + (size_t)b * 3 * H * W;
+    const int rowbytes = NHWC ? 3 * W : W;
+    unsigned raw[ITER][ND];
+    int shv[ITER];
+    // the six transform values in scalar registers once: picked per step by the (wave-uniform)
+    // channel, not fetched from the kernel arguments at each use
+    const float sc0 = xf.scale[0], sc1 = xf.scale[1], sc2 = xf.scale[2];
+    const float sh0 = xf.shift[0], sh1 = xf.shift[1], sh2 = xf.shift[2];
+    // Branch-free loads: a load under a per-lane or per-step condition is waited for at the end of
+    // its block, which serialises the steps on the memory latency.  So every lane loads in every
+    // step, from an address clamped into the image -- the step's row into [0, H), the dword into
+    // those that overlap the row -- and what a clamp substituted feeds only pixels that the range
+    // test below zeroes (a dword that does not overlap the row holds none of its pixels).
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+      const int row = min(wave + it * NW, NROW - 1);  // wave-uniform; a step past the last repeats it
+      const int c = NHWC ? 0 : row / NR, r = min(max(ir0 + (NHWC ? row : row - c * NR), 0), H - 1);
+      const unsigned char* rp = xb + (NHWC ? (size_t)r * rowbytes : ((size_t)c * H + r) * W);
+      const int a0 = (int)(reinterpret_cast<uintptr_t>(rp) & 3);
+      // the lane's first byte (column 4 L - 3) is at aligned byte ND 4 (L - 1) + (a0 + ND)
+      const int idx = ND * (lane - 1) + ((a0 + ND) >> 2);
+      shv[it] = (a0 + ND) & 3;
+      const unsigned* ap = reinterpret_cast<const unsigned*>(rp - a0);
+      const int klast = (a0 + rowbytes - 1) >> 2;  // dwords 0 .. klast overlap the row's bytes
+#pragma unroll
+      for (int d = 0; d < ND; ++d) raw[it][d] = ap[min(max(idx + d, 0), klast)];
+    }
+    // plane dword e of every copy, as the fp32 fill writes it -- without that fill's `if (e)` in front
+    // of the shifted copies: dword 0 (plane 0's columns -3, -2, always 0) then lands on the last
+    // slack dword of the copy before, which the slack fill below zeroes too
+    auto put = [&](int e, float v0, float v1) {
+      const _Float16 h0 = static_cast<_Float16>(v0), h1 = static_cast<_Float16>(v1);
+      const unsigned hw = pack2(h0, h1);
+      ldw[e] = hw;
+      ldw[PD + e - 1] = hw;
+      if constexpr (LO) {
+        const unsigned lw = pack2(static_cast<_Float16>(v0 - static_cast<float>(h0)),
+                                  static_cast<_Float16>(v1 - static_cast<float>(h1)));
+        ldw[2 * PD + e] = lw;
+        ldw[3 * PD + e - 1] = lw;
+      }
+    };
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+      const int row = wave + it * NW;
+      // every lane takes part in the exchange (the step's control flow is wave-uniform); lane 63
+      // gets 0, and its columns (249 ..) are past any image
+      // (DPP wave_shl:1, a VALU move: lane i reads lane i + 1 without the LDS round trip of a
+      // ds_bpermute, which would sit on every step's dependent chain)
+      const unsigned next = (unsigned)__builtin_amdgcn_update_dpp(0, (int)raw[it][0], 0x130, 0xf, 0xf, true);
+      if (row >= NROW) continue;
+      const int c = NHWC ? 0 : row / NR, r = ir0 + (NHWC ? row : row - c * NR);
+      const bool rin = r >= 0 && r < H && diag != 1;
+      unsigned bytes[ND];
+#pragma unroll
+      for (int d = 0; d < ND; ++d)
+        bytes[d] = __builtin_amdgcn_alignbyte(d + 1 < ND ? raw[it][d + 1] : next, raw[it][d], (unsigned)shv[it]);
+      const int c0 = 4 * lane - 3;
+#pragma unroll
+      for (int ch = 0; ch < (NHWC ? 3 : 1); ++ch) {
+        const int cc = NHWC ? ch : c;
+        const float sc = cc == 0 ? sc0 : cc == 1 ? sc1 : sc2, sh = cc == 0 ? sh0 : cc == 1 ? sh1 : sh2;
+        float v[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int k = NHWC ? 3 * t + ch : t;  // byte of the lane's 4 ND bytes
+          const unsigned char px = (unsigned char)(bytes[k >> 2] >> (8 * (k & 3)));
+          const float val = input_xf_apply(px, sc, sh);
+          v[t] = rin && c0 + t >= 0 && c0 + t < W ? val : 0.f;
+        }
+        const int e = ((NHWC ? ch * NR + row : row) * HALF) + 2 * lane;
+        put(e, v[0], v[1]);
+        put(e + 1, v[2], v[3]);
+      }
     }
   }
   if (tid < 33) {  // the slack after the last plane: finite bytes for the discarded rows
@@ -299,9 +404,9 @@ __global__ __launch_bounds__(64 * NW) void stem_pool_kernel(const float* __restr
   }
 }
 
-template <int PR, int NW>
-void launch_pr(const float* x, const _Float16* w, const float* bias, void* y, int B, int H, int W, int OH, int OW,
-               int PH, int PW, int lo, bool split, hipStream_t s) {
+template <int PR, int NW, int SRC>
+void launch_src(const void* x, const _Float16* w, const float* bias, void* y, int B, int H, int W, int OH, int OW,
+                int PH, int PW, int lo, bool split, const InputXf& xf, hipStream_t s) {
   // diagnostic builds only (-DSPI_STEM_DIAG=1: no image loads, 2: fill only, 3: empty)
 #ifdef SPI_STEM_DIAG
   constexpr int diag = SPI_STEM_DIAG;
@@ -310,13 +415,28 @@ void launch_pr(const float* x, const _Float16* w, const float* bias, void* y, in
 #endif
   const dim3 grid((PH + PR - 1) / PR, B), block(64 * NW);
   if (split)
-    SPI_LAUNCH((stem_pool_kernel<PR, NW, 2, 1>), grid, block, 0, s, x, w, bias, y, H, W, OH, OW, PH, PW, diag);
+    SPI_LAUNCH((stem_pool_kernel<PR, NW, 2, 1, SRC>), grid, block, 0, s, x, w, bias, y, H, W, OH, OW, PH, PW, diag,
+               xf);
   else if (lo == 2)
-    SPI_LAUNCH((stem_pool_kernel<PR, NW, 2, 0>), grid, block, 0, s, x, w, bias, y, H, W, OH, OW, PH, PW, diag);
+    SPI_LAUNCH((stem_pool_kernel<PR, NW, 2, 0, SRC>), grid, block, 0, s, x, w, bias, y, H, W, OH, OW, PH, PW, diag,
+               xf);
   else if (lo == 1)
-    SPI_LAUNCH((stem_pool_kernel<PR, NW, 1, 0>), grid, block, 0, s, x, w, bias, y, H, W, OH, OW, PH, PW, diag);
+    SPI_LAUNCH((stem_pool_kernel<PR, NW, 1, 0, SRC>), grid, block, 0, s, x, w, bias, y, H, W, OH, OW, PH, PW, diag,
+               xf);
   else
-    SPI_LAUNCH((stem_pool_kernel<PR, NW, 0, 0>), grid, block, 0, s, x, w, bias, y, H, W, OH, OW, PH, PW, diag);
+    SPI_LAUNCH((stem_pool_kernel<PR, NW, 0, 0, SRC>), grid, block, 0, s, x, w, bias, y, H, W, OH, OW, PH, PW, diag,
+               xf);
+}
+
+template <int PR, int NW>
+void launch_pr(const void* x, const _Float16* w, const float* bias, void* y, int B, int H, int W, int OH, int OW,
+               int PH, int PW, int lo, bool split, int src, const InputXf& xf, hipStream_t s) {
+  if (src == kSrcU8Nchw)
+    launch_src<PR, NW, kSrcU8Nchw>(x, w, bias, y, B, H, W, OH, OW, PH, PW, lo, split, xf, s);
+  else if (src == kSrcU8Nhwc)
+    launch_src<PR, NW, kSrcU8Nhwc>(x, w, bias, y, B, H, W, OH, OW, PH, PW, lo, split, xf, s);
+  else
+    launch_src<PR, NW, kSrcF32Nchw>(x, w, bias, y, B, H, W, OH, OW, PH, PW, lo, split, xf, s);
 }
 
 }  // namespace
@@ -334,22 +454,23 @@ void stem_pool_pack(const float* w, _Float16* dst) {
       }
 }
 
-void stem_pool(const float* x, const void* w, const float* bias, void* y, int B, int H, int W, int lo, bool split,
-               int pr, hipStream_t s) {
+void stem_pool(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int lo, bool split,
+               int pr, hipStream_t s, int src, const InputXf& xf) {
   const int OH = (H + 6 - 7) / 2 + 1, OW = (W + 6 - 7) / 2 + 1;
   const int PH = (OH + 2 - 3) / 2 + 1, PW = (OW + 2 - 3) / 2 + 1;
   if (OW > kStemPoolMaxOW || OH < 1 || OW < 1 || B < 1) throw std::runtime_error("stem_pool: unsupported image size");
   if (split && lo != 2) throw std::runtime_error("stem_pool: split output needs the split image and weights");
   if (lo < 0 || lo > 2) throw std::runtime_error("stem_pool: lo is 0, 1 or 2");
+  if (src < kSrcF32Nchw || src > kSrcU8Nhwc) throw std::runtime_error("stem_pool: unknown source kind");
   const _Float16* wp = static_cast<const _Float16*>(w);
   // pr: 1 / 2 pooled rows per 4-wave workgroup; 0 (default): two rows per 8-wave
   // workgroup (one 64-pixel group per wave) when the map has two groups, else 1 x 4 waves
   if (pr == 2)
-    launch_pr<2, 4>(x, wp, bias, y, B, H, W, OH, OW, PH, PW, lo, split, s);
+    launch_pr<2, 4>(x, wp, bias, y, B, H, W, OH, OW, PH, PW, lo, split, src, xf, s);
   else if (pr == 1 || OW <= 64)
-    launch_pr<1, 4>(x, wp, bias, y, B, H, W, OH, OW, PH, PW, lo, split, s);
+    launch_pr<1, 4>(x, wp, bias, y, B, H, W, OH, OW, PH, PW, lo, split, src, xf, s);
   else
-    launch_pr<2, 8>(x, wp, bias, y, B, H, W, OH, OW, PH, PW, lo, split, s);
+    launch_pr<2, 8>(x, wp, bias, y, B, H, W, OH, OW, PH, PW, lo, split, src, xf, s);
 }
 
 }  // namespace spi

@@ -32,6 +32,9 @@ struct spi_torch_module {
   std::vector<std::string> names;
   std::vector<at::Tensor> tensors;
   std::vector<spi_named_tensor> views;
+  // spi_torch_set_input_transform: 8-bit image inputs are fed as the transformed fp32 NCHW tensor
+  bool xf_set = false;
+  float xf_scale[3] = {1.f, 1.f, 1.f}, xf_shift[3] = {0.f, 0.f, 0.f};
 };
 
 namespace {
@@ -130,7 +133,19 @@ int spi_torch_cpu_forward(void* model_cpu, const spi_tensor_view* inputs, int ni
     for (int i = 0; i < ni; ++i) {
       // assign_tensor_view: non-owning row-major view, dims from the layout
       std::vector<int64_t> dims(inputs[i].shape, inputs[i].shape + inputs[i].ndim);
-      args.emplace_back(torch::from_blob(inputs[i].data, dims, torch::TensorOptions().dtype(to_scalar(inputs[i].dtype))));
+      at::Tensor t = torch::from_blob(inputs[i].data, dims, torch::TensorOptions().dtype(to_scalar(inputs[i].dtype)));
+      if (i == 0 && m->xf_set && inputs[i].dtype == SPI_DTYPE_U8 && inputs[i].ndim == 4) {
+        // the GPU codelet's 8-bit image contract (spi_model_set_input_transform): [B,3,S,S] is NCHW,
+        // [B,S,S,3] NHWC; fl(fl(p * scale[c]) + shift[c]) as two ATen ops, so never an FMA
+        if (dims[1] != 3) {
+          if (dims[3] != 3) throw std::runtime_error("[ERROR] Tensor layout mismatch: expected [B,3,H,W] or [B,H,W,3]");
+          t = t.permute({0, 3, 1, 2});
+        }
+        const at::Tensor sc = torch::from_blob(m->xf_scale, {1, 3, 1, 1}, torch::kFloat);
+        const at::Tensor sh = torch::from_blob(m->xf_shift, {1, 3, 1, 1}, torch::kFloat);
+        t = t.to(at::kFloat).contiguous().mul(sc).add(sh);
+      }
+      args.emplace_back(std::move(t));
     }
     const c10::IValue result = m->module.forward(args);
     std::vector<at::Tensor> outs;
@@ -158,6 +173,22 @@ int spi_torch_cpu_forward(void* model_cpu, const spi_tensor_view* inputs, int ni
     put_err(err, errlen, msg);
     return 1;
   }
+}
+
+int spi_torch_set_input_transform(spi_torch_module* m, const float scale[3], const float shift[3]) {
+  if (!m || (!scale != !shift)) return SPI_ERR_INVALID_ARGUMENT;
+  if (!scale) {
+    m->xf_set = false;
+    return SPI_OK;
+  }
+  for (int c = 0; c < 3; ++c)
+    if (!std::isfinite(scale[c]) || !std::isfinite(shift[c])) return SPI_ERR_INVALID_ARGUMENT;
+  for (int c = 0; c < 3; ++c) {
+    m->xf_scale[c] = scale[c];
+    m->xf_shift[c] = shift[c];
+  }
+  m->xf_set = true;
+  return SPI_OK;
 }
 
 int32_t spi_torch_named_tensors(spi_torch_module* m, const spi_named_tensor** out) {

@@ -37,6 +37,7 @@ _PROTOS = {
     "spi_torch_free": (None, [C.c_void_p]),
     "spi_torch_cpu_forward": (C.c_int, [C.c_void_p, C.POINTER(N.TensorView), C.c_int, C.POINTER(N.TensorView),
                                         C.c_int, C.c_char_p, C.c_size_t]),
+    "spi_torch_set_input_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "spi_torch_named_tensors": (C.c_int32, [C.c_void_p, C.POINTER(C.POINTER(N.NamedTensor))]),
     "spi_torch_create_replica": (C.c_void_p, [C.c_void_p, C.c_int32, C.POINTER(N.ModelConfig), C.c_char_p,
                                               C.c_size_t]),
@@ -86,6 +87,12 @@ class TorchScriptModule:
         self.handle = C.c_void_p(h)
         # What InferenceParams.to_args puts in cl_arg: model_cpu + cpu_forward.
         self._cb = C.cast(lib.spi_torch_cpu_forward, N.CPU_FORWARD_FN)
+
+    def set_input_transform(self, scale=None, shift=None) -> None:
+        """8-bit image inputs of the CPU codelet (spi_torch_set_input_transform): a 4-D uint8 input 0
+        is fed to the module as float32(p) * scale[c] + shift[c] in NCHW.  (None, None) clears it."""
+        if lib.spi_torch_set_input_transform(self.handle, N.float3(scale), N.float3(shift)) != N.SPI_OK:
+            raise InferenceExecutionException("set_input_transform: three finite values each for scale and shift")
 
     def named_tensors(self) -> list[tuple[str, tuple]]:
         arr = C.POINTER(N.NamedTensor)()

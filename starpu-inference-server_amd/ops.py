@@ -159,6 +159,51 @@ def stem_pool(prec, x_nchw, w_folded, bias, rows_per_block=0, stream=None):
     return out
 
 
+def stem_pool_u8(prec, x_u8, w_folded, bias, scale=None, shift=None, nhwc=False, rows_per_block=0, stream=None):
+    """stem_pool on 8-bit pixels: x_u8 uint8 [B][3][H][W], or [B][H][W][3] with nhwc; a pixel p of
+    channel c enters as float32(p) * scale[c] + shift[c] (default 1, 0).  x_u8 may start at any byte
+    address (a slice of a larger buffer), but must be contiguous."""
+    if x_u8.dtype != torch.uint8 or not x_u8.is_contiguous():
+        raise OpError("stem_pool_u8: a contiguous uint8 tensor")
+    if nhwc:
+        B, H, W_, _ = x_u8.shape
+    else:
+        B, _, H, W_ = x_u8.shape
+    oh, ow = (H - 1) // 2 + 1, (W_ - 1) // 2 + 1
+    ph, pw = (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
+    w = np.ascontiguousarray(np.asarray(w_folded.cpu() if isinstance(w_folded, torch.Tensor) else w_folded,
+                                        dtype=np.float32))
+    host = np.empty(lib.spi_op_stem_pool_bytes(), dtype=np.uint8)
+    _check(lib.spi_op_stem_pool_pack(w.ctypes.data, host.ctypes.data))
+    wp = torch.from_numpy(host).to(x_u8.device)
+    out = torch.empty(B, ph, pw, 64, device=x_u8.device, dtype=torch.float32 if prec == "fp16x3s" else torch.float16)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(lib.spi_op_stem_pool_u8(STEM_PREC[prec], _ptr(x_u8), int(nhwc), B, H, W_, _ptr(wp), _ptr(bias),
+                                   N.float3(scale), N.float3(shift), _ptr(out), rows_per_block, C.c_void_p(s)))
+    return out
+
+
+SRC_KIND = {"fp32": 0, "u8_nchw": 1, "u8_nhwc": 2}
+
+
+def patchify(src_kind, x, ps, scale=None, shift=None, out_f16=False, stream=None):
+    """ViT patchify of a 3-channel image: fp32 [B][3][H][W] ("fp32"), uint8 [B][3][H][W] ("u8_nchw") or
+    uint8 [B][H][W][3] ("u8_nhwc", both under the scale / shift transform) -> [B (H/ps) (W/ps)][3 ps ps]
+    fp32 or fp16, column c ps ps + kh ps + kw."""
+    if not x.is_contiguous() or x.dtype != (torch.float32 if src_kind == "fp32" else torch.uint8):
+        raise OpError("patchify: a contiguous tensor of the source kind's element type")
+    if src_kind == "u8_nhwc":
+        B, H, W_, _ = x.shape
+    else:
+        B, _, H, W_ = x.shape
+    out = torch.empty(B * (H // ps) * (W_ // ps), 3 * ps * ps, device=x.device,
+                      dtype=torch.float16 if out_f16 else torch.float32)
+    s = torch.cuda.current_stream().cuda_stream if stream is None else stream
+    _check(lib.spi_op_patchify(SRC_KIND[src_kind], _ptr(x), B, H, W_, ps, N.float3(scale), N.float3(shift),
+                               _ptr(out), int(out_f16), C.c_void_p(s)))
+    return out
+
+
 # ---- LayerNorm folded across GEMMs (spi_ops.h: spi_op_fold_linear / spi_op_gemm_ln / ..._planes) ----
 
 KIND = {None: 0, "none": 0, "fp16": 1, "fp32": 2, "planes": 3}  # SPI_KIND_*
