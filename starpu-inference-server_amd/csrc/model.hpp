@@ -1,58 +1,37 @@
 // Device-resident model replica: the MI355X replacement for the per-device
-// TorchScript clones of inference_runner.cpp:251-275.  Weights are recognised
-// by their torchvision / HF parameter names, BN is folded into the convs, every
-// contraction weight is packed [Npad][Kpad] in the compute type, and the whole
-// replica lives in one HBM blob.  Activations live in per-stream workspaces
-// (one per StarPU worker stream: replicas are shared read-only by the workers
-// of a device, starpu_setup.cpp:725-778 / docs/server_guide.md:116).
+// TorchScript clones of inference_runner.cpp:251-275.  The weights are recognised, folded and
+// packed on the host (model_pack.hpp) and the whole replica lives in one HBM blob.
+// Activations live in per-stream workspaces (one per StarPU worker stream: replicas are
+// shared read-only by the workers of a device, starpu_setup.cpp:725-778 /
+// docs/server_guide.md:116).  Layers: packer (model_pack.cpp) -> replica, workspaces and
+// launch helpers -> per-family forward plans (model.cpp) -> profiling hooks (model_profile.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <map>
 #include <memory>
 #include <mutex>
+#include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
-#include "../../include/spi_codelet.h"
+#include "model_pack.hpp"
 #include "spi_kernels.hpp"
 
+#define SPI_HIP(x)                                                                  \
+  do {                                                                              \
+    hipError_t e__ = (x);                                                           \
+    if (e__ != hipSuccess)                                                          \
+      throw std::runtime_error(std::string("HIP error: ") + hipGetErrorString(e__) + \
+                               " at " #x);                                          \
+  } while (0)
+
+#ifndef SPI_STEM_PR  // variant builds: 1 / 2 pooled rows per 4-wave workgroup (stem.hip)
+#define SPI_STEM_PR 0
+#endif
+
 namespace spi {
-
-struct ConvW {
-  size_t w = 0, b = 0;  // blob offsets (packed weight, fp32 bias)
-  int cout = 0, cin = 0, cin_pad = 0, kh = 1, kw = 1, stride = 1, pad = 0;
-  int kpad = 0, npad = 0;
-  size_t wplane = 0;
-  Prec prec = Prec::F16;  // packing / contraction precision of this conv
-  int krep = 1;           // 2: hi + lo weight steps per A step (GemmDesc::krep; SPI_PREC_F16M)
-  bool w_image = false;   // the packed rows 64..127 hold conv_wres's LDS image (GemmDesc::w_image)
-};
-
-struct LinearW {
-  size_t w = 0, b = 0;
-  size_t c1 = 0;  // LayerNorm fold (GemmDesc::ln_in_chunks): sum_k W'[n][k] of the folded weights, else 0
-  int n = 0, k = 0, kpad = 0, npad = 0;
-  size_t wplane = 0;
-  bool has_bias = true;
-  Prec prec = Prec::F16;
-  int krep = 1;
-};
-
-struct LnW {
-  size_t g = 0, b = 0;
-};
-
-struct ResBlock {
-  ConvW c1, c2, c3;  // c3 only for bottleneck
-  bool has_ds = false;
-  ConvW ds;  // SPI_PREC_F16M: packed hi + lo (krep = 2), fp32 output
-};
-
-struct TfLayer {  // BERT (post-LN) / ViT (pre-LN) encoder layer
-  LinearW qkv, out, ff1, ff2;
-  LnW ln1, ln2;
-};
 
 struct Workspace;
 
@@ -62,12 +41,12 @@ class Model {
   ~Model();
 
   int device() const { return device_; }
-  int family() const { return family_; }
-  bool f16() const { return f16_; }
-  int max_batch() const { return max_batch_; }
-  size_t weight_bytes() const { return blob_bytes_; }
-  uint64_t weight_digest() const { return digest_; }
-  const std::string& describe() const { return desc_; }
+  int family() const { return m_.family; }
+  bool f16() const { return m_.f16; }
+  int max_batch() const { return m_.max_batch; }
+  size_t weight_bytes() const { return m_.blob_bytes; }
+  uint64_t weight_digest() const { return m_.digest; }
+  const std::string& describe() const { return m_.desc; }
   double flops(int64_t batch) const;
   void set_graphs(bool on) { graphs_ = on; }
 
@@ -107,20 +86,27 @@ class Model {
   int profile_op(hipStream_t s, int batch, int S, const void* const* in, void* const* out, const char* name,
                  int reps, float* ms, double* flops, double* bytes);
 
-  // Output element count per sample (for size checks).
-  size_t out_elems_per_sample() const;
-  int num_inputs_min() const;
-  int num_inputs_max() const;
-
  private:
-  void build_resnet(const std::map<std::string, const spi_named_tensor*>& p);
-  void build_bert(const std::map<std::string, const spi_named_tensor*>& p);
-  void build_vit(const std::map<std::string, const spi_named_tensor*>& p);
+  int num_inputs_max() const { return m_.family == SPI_FAMILY_BERT ? 2 : 1; }
   Workspace* workspace(hipStream_t s);
   hipGraphExec_t graph(Workspace& w, int batch, int S, hipStream_t s);
-  void body(Workspace& w, int batch, int S, hipStream_t s);
+  // Forward: prologue (reads the task's input buffers) -> body (workspace only, graph-capturable)
+  // -> epilogue (writes the task's output buffer); each dispatches once to its family's plan.
   void prologue(Workspace& w, int batch, int S, const void* const* in, hipStream_t s, int src = kSrcF32Nchw);
+  void body(Workspace& w, int batch, int S, hipStream_t s);
   void epilogue(Workspace& w, int batch, int S, void* const* out, hipStream_t s);
+  // Bytes per workspace buffer of the family (indexed by its buffer enum, model.cpp) at max_batch;
+  // raises `partial` to the split-K slab floats its GEMMs need.
+  std::vector<size_t> workspace_sizes_resnet(size_t& partial) const;
+  std::vector<size_t> workspace_sizes_bert(size_t& partial) const;
+  std::vector<size_t> workspace_sizes_vit(size_t& partial) const;
+  void prologue_resnet(Workspace& w, int B, const void* x, hipStream_t s, int src);
+  void body_resnet(Workspace& w, int B, hipStream_t s);
+  void body_bert(Workspace& w, int B, int S, hipStream_t s);
+  void body_bert_folded(Workspace& w, int B, int S, hipStream_t s);
+  void body_vit(Workspace& w, int B, hipStream_t s);
+  void body_vit_folded(Workspace& w, int B, hipStream_t s);
+  void epilogue_bert(Workspace& w, int B, int S, void* out, hipStream_t s);
   // The LayerNorm fold of one transformer GEMM (ln_fold.hpp).
   struct LnSpec {
     const float* in_stats = nullptr;  // A rows are pre-LN: their chunk statistics (L.c1 folded in)
@@ -140,11 +126,10 @@ class Model {
   void run_conv(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW,
                 Act act, const void* res, Workspace& ws, hipStream_t s, bool out_f32 = false,
                 bool res_f32 = false);
-  struct ConvCall {
+  struct ConvCall {  // the op's name (conv_name) is built only while profiling
     GemmDesc d;
     GemmPtrs p;
     Prec prec = Prec::F16;
-    std::string name;
     double flops = 0, bytes = 0;
   };
   ConvCall conv_call(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW, Act act,
@@ -155,66 +140,30 @@ class Model {
   void run_pooled_fc(const void* act, int B, int hw, void* out, Workspace& ws, hipStream_t s);
   size_t conv_partial(const ConvW& c, int B, int H, int W) const;
   size_t linear_partial(const LinearW& L, int M) const;
+  size_t layers_partial(int T) const;  // the encoder layers' four GEMMs over T rows
   GemmDesc pooled_fc_desc(int B, int hw) const;  // avgpool + FC as one GEMM (pool_rows = hw)
   template <typename P>
   const P* ptr(size_t off) const {
     return reinterpret_cast<const P*>(static_cast<const char*>(dblob_) + off);
   }
+  // The pointers of one GEMM / conv launch: weight and bias at their blob offsets, the stream's
+  // split-K workspace, and the blob's leading zero line.
+  GemmPtrs gemm_ptrs(const void* A, size_t w, size_t bias, const void* res, void* C, const Workspace& ws) const;
 
   int device_ = 0;
-  int family_ = 0;
-  Prec prec_ = Prec::F16;
-  bool f16_ = true;  // activations stored as fp16 (Prec::F16 only)
-  bool mixed_ = false;  // SPI_PREC_F16M on a ResNet (stem in F16X3, downsample + FC with krep = 2)
-  // ResNet under Prec::F16X3: conv outputs / pool inputs in the split layout
-  // (GemmDesc::a_split), so the GEMM main loop never splits A on the VALU.
-  bool split_ = false;
-  int max_batch_ = 1;
+  PackedModel m_;  // what the packer recognised and laid out; its host blob is dropped after the upload
   bool graphs_ = false;
-  std::string desc_;
-  std::vector<char> hblob_;
   void* dblob_ = nullptr;
-  size_t blob_bytes_ = 0;
-  uint64_t digest_ = 0;
-
-  // AFFINE
-  float aff_scale_ = 1.f, aff_shift_ = 0.f;
-  // ResNet
-  bool bottleneck_ = false;
-  std::vector<int> stage_blocks_;
-  ConvW stem_;
-  bool stem_fused_ = false;  // stem + max pool in one launch on the NCHW input (stem.hip)
-#ifndef SPI_STEM_PR  // variant builds: 1 / 2 pooled rows per 4-wave workgroup (stem.hip)
-#define SPI_STEM_PR 0
-#endif
-  int stem_pr_ = SPI_STEM_PR;  // its workgroup shape (0 = auto, stem.hip)
-  size_t stem_pool_w_ = 0;   // its weights, [hi | lo][64][24][8] fp16
-  std::vector<ResBlock> blocks_;
-  LinearW fc_;
-  int image_ = 224, classes_ = 1000, feat_ = 512;
+  int stem_pr_ = SPI_STEM_PR;  // the fused stem's workgroup shape (0 = auto, stem.hip)
   InputXf input_xf_;  // ResNet / ViT: the transform of 8-bit image tasks, passed to the prologue's kernel
-  // transformers
-  int D_ = 768, heads_ = 12, ffn_ = 3072, seq_ = 128, layers_ = 0, vocab_ = 0, maxpos_ = 0;
-  float eps_ = 1e-12f;
-  // LayerNorm folded across the GEMMs (fp16, D and FFN multiples of 128; SPI_LN_FOLD=0: the
-  // separate LayerNorm launches): no LN launch inside the encoder stack
-  bool ln_fold_ = false;
   // SPI_QKV_ATTN: 0 the QKV GEMM + attention launches (A/B); 1 (default) the fused kernel for S <= 128;
   // 2 also for 129..256 tokens (ViT-L at 197: correct, but -4 % under the four streams)
   int qkv_fused_ = 1;
-  size_t word_ = 0, pos_ = 0, type0_ = 0;
-  LnW emb_ln_, final_ln_;
-  std::vector<TfLayer> tf_;
-  // ViT
-  int patch_ = 16, npatch_ = 196;
-  LinearW patch_proj_, head_;
-  size_t cls_ = 0, vpos_ = 0;
 
   std::mutex mu_;
   std::map<hipStream_t, std::unique_ptr<Workspace>> ws_;
   void run_profiled(hipStream_t s, int B, int S, const void* const* in, void* const* out, std::vector<OpRecord>& recs);
-  // Set only inside profile(), on the profiling thread: forwards running on
-  // other worker threads at the same time never see it.
+  // Set only inside profile(), on the profiling thread: concurrent forwards on other threads never see it.
   static thread_local std::vector<OpRecord>* prof_;
   struct ProfRepeat {
     std::string name;
@@ -226,19 +175,21 @@ class Model {
   // profile_op's repeat count for the op it names).
   int op_begin(hipStream_t s, const std::string& name, double flops, double bytes);
   void op_end(hipStream_t s);
-  // Profiled launch (bytes = algorithmic traffic); a plain call when not profiling.
-  template <typename F>
-  void prof_op(hipStream_t s, const char* name, double bytes, F&& launch) {
-    const int nrep = prof_ ? op_begin(s, name, 0, bytes) : 1;
+  // Profiled launch (bytes = algorithmic traffic); a plain call when not profiling.  `name` is a
+  // string literal or a callable returning the name, which runs only while profiling.
+  template <typename N, typename F>
+  void prof_op(hipStream_t s, N&& name, double flops, double bytes, F&& launch) {
+    if (!prof_) return launch();
+    int nrep;
+    if constexpr (std::is_invocable_v<N>) nrep = op_begin(s, name(), flops, bytes);
+    else nrep = op_begin(s, name, flops, bytes);
     for (int r = 0; r < nrep; ++r) launch();
-    if (prof_) op_end(s);
+    op_end(s);
   }
-  // LayerNorm over rows x D_: fp32 in + fp32 out (+ compute-type copy).
+  // LayerNorm over rows x D: fp32 in + fp32 out (+ compute-type copy).
   double ln_bytes(double rows, bool f32_out) const {
-    return rows * D_ * (4 + (f32_out ? 4 : 0) + (f16_ ? 2 : (f32_out ? 0 : 4)));
+    return rows * m_.D * (4 + (f32_out ? 4 : 0) + (m_.f16 ? 2 : (f32_out ? 0 : 4)));
   }
-
-  friend struct Workspace;
 };
 
 }  // namespace spi

@@ -1,0 +1,94 @@
+// Host-only weight packer of a model replica: recognise the torchvision / HF parameter names, fold
+// BN (and, on the fp16 transformers, the LayerNorms) into the weights, pack every contraction weight
+// [Npad][Kpad] in the compute type, and lay everything out in one blob.  Plain data in, plain data
+// out, no HIP: Model (model.hpp) uploads the blob and runs the forward plans over the offset tables.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/spi_codelet.h"
+#include "gemm_desc.hpp"
+
+namespace spi {
+
+struct ConvW {
+  size_t w = 0, b = 0;  // blob offsets (packed weight, fp32 bias)
+  int cout = 0, cin = 0, cin_pad = 0, kh = 1, kw = 1, stride = 1, pad = 0;
+  int kpad = 0, npad = 0;
+  size_t wplane = 0;
+  Prec prec = Prec::F16;  // packing / contraction precision of this conv
+  int krep = 1;           // 2: hi + lo weight steps per A step (GemmDesc::krep; SPI_PREC_F16M)
+  bool w_image = false;   // the packed rows 64..127 hold conv_wres's LDS image (GemmDesc::w_image)
+};
+
+struct LinearW {
+  size_t w = 0, b = 0;
+  size_t c1 = 0;  // LayerNorm fold (GemmDesc::ln_in_chunks): sum_k W'[n][k] of the folded weights, else 0
+  int n = 0, k = 0, kpad = 0, npad = 0;
+  size_t wplane = 0;
+  bool has_bias = true;
+  Prec prec = Prec::F16;
+  int krep = 1;
+};
+
+struct LnW {
+  size_t g = 0, b = 0;
+};
+
+struct ResBlock {
+  ConvW c1, c2, c3;  // c3 only for bottleneck
+  bool has_ds = false;
+  ConvW ds;  // SPI_PREC_F16M: packed hi + lo (krep = 2), fp32 output
+};
+
+struct TfLayer {  // BERT (post-LN) / ViT (pre-LN) encoder layer
+  LinearW qkv, out, ff1, ff2;
+  LnW ln1, ln2;
+};
+
+struct PackedModel {
+  int family = 0;
+  Prec prec = Prec::F16;
+  bool f16 = true;     // activations stored as fp16 (Prec::F16 only)
+  bool mixed = false;  // SPI_PREC_F16M: ResNet stem in F16X3 + downsample hi + lo; transformers: hi + lo on every GEMM
+  // ResNet under Prec::F16X3: conv outputs / pool inputs in the split layout
+  // (GemmDesc::a_split), so the GEMM main loop never splits A on the VALU.
+  bool split = false;
+  int max_batch = 1;
+  // AFFINE
+  float aff_scale = 1.f, aff_shift = 0.f;
+  // ResNet
+  bool bottleneck = false;
+  std::vector<int> stage_blocks;
+  ConvW stem;
+  bool stem_fused = false;  // stem + max pool in one launch on the NCHW input (stem.hip)
+  size_t stem_pool_w = 0;   // its weights, [hi | lo][64][24][8] fp16
+  std::vector<ResBlock> blocks;
+  LinearW fc;
+  int image = 224, classes = 1000, feat = 512;
+  // transformers
+  int D = 768, heads = 12, ffn = 3072, seq = 128, layers = 0, vocab = 0, maxpos = 0;
+  float eps = 1e-12f;
+  // LayerNorm folded across the GEMMs (fp16, D and FFN multiples of 128; SPI_LN_FOLD=0: the
+  // separate LayerNorm launches): no LN launch inside the encoder stack
+  bool ln_fold = false;
+  size_t word = 0, pos = 0, type0 = 0;
+  LnW emb_ln, final_ln;
+  std::vector<TfLayer> tf;
+  // ViT
+  int patch = 16, npatch = 196;
+  LinearW patch_proj, head;
+  size_t cls = 0, vpos = 0;
+
+  std::string desc;
+  uint64_t digest = 0;  // FNV-1a 64 of the blob
+  size_t blob_bytes = 0;
+  std::vector<char> blob;  // starts with a zeroed 256-byte line; Model drops it after the upload
+};
+
+// Throws std::runtime_error on unrecognised names, unsupported shapes or precisions.
+PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* params, int n);
+
+}  // namespace spi

@@ -3,11 +3,22 @@
 #include <cstddef>
 #include <cstring>
 
-#include "spi_kernels.hpp"
+#include "gemm_desc.hpp"
 
 namespace spi {
 
 inline int round_up_to(int v, int m) { return (v + m - 1) / m * m; }
+
+// Element kp of a hi + lo packed row (GemmDesc::krep = 2): every 128-k packed block is
+// [64 hi | 64 lo] of 64 logical k -- fp16(w), then w - fp16(w), which the pack rounds to fp16.
+// at(k) supplies logical element k < K.
+template <typename F>
+inline float hilo_element(int kp, int K, F at) {
+  const int k = (kp >> 7) * 64 + (kp & 63);
+  if (k >= K) return 0.f;
+  const float v = at(k);
+  return (kp & 64) ? v - static_cast<float>(static_cast<_Float16>(v)) : v;
+}
 
 inline size_t packed_bytes(Prec prec, int Npad, int Kpad) {
   return (size_t)Npad * Kpad * (prec == Prec::F16 ? 2 : 4);
@@ -54,6 +65,22 @@ void pack_matrix_into(char* dst, int N, int K, int Npad, int Kpad, Prec prec, F 
           for (int e = 0; e < 8; ++e) img[((size_t)t * 64 + n) * 64 + sl * 8 + e] = w[(size_t)n * Kpad + t * 64 + c * 8 + e];
         }
   }
+}
+
+// The fused stem's weights (stem.hip): folded [64][3][7][7] fp32 -> [hi | lo][64][24][8] fp16,
+// k = (c, kh) groups of 8 kw values (21 real + 3 zero groups, kw = 7 zero).
+constexpr int kStemPoolMaxOW = 112;  // stem output width bound (images up to 224)
+constexpr size_t stem_pool_bytes() { return (size_t)2 * 64 * 24 * 8 * sizeof(_Float16); }
+inline void stem_pool_pack(const float* w, _Float16* dst) {
+  for (int n = 0; n < 64; ++n)
+    for (int g = 0; g < 24; ++g)
+      for (int kw = 0; kw < 8; ++kw) {
+        const float v = (g < 21 && kw < 7) ? w[((size_t)n * 3 + g / 7) * 49 + (g % 7) * 7 + kw] : 0.f;
+        const _Float16 hi = static_cast<_Float16>(v);
+        const size_t i = ((size_t)n * 24 + g) * 8 + kw;
+        dst[i] = hi;
+        dst[i + (size_t)64 * 24 * 8] = static_cast<_Float16>(v - static_cast<float>(hi));
+      }
 }
 
 }  // namespace spi

@@ -121,10 +121,8 @@ void ingest_nchw(const void* x, void* y, int B, int C, int H, int W, int cpad,
 // (64 output channels, folded BN) + ReLU -> 3x3/s2/p1 max pool -> NHWC [B][PH][PW][64]:
 // fp16 (split false) or the split layout (split true, needs lo).  lo: hi + lo
 // weights and image (three fp16 MFMAs per fragment, fp32-grade); else fp16 only.
-// w: stem_pool_bytes() from stem_pool_pack(); pr: 0 auto, 1 / 2 pooled rows per 4-wave workgroup.
-constexpr int kStemPoolMaxOW = 112;  // stem output width bound (images up to 224)
-constexpr size_t stem_pool_bytes() { return (size_t)2 * 64 * 24 * 8 * sizeof(_Float16); }
-void stem_pool_pack(const float* w_folded /* [64][3][7][7] */, _Float16* dst);
+// w: stem_pool_bytes() from stem_pool_pack() (pack.hpp, which also bounds the stem's output width:
+// kStemPoolMaxOW); pr: 0 auto, 1 / 2 pooled rows per 4-wave workgroup.
 // lo: 0 fp16 weights, 1 hi + lo weights on the fp16 image (fp16m), 2 hi + lo weights on the split
 // image (fp16x3; required for the split output).  src / xf: the image's kind (above); an 8-bit image
 // is [B][3][H][W] or [B][H][W][3] bytes at any byte address.

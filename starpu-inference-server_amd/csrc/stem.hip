@@ -37,6 +37,7 @@
 // and are discarded (MFMA rows are independent).  max commutes with the monotone
 // fp16 rounding, so pooling the fp32 values and rounding once is what pooling
 // the rounded stem outputs gives.
+#include "pack.hpp"
 #include "spi_kernels.hpp"
 
 #include <cstdlib>
@@ -440,19 +441,6 @@ void launch_pr(const void* x, const _Float16* w, const float* bias, void* y, int
 }
 
 }  // namespace
-
-void stem_pool_pack(const float* w, _Float16* dst) {
-  // dst: [hi | lo][64][24][8]; w: folded [64][3][7][7] fp32
-  for (int n = 0; n < kCout; ++n)
-    for (int g = 0; g < kGroups; ++g)
-      for (int kw = 0; kw < 8; ++kw) {
-        const float v = (g < 21 && kw < 7) ? w[((size_t)n * 3 + g / 7) * 49 + (g % 7) * 7 + kw] : 0.f;
-        const _Float16 hi = static_cast<_Float16>(v);
-        const size_t i = ((size_t)n * kGroups + g) * 8 + kw;
-        dst[i] = hi;
-        dst[i + (size_t)kCout * kGroups * 8] = static_cast<_Float16>(v - static_cast<float>(hi));
-      }
-}
 
 void stem_pool(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int lo, bool split,
                int pr, hipStream_t s, int src, const InputXf& xf) {
