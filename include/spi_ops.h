@@ -149,6 +149,59 @@ int spi_op_layernorm_planes(int32_t precision, const void* xh, size_t plane, int
 int spi_op_vit_assemble_planes(const float* patches, const float* cls, const float* pos, void* xh, size_t plane,
                                float* stats, int32_t B, int32_t P, int32_t D, void* stream);
 
+/* ---- Fused QKV projection + attention (qkv_attn.hip) ----
+ * ctx [B S][D] fp16 = attention over q | k | v = A . W^T + bias, D = 64 heads.  A: fp16 [B S][lda];
+ * W_packed: spi_op_pack_weight(fp16, [3 D][D]) (rows q, k, v; row stride the packed Kpad = D); bias fp32
+ * [3 D], required.  in_stats / c1 (both or neither): the LayerNorm fold's consumer -- A holds the rows
+ * before the LayerNorm, in_stats their chunk statistics [B S][D / 64][2], W / bias / c1 come from
+ * spi_op_fold_linear; needs D <= 1024.  mask_bias: fp32 [B S] additive key bias, or null.
+ * 1 <= S <= 256, heads >= 2, lda >= D and a multiple of 8, A and W_packed 16-byte aligned, ctx and
+ * in_stats 8-byte aligned.  Always the fused kernel (SPI_QKV_ATTN is the model's switch); SPI_QKV_HP
+ * applies as in the model. */
+int spi_op_qkv_attention(const void* A, int32_t lda, const void* W_packed, int32_t heads, const float* bias,
+                         const float* in_stats, const float* c1, float eps, const float* mask_bias, void* ctx,
+                         int32_t B, int32_t S, float scale, void* stream);
+
+/* ---- The HBM-bound kernels around the contractions (elementwise.hip) ---- */
+
+/* Image -> NHWC with the channels zero-padded to cpad: y [B][H][W][cpad] (fp16 when out_f16, else fp32).
+ * src_kind, scale_host, shift_host as in spi_op_patchify; x is [B][C][H][W] fp32 (src_kind 0) or 8-bit
+ * pixels with C = 3 at any byte address.  1 <= C <= cpad. */
+int spi_op_ingest(int32_t src_kind, const void* x, int32_t B, int32_t C, int32_t H, int32_t W, int32_t cpad,
+                  const float* scale_host, const float* shift_host, void* y, int32_t out_f16, void* stream);
+
+/* k x k max pool, NHWC: x [B][H][W][C] -> y [B][OH][OW][C], OH = (H + 2 pad - k) / stride + 1 (OW alike),
+ * padding never wins.  precision 0 fp32, 1 fp16, 3 split -> split; 0 <= pad < k; C a multiple of the
+ * 16-byte vector: 4 (fp32), 8 (fp16), 32 (split). */
+int spi_op_maxpool(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                   int32_t stride, int32_t pad, void* y, void* stream);
+
+/* Global average pool x [B][HW][C] -> y [B][C]; precisions and C as spi_op_maxpool.  y is fp32 for
+ * precision 0 and 3 (the split form always writes fp32); for fp16, fp16 or -- with out_f32 -- fp32. */
+int spi_op_avgpool(int32_t precision, const void* x, int32_t B, int32_t HW, int32_t C, void* y, int32_t out_f32,
+                   void* stream);
+
+/* BERT embeddings: row (b, s) = LN(word[clamp(ids[b][s], 0, vocab - 1)] + type0 + pos[s]) gamma + beta ->
+ * yf fp32 [B S][D] (required) and, when yt is not null, yt (fp16 for precision 1, fp32 for 0).  ids int64
+ * [B S]; word [vocab][D], pos [npos][D], type0 / gamma / beta [D] fp32.  mask (int64 [B S]) and mask_bias
+ * (fp32 [B S], written 0 where mask != 0, else the lowest finite fp32) come both or neither.  D <= 1024,
+ * S <= npos. */
+int spi_op_bert_embed(int32_t precision, const int64_t* ids, const float* word, const float* pos,
+                      const float* type0, const float* gamma, const float* beta, float* yf, void* yt, int32_t B,
+                      int32_t S, int32_t D, int32_t vocab, int32_t npos, float eps, const int64_t* mask,
+                      float* mask_bias, void* stream);
+
+/* bias[i] = mask[i] != 0 ? 0 : the lowest finite fp32, i < n. */
+int spi_op_mask_to_bias(const int64_t* mask, float* bias, int32_t n, void* stream);
+
+/* ViT stream assembly, fp32: x [B][P + 1][D], row (b, 0) = cls + pos[0], row (b, 1 + p) = patches[b][p] + pos[1 + p]. */
+int spi_op_vit_assemble(const float* patches, const float* cls, const float* pos, float* x, int32_t B, int32_t P,
+                        int32_t D, void* stream);
+
+/* y[i] = x[i stride_rows] for i < rows: rows of D fp32 -> fp16 when out_f16, else fp32. */
+int spi_op_gather_rows(const float* x, void* y, int32_t rows, int32_t stride_rows, int32_t D, int32_t out_f16,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

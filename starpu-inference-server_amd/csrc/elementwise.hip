@@ -775,6 +775,8 @@ void ingest_nchw(const void* x, void* y, int B, int C, int H, int W, int cpad, b
 
 void maxpool_nhwc(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, int k,
                   int stride, int pad, bool f16, hipStream_t s) {
+  // whole 16-byte channel vectors: the kernels would drop the trailing channels
+  if (C % (f16 ? 8 : 4)) throw std::invalid_argument("maxpool_nhwc: C % 8 == 0 (fp16) / C % 4 == 0 (fp32)");
   const size_t n = (size_t)B * OH * OW * C / (f16 ? 8 : 4);
   if (f16)
     SPI_LAUNCH((maxpool_kernel<_Float16>), dim3(grid_for(n)), dim3(256), 0, s,
@@ -786,16 +788,19 @@ void maxpool_nhwc(const void* x, void* y, int B, int H, int W, int C, int OH, in
 
 void maxpool_nhwc_split(const void* x, void* y, int B, int H, int W, int C, int OH, int OW, int k, int stride,
                         int pad, hipStream_t s) {
+  if (C % 32) throw std::invalid_argument("maxpool_nhwc_split: C % 32 == 0");
   const size_t n = (size_t)B * OH * OW * (C / 8);
   SPI_LAUNCH(maxpool_split_kernel, dim3(grid_for(n)), dim3(256), 0, s, (const _Float16*)x, (_Float16*)y, B,
                      H, W, C, OH, OW, k, stride, pad);
 }
 
 void avgpool_nhwc_split(const void* x, float* y, int B, int HW, int C, hipStream_t s) {
+  if (C % 32) throw std::invalid_argument("avgpool_nhwc_split: C % 32 == 0");
   SPI_LAUNCH(avgpool_split_kernel, dim3(B), dim3(256), 0, s, (const _Float16*)x, y, HW, C);
 }
 
 void avgpool_nhwc(const void* x, void* y, int B, int HW, int C, bool f16, hipStream_t s, bool out_f32) {
+  if (C % (f16 ? 8 : 4)) throw std::invalid_argument("avgpool_nhwc: C % 8 == 0 (fp16) / C % 4 == 0 (fp32)");
   if (f16 && out_f32)
     SPI_LAUNCH((avgpool_kernel<_Float16, float>), dim3(B), dim3(256), 0, s, (const _Float16*)x,
                        (float*)y, B, HW, C);
@@ -839,6 +844,9 @@ void layernorm(const float* x, int ldx, const float* g, const float* b, float* y
 void bert_embed(const int64_t* ids, const float* word, const float* pos, const float* type0,
                 const float* g, const float* b, float* yf, void* yt, int B, int S, int D,
                 int vocab, float eps, bool f16, hipStream_t s, const int64_t* mask, float* mask_bias) {
+  // both kernels store every row through yf (the vector one unconditionally, the scalar one through
+  // yf + row D, which is non-null past row 0)
+  if (!yf) throw std::invalid_argument("bert_embed: the fp32 output yf is required");
   const dim3 grid((B * S + 3) / 4);
   const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   if ((D == 768 || D == 1024) && al16(word) && al16(pos) && al16(type0) && al16(g) && al16(b) && al16(yf) &&

@@ -382,4 +382,120 @@ int spi_op_vit_assemble_planes(const float* patches, const float* cls, const flo
   });
 }
 
+int spi_op_qkv_attention(const void* A, int32_t lda, const void* W, int32_t heads, const float* bias,
+                         const float* in_stats, const float* c1, float eps, const float* mask_bias, void* ctx,
+                         int32_t B, int32_t S, float scale, void* stream) {
+  if (!A || !W || !bias || !ctx || B <= 0 || heads <= 0 || heads > (1 << 20))
+    return fail("invalid qkv_attention arguments");
+  if ((in_stats == nullptr) != (c1 == nullptr)) return fail("qkv_attention: in_stats and c1 come both or neither");
+  const int D = heads * 64;  // the packed Kpad too: D is a multiple of 64
+  if (lda < D || !spi::qkv_attention_eligible(S, heads, 64, D, D, 1, lda, D))
+    return fail("qkv_attention: 1 <= S <= 256, heads >= 2, lda >= D and a multiple of 8");
+  if (in_stats && D > 1024) return fail("qkv_attention: the fold holds at most 16 statistics chunks (D <= 1024)");
+  if ((reinterpret_cast<uintptr_t>(ctx) & 7) || (reinterpret_cast<uintptr_t>(in_stats) & 7))
+    return fail("qkv_attention: 8-byte aligned ctx and in_stats");
+  return guarded([&] {
+    spi::qkv_attention(A, lda, W, D, bias, in_stats, c1, D / 64, eps, mask_bias, ctx, B, S, heads, scale,
+                       static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_ingest(int32_t src_kind, const void* x, int32_t B, int32_t Cc, int32_t H, int32_t W, int32_t cpad,
+                  const float* scale, const float* shift, void* y, int32_t out_f16, void* stream) {
+  spi::InputXf xf;
+  if (src_kind < 0 || src_kind > 2 || !x || !y || B <= 0 || Cc <= 0 || H <= 0 || W <= 0 || Cc > cpad ||
+      (src_kind != 0 && Cc != 3) || !input_xf(scale, shift, &xf))
+    return fail("invalid ingest arguments");
+  return guarded([&] {
+    spi::ingest_nchw(x, y, B, Cc, H, W, cpad, out_f16 != 0, static_cast<hipStream_t>(stream), src_kind, xf);
+    return check_launch();
+  });
+}
+
+namespace {
+
+// 16-byte channel vectors of the pooling kernels: 4 fp32, 8 fp16, a 32-channel block of the split layout
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int pool_vec(int32_t precision) { return precision == 0 ? 4 : precision == 1 ? 8 : precision == kSplitPrecision ? 32 : 0; }
+
+}  // namespace
+
+int spi_op_maxpool(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t Cc, int32_t k,
+                   int32_t stride, int32_t pad, void* y, void* stream) {
+  const int vec = pool_vec(precision);
+  if (!vec || !x || !y || B <= 0 || H <= 0 || W <= 0 || Cc <= 0 || k <= 0 || stride <= 0 || pad < 0 || pad >= k)
+    return fail("invalid maxpool arguments");
+  if (Cc % vec) return fail("maxpool: C must be a multiple of 4 (fp32), 8 (fp16) or 32 (split)");
+  if (!aligned16(x) || !aligned16(y)) return fail("maxpool: 16-byte aligned x and y");
+  if (H + 2 * pad < k || W + 2 * pad < k) return fail("empty maxpool output");
+  const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
+  return guarded([&] {
+    if (precision == kSplitPrecision)
+      spi::maxpool_nhwc_split(x, y, B, H, W, Cc, OH, OW, k, stride, pad, static_cast<hipStream_t>(stream));
+    else
+      spi::maxpool_nhwc(x, y, B, H, W, Cc, OH, OW, k, stride, pad, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_avgpool(int32_t precision, const void* x, int32_t B, int32_t HW, int32_t Cc, void* y, int32_t out_f32,
+                   void* stream) {
+  const int vec = pool_vec(precision);
+  if (!vec || !x || !y || B <= 0 || HW <= 0 || Cc <= 0) return fail("invalid avgpool arguments");
+  if (Cc % vec) return fail("avgpool: C must be a multiple of 4 (fp32), 8 (fp16) or 32 (split)");
+  if (!aligned16(x) || !aligned16(y)) return fail("avgpool: 16-byte aligned x and y");
+  return guarded([&] {
+    if (precision == kSplitPrecision)
+      spi::avgpool_nhwc_split(x, static_cast<float*>(y), B, HW, Cc, static_cast<hipStream_t>(stream));
+    else
+      spi::avgpool_nhwc(x, y, B, HW, Cc, precision == 1, static_cast<hipStream_t>(stream),
+                        precision == 1 && out_f32 != 0);
+    return check_launch();
+  });
+}
+
+int spi_op_bert_embed(int32_t precision, const int64_t* ids, const float* word, const float* pos, const float* type0,
+                      const float* g, const float* b, float* yf, void* yt, int32_t B, int32_t S, int32_t D,
+                      int32_t vocab, int32_t npos, float eps, const int64_t* mask, float* mask_bias, void* stream) {
+  if ((precision != 0 && precision != 1) || !ids || !word || !pos || !type0 || !g || !b || B <= 0 || S <= 0 ||
+      D <= 0 || vocab <= 0 || npos <= 0)
+    return fail("invalid bert_embed arguments");
+  if (!yf) return fail("bert_embed: the fp32 output yf is required");
+  if (D > 1024) return fail("bert_embed: D <= 1024");
+  if (S > npos) return fail("bert_embed: S exceeds the position table");
+  if ((mask == nullptr) != (mask_bias == nullptr)) return fail("bert_embed: mask and mask_bias come both or neither");
+  return guarded([&] {
+    spi::bert_embed(ids, word, pos, type0, g, b, yf, yt, B, S, D, vocab, eps, precision == 1,
+                    static_cast<hipStream_t>(stream), mask, mask_bias);
+    return check_launch();
+  });
+}
+
+int spi_op_mask_to_bias(const int64_t* mask, float* bias, int32_t n, void* stream) {
+  if (!mask || !bias || n <= 0) return fail("invalid mask_to_bias arguments");
+  return guarded([&] {
+    spi::mask_to_bias(mask, bias, n, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_vit_assemble(const float* patches, const float* cls, const float* pos, float* x, int32_t B, int32_t P,
+                        int32_t D, void* stream) {
+  if (!patches || !cls || !pos || !x || B <= 0 || P <= 0 || D <= 0) return fail("invalid vit_assemble arguments");
+  return guarded([&] {
+    spi::vit_assemble(patches, cls, pos, x, B, P, D, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_gather_rows(const float* x, void* y, int32_t rows, int32_t stride_rows, int32_t D, int32_t out_f16,
+                       void* stream) {
+  if (!x || !y || rows <= 0 || stride_rows <= 0 || D <= 0) return fail("invalid gather_rows arguments");
+  return guarded([&] {
+    spi::gather_rows(x, y, rows, stride_rows, D, out_f16 != 0, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
 }  // extern "C"

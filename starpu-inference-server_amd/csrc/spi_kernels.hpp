@@ -128,7 +128,8 @@ void ingest_nchw(const void* x, void* y, int B, int C, int H, int W, int cpad,
 // is [B][3][H][W] or [B][H][W][3] bytes at any byte address.
 void stem_pool(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int lo,
                bool split, int pr, hipStream_t s, int src = kSrcF32Nchw, const InputXf& xf = InputXf{});
-// 3x3/s2/p1 max pool on NHWC.
+// 3x3/s2/p1 max pool on NHWC.  The pools work on whole 16-byte channel vectors: C % 8 == 0 (fp16),
+// C % 4 == 0 (fp32), else they throw.
 void maxpool_nhwc(const void* x, void* y, int B, int H, int W, int C, int OH,
                   int OW, int k, int stride, int pad, bool f16, hipStream_t s);
 // Global average pool NHWC [B,HW,C] -> [B,C] (compute type).
@@ -145,7 +146,8 @@ void layernorm(const float* x, int ldx, const float* g, const float* b,
                float* yf, void* yt, int ldy, int rows, int D, float eps, bool f16,
                hipStream_t s);
 // BERT embeddings: LN(word[ids] + pos[s] + type[0]) -> fp32 + compute type; with a mask, each
-// token's additive attention bias too (mask_to_bias's, one launch fewer per forward).
+// token's additive attention bias too (mask_to_bias's, one launch fewer per forward).  yf is
+// required (throws on null); yt may be null.
 void bert_embed(const int64_t* ids, const float* word, const float* pos,
                 const float* type0, const float* g, const float* b, float* yf,
                 void* yt, int B, int S, int D, int vocab, float eps, bool f16,

@@ -295,3 +295,71 @@ def vit_assemble_planes(patches, cls, pos, xh, plane, stats, B, P, D, stream=Non
     _check(lib.spi_op_vit_assemble_planes(_ptr(patches), _ptr(cls), _ptr(pos), _ptr(xh), plane, _ptr(stats), B, P, D,
                                           C.c_void_p(s)))
     return xh
+
+
+# ---- fused QKV projection + attention, and the HBM-bound kernels (spi_ops.h) ----
+# All on caller-owned buffers, so a test can put guard rows behind every output.
+
+
+def _stream(stream):
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream if stream is None else stream)
+
+
+def qkv_attention(A, W_packed, heads, bias, ctx, B, S, lda=None, in_stats=None, c1=None, eps=1e-5, mask_bias=None,
+                  scale=0.125, stream=None):
+    """Fused QKV GEMM + attention: A fp16 [B S][lda] (default lda: A's row stride), W_packed from
+    pack_weight("fp16", [3 D][D]), bias fp32 [3 D]; with in_stats / c1 the LayerNorm fold's consumer.
+    Writes ctx fp16 [B S][64 heads]."""
+    _check(lib.spi_op_qkv_attention(_ptr(A), A.stride(0) if lda is None else lda, _ptr(W_packed), heads, _ptr(bias),
+                                    _ptr(in_stats), _ptr(c1), eps, _ptr(mask_bias), _ptr(ctx), B, S, scale,
+                                    _stream(stream)))
+    return ctx
+
+
+def ingest(src_kind, x, B, Cc, H, W_, cpad, out, scale=None, shift=None, stream=None):
+    """Image ("fp32" [B][C][H][W], "u8_nchw", "u8_nhwc") -> out NHWC [B][H][W][cpad], fp16 or fp32 by out.dtype."""
+    _check(lib.spi_op_ingest(SRC_KIND[src_kind], _ptr(x), B, Cc, H, W_, cpad, N.float3(scale), N.float3(shift),
+                             _ptr(out), int(out.dtype == torch.float16), _stream(stream)))
+    return out
+
+
+def pool_out(H, W_, k, stride, pad):
+    return (H + 2 * pad - k) // stride + 1, (W_ + 2 * pad - k) // stride + 1
+
+
+def maxpool(prec, x, B, H, W_, Cc, k, stride, pad, out, stream=None):
+    """NHWC max pool; prec "fp32", "fp16" or "fp16x3s" (split in, split out)."""
+    _check(lib.spi_op_maxpool(PREC[prec], _ptr(x), B, H, W_, Cc, k, stride, pad, _ptr(out), _stream(stream)))
+    return out
+
+
+def avgpool(prec, x, B, HW, Cc, out, stream=None):
+    """Global average pool [B][HW][C] -> out [B][C]; fp16 input writes fp32 when out is a float32 tensor."""
+    _check(lib.spi_op_avgpool(PREC[prec], _ptr(x), B, HW, Cc, _ptr(out),
+                              int(prec == "fp16" and out.dtype == torch.float32), _stream(stream)))
+    return out
+
+
+def bert_embed(prec, ids, word, pos, type0, gamma, beta, yf, yt, B, S, D, eps, mask=None, mask_bias=None,
+               vocab=None, npos=None, stream=None):
+    _check(lib.spi_op_bert_embed(PREC[prec], _ptr(ids), _ptr(word), _ptr(pos), _ptr(type0), _ptr(gamma), _ptr(beta),
+                                 _ptr(yf), _ptr(yt), B, S, D, word.shape[0] if vocab is None else vocab,
+                                 pos.shape[0] if npos is None else npos, eps, _ptr(mask), _ptr(mask_bias),
+                                 _stream(stream)))
+    return yf, yt
+
+
+def mask_to_bias(mask, bias, n, stream=None):
+    _check(lib.spi_op_mask_to_bias(_ptr(mask), _ptr(bias), n, _stream(stream)))
+    return bias
+
+
+def vit_assemble(patches, cls, pos, x, B, P, D, stream=None):
+    _check(lib.spi_op_vit_assemble(_ptr(patches), _ptr(cls), _ptr(pos), _ptr(x), B, P, D, _stream(stream)))
+    return x
+
+
+def gather_rows(x, out, rows, stride_rows, D, stream=None):
+    _check(lib.spi_op_gather_rows(_ptr(x), _ptr(out), rows, stride_rows, D, int(out.dtype == torch.float16),
+                                  _stream(stream)))
+    return out

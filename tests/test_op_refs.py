@@ -1,0 +1,170 @@
+"""The references of tests/op_refs.py against the torch ops they restate, without a GPU -- what makes
+the bars of test_qkv_attention_ops_gpu.py and test_elementwise_ops_gpu.py trustworthy -- and the
+emulation of qkv_attn.hip's arithmetic from which the fused kernel's GPU bar is taken."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import op_refs as R
+
+# The emulated kernel arithmetic (fp32 accumulation, fp16 q / k / v, fp16 P, fp16 output) against the
+# float64 reference, normalised max error over every parity case.  Measured on such an emulation: 2.5e-4
+# to 5.2e-4 over all the cases; the bar leaves that 15 % headroom.  The GPU bar is 3x its worst case.
+EMU_TOL = 6e-4
+# float64 against float64: summation order only
+TOL64 = 1e-12
+
+
+@pytest.fixture(scope="module")
+def ops(spi):
+    return importlib.import_module("starpu-inference-server_amd.ops")
+
+
+# ---- fused QKV + attention ----------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("B,S,heads,masked", [(2, 17, 3, True), (1, 129, 2, False), (2, 64, 2, True)])
+def test_qkv_ref_equals_sdpa_float64(ops, B, S, heads, masked):
+    c = R.qkv_case(ops, B, S, heads, False, masked)
+    got = R.qkv_attention_ref(c["A16"], c["W16"], c["bias"], c["mask"], B, S, heads, 0.125, round16=False)
+    qkv = torch.from_numpy(c["A16"].astype(np.float64) @ c["W16"].astype(np.float64).T + c["bias"])
+    q, k, v = qkv.view(B, S, 3, heads, 64).permute(2, 0, 3, 1, 4)
+    m = None if c["mask"] is None else torch.from_numpy(c["mask"]).double()[:, None, None, :]
+    ref = F.scaled_dot_product_attention(q, k, v, attn_mask=m, scale=0.125)
+    ref = ref.permute(0, 2, 1, 3).reshape(B * S, heads * 64).numpy()
+    assert R.nerr(got, ref) < TOL64
+
+
+def test_qkv_ref_folded_equals_layernorm_linear_attention(ops):
+    """The folded form on fold_linear's outputs (fp32 rows as A, so nothing but the weights is rounded):
+    exactly LN(x) -> the fp16 folded weights, and LN -> linear -> attention to fp16-weight rounding."""
+    B, S, heads = 2, 40, 3
+    D = heads * 64
+    c = R.qkv_case(ops, B, S, heads, True, True)
+    x64 = c["x"].astype(np.float64)
+    got = R.qkv_attention_ref(c["x"], c["W16"], c["bias"], c["mask"], B, S, heads, 0.125, stats=c["stats"], c1=c["c1"],
+                              eps=R.EPS, round16=False)
+    xhat = (x64 - x64.mean(1, keepdims=True)) / np.sqrt(x64.var(1, keepdims=True) + R.EPS)
+    # rstd (x W'^T - mean c1) + b' = xhat W'^T + b' with W' the weights as packed.  What differs: the
+    # statistics travel as fp32 (2^-24 relative on a mean of up to 6 sigma times c1) and c1 is an fp32 sum
+    # of D fp16 weights: 1e-5 of max|ref| covers both with an order of magnitude to spare.
+    same = R.qkv_attention_ref(xhat, c["W16"], c["bias"], c["mask"], B, S, heads, 0.125, round16=False)
+    assert R.nerr(got, same) < 1e-5
+    # against the unfolded layer in float64: LayerNorm -> linear (W, b before the fold) -> attention.
+    # Each folded weight is rounded to fp16, 2^-11 relative; a 2^-11 relative error of q and k moves a
+    # score by about 2^-11 sqrt(64) sigma^2 / 8 = 1e-3 and the output by that fraction of max|v|: 5e-3.
+    rng = np.random.default_rng(B * S + heads)  # qkv_case's draw of W and b
+    W = (rng.standard_normal((3 * D, D)) * 1.5 / np.sqrt(D)).astype(np.float32)
+    b = (rng.standard_normal(3 * D) * 0.5).astype(np.float32)
+    ln = F.layer_norm(torch.from_numpy(x64), (D,), torch.from_numpy(c["gamma"]).double(),
+                      torch.from_numpy(c["beta"]).double(), R.EPS).numpy()
+    ref = R.qkv_attention_ref(ln, W, b, c["mask"], B, S, heads, 0.125, round16=False)
+    assert R.nerr(got, ref) < 5e-3
+
+
+def test_qkv_ref_fully_masked_sequence_is_the_mean_of_v(ops):
+    B, S, heads = 2, 19, 2
+    c = R.qkv_case(ops, B, S, heads, False, False)
+    mask = np.zeros((B, S), np.float32)
+    mask[1, :] = R.FMIN
+    got = R.qkv_attention_ref(c["A16"], c["W16"], c["bias"], mask, B, S, heads, 0.125)
+    qkv = (c["A16"].astype(np.float64) @ c["W16"].astype(np.float64).T + c["bias"]).astype(np.float16)
+    v = qkv.astype(np.float64)[S:, 2 * heads * 64:]
+    assert np.abs(got[S:] - v.mean(0, keepdims=True)).max() < TOL64
+
+
+@pytest.mark.parametrize("B,S,heads,fold,masked", R.QKV_CASES)
+def test_qkv_emulation_within_bar(ops, B, S, heads, fold, masked):
+    c = R.qkv_case(ops, B, S, heads, fold, masked)
+    args = (c["A16"], c["W16"], c["bias"], c["mask"], B, S, heads, 0.125)
+    kw = dict(stats=c["stats"], c1=c["c1"], eps=R.EPS)
+    ref = R.qkv_attention_ref(*args, **kw)
+    e = R.nerr(R.emulate_qkv_attention(*args, **kw), ref)
+    print(f"emulation B{B} S{S} H{heads} fold{int(fold)} mask{int(masked)}: {e:.3e}")
+    assert np.isfinite(ref).all() and e < EMU_TOL
+
+
+def test_combine_stats_restated(ops):
+    x = R.make_rows(np.random.default_rng(3), 9, 192).astype(np.float64)
+    st = ops.chunk_stats(x)
+    for a, b in zip(R.combine_stats64(st, R.EPS), ops.combine_stats(st, R.EPS)):
+        np.testing.assert_array_equal(a, b)
+    np.testing.assert_allclose(R.combine_stats64(st, R.EPS)[1], 1 / np.sqrt(x.var(1) + R.EPS), rtol=1e-12)
+
+
+# ---- the HBM-bound kernels ----------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("k,stride,pad", [(3, 2, 1), (2, 2, 0)])
+@pytest.mark.parametrize("B,H,W,C", [(1, 5, 5, 8), (2, 9, 7, 64), (1, 113, 57, 32)])
+def test_maxpool_ref_equals_torch(B, H, W, C, k, stride, pad):
+    x = np.random.default_rng(H * W + C).standard_normal((B, H, W, C)).astype(np.float32)
+    ref = F.max_pool2d(torch.from_numpy(x).permute(0, 3, 1, 2), k, stride, pad).permute(0, 2, 3, 1).numpy()
+    got = R.maxpool_ref(x, k, stride, pad)
+    assert got.dtype == np.float32 and got.shape == ref.shape
+    np.testing.assert_array_equal(got, ref)
+
+
+def test_avgpool_ref_equals_torch():
+    x = np.random.default_rng(1).standard_normal((3, 49, 96)).astype(np.float32)
+    ref = F.adaptive_avg_pool1d(torch.from_numpy(x).double().permute(0, 2, 1), 1)[..., 0].numpy()
+    assert R.nerr(R.avgpool_ref(x), ref) < TOL64
+
+
+def test_bert_embed_ref_equals_torch():
+    rng = np.random.default_rng(2)
+    vocab, npos, D, B, S = 50, 128, 200, 3, 7
+    word, pos = (rng.standard_normal((n, D)).astype(np.float32) for n in (vocab, npos))
+    type0, gamma, beta = (rng.standard_normal(D).astype(np.float32) for _ in range(3))
+    ids = rng.integers(0, vocab, B * S)
+    ids[:5] = [0, vocab - 1, -1, vocab, 2 ** 40]
+    got = R.bert_embed_ref(ids, word, pos, type0, gamma, beta, S, 1e-12)
+    t = lambda a: torch.from_numpy(a).double()  # noqa: E731
+    emb = F.embedding(torch.from_numpy(np.clip(ids, 0, vocab - 1)), t(word)) + t(type0) + t(pos)[:S].repeat(B, 1)
+    ref = F.layer_norm(emb, (D,), t(gamma), t(beta), 1e-12).numpy()
+    # the reference adds in fp32 as the kernels do, torch here in float64: two fp32 roundings, 2^-23
+    assert R.nerr(got, ref) < 1e-6
+    # row 2 holds id -1: word row 0 at position 2
+    np.testing.assert_array_equal(got[2], R.bert_embed_ref(np.int64([0]), word, pos[2:], type0, gamma, beta, 1, 1e-12)[0])
+
+
+def test_ingest_ref_equals_permute_pad():
+    rng = np.random.default_rng(4)
+    x = rng.standard_normal((2, 3, 5, 7)).astype(np.float32)
+    ref = F.pad(torch.from_numpy(x).permute(0, 2, 3, 1), (0, 5))
+    np.testing.assert_array_equal(R.ingest_ref(x, 8, False), ref.numpy())
+    np.testing.assert_array_equal(R.ingest_ref(x, 8, True), ref.half().numpy())
+    u8 = rng.integers(0, 256, (2, 5, 7, 3), dtype=np.uint8)
+    scale, shift = np.float32([0.017, 0.0175, 0.0174]), np.float32([-2.1, -2.0, -1.8])
+    img = R.xf_image(u8, True, scale, shift)
+    want = torch.from_numpy(u8).permute(0, 3, 1, 2).float() * torch.from_numpy(scale).view(1, 3, 1, 1)
+    want = want + torch.from_numpy(shift).view(1, 3, 1, 1)  # two torch ops: two fp32 roundings
+    np.testing.assert_array_equal(img, want.numpy())
+    np.testing.assert_array_equal(R.xf_image(np.ascontiguousarray(u8.transpose(0, 3, 1, 2)), False, scale, shift), img)
+
+
+def test_split_round_trips(ops):
+    x = torch.from_numpy(np.random.default_rng(5).standard_normal((3, 4, 64)).astype(np.float32)) * 7
+    s = ops.to_split(x)
+    back = ops.from_split(s)
+    # hi + lo keeps 22 significant bits, |x - (hi + lo)| <= 2^-22 |x|, until lo is an fp16 subnormal
+    # (spacing 2^-24: half of it)
+    assert bool(((back - x).abs() <= torch.clamp(x.abs() * 2.0 ** -22, min=2.0 ** -25)).all())
+    # a value the layout holds is a fixed point: split -> values -> split gives the same bits
+    assert torch.equal(ops.to_split(back).view(torch.int16), s.view(torch.int16))
+
+
+def test_small_refs_equal_torch():
+    rng = np.random.default_rng(6)
+    mask = rng.integers(0, 2, 37)
+    ref = (1.0 - torch.from_numpy(mask).float()) * torch.finfo(torch.float32).min
+    np.testing.assert_array_equal(R.mask_to_bias_ref(mask), ref.numpy())
+    patches, cls, pos = (rng.standard_normal(s).astype(np.float32) for s in ((2, 9, 40), (40,), (10, 40)))
+    t = torch.cat([torch.from_numpy(cls).expand(2, 1, 40), torch.from_numpy(patches)], 1) + torch.from_numpy(pos)
+    np.testing.assert_array_equal(R.vit_assemble_ref(patches, cls, pos), t.numpy())
+    x = rng.standard_normal((21, 12)).astype(np.float32)
+    np.testing.assert_array_equal(R.gather_rows_ref(x, 4, 5, False), x[[0, 5, 10, 15]])
+    np.testing.assert_array_equal(R.gather_rows_ref(x, 4, 5, True), torch.from_numpy(x[[0, 5, 10, 15]]).half().numpy())
