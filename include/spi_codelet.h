@@ -266,8 +266,33 @@ typedef struct spi_model_config {
   float eps;          /* norm epsilon (0 = family default) */
   float affine_scale; /* AFFINE only */
   float affine_shift; /* AFFINE only */
-  int32_t _pad;
+  int32_t bert_io;    /* BERT only: SPI_BERT_* bits; 0 = [ids, mask] -> last_hidden_state */
 } spi_model_config;
+
+/* spi_model_config.bert_io: which outputs a BERT replica writes and whether it takes segment ids.
+ * The field replaces a padding word, so a zeroed config keeps the one-output contract.
+ *
+ * Outputs, always in this order and all fp32: last_hidden_state [B,S,D] (unless
+ * SPI_BERT_NO_HIDDEN), then pooler_output [B,D], then the masked mean [B,D].  With
+ * SPI_BERT_OUT_POOLER alone that is HF's BertModel(..., return_dict=False) tuple.
+ *   pooler_output = tanh(W_p . last_hidden_state[:, 0] + b_p)   (pooler.dense.weight / .bias)
+ *   masked mean   = sum_s m[b,s] h[b,s,:] / max(sum_s m[b,s], 1e-9), m = (attention_mask != 0),
+ *                   the rule the attention bias uses; without a mask input every token counts.
+ * Inputs: input_ids, then attention_mask, then -- with SPI_BERT_TOKEN_TYPES only --
+ * token_type_ids, each [B,S] int64 and each optional from the end.  Type ids are clamped to
+ * [0, type_vocab - 1] like word ids; all-zero ids, or a two-input task, give the bits of a
+ * replica without the flag.
+ * spi_model_create refuses, with a message: unknown bits; any bit on another family;
+ * SPI_BERT_NO_HIDDEN with neither pooled output; SPI_BERT_OUT_POOLER on a model without
+ * pooler.dense.weight / .bias (add_pooling_layer=False).
+ * The measurement hooks (spi_model_profile, _profile_op, _launch_table) read `inputs` up to
+ * the replica's input count (absent inputs null) and `outputs` in the order above. */
+enum spi_bert_io {
+  SPI_BERT_OUT_POOLER = 1,
+  SPI_BERT_OUT_MEAN = 2,
+  SPI_BERT_NO_HIDDEN = 4,
+  SPI_BERT_TOKEN_TYPES = 8
+};
 
 spi_model* spi_model_create(int32_t device_id, const spi_model_config* config,
                             const spi_named_tensor* params, int32_t num_params,

@@ -191,6 +191,30 @@ int spi_op_bert_embed(int32_t precision, const int64_t* ids, const float* word, 
                       int32_t S, int32_t D, int32_t vocab, int32_t npos, float eps, const int64_t* mask,
                       float* mask_bias, void* stream);
 
+/* spi_op_bert_embed with segment ids: `type0` becomes type_table [type_vocab][D] and row (b, s) adds
+ * type_table[clamp(type_ids[b][s], 0, type_vocab - 1)].  type_ids int64 [B S], or null for row 0 --
+ * then, and with all-zero ids, the output has the bits of spi_op_bert_embed on type_table's first row. */
+int spi_op_bert_embed_types(int32_t precision, const int64_t* ids, const float* word, const float* pos,
+                            const float* type_table, int32_t type_vocab, const int64_t* type_ids,
+                            const float* gamma, const float* beta, float* yf, void* yt, int32_t B, int32_t S,
+                            int32_t D, int32_t vocab, int32_t npos, float eps, const int64_t* mask,
+                            float* mask_bias, void* stream);
+
+/* ---- BERT sentence outputs (bert_pool.hip); fp32 throughout, deterministic (no atomics) ---- */
+
+/* BERT pooler: y[b][n] = tanh(bias[n] + sum_k h[b ld + k] W[n][k]), b < B, n < D.  h: fp32 rows of D, ld
+ * floats between consecutive b (ld >= D: D for packed rows, S D for the class-token rows of a [B][S][D]
+ * hidden state); W fp32 [D][D] row-major (pooler.dense.weight), bias fp32 [D]; y fp32 [B][D].
+ * B >= 1, D a multiple of 64 and <= 1024. */
+int spi_op_bert_pooler(const float* h, int64_t ld, const float* W, const float* bias, float* y, int32_t B,
+                       int32_t D, void* stream);
+
+/* Masked mean over the sequence: y[b][:] = sum_s m[b][s] h[b][s][:] / max(sum_s m[b][s], 1e-9),
+ * m = (mask[b][s] != 0); mask int64 [B][S], or null = every token counts.  h fp32 [B][S][D], y fp32 [B][D].
+ * B >= 1, S >= 1, D a multiple of 64 and <= 1024. */
+int spi_op_masked_mean(const float* h, const int64_t* mask, float* y, int32_t B, int32_t S, int32_t D,
+                       void* stream);
+
 /* bias[i] = mask[i] != 0 ? 0 : the lowest finite fp32, i < n. */
 int spi_op_mask_to_bias(const int64_t* mask, float* bias, int32_t n, void* stream);
 

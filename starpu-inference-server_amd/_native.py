@@ -154,8 +154,12 @@ class ModelConfig(C.Structure):
         ("eps", C.c_float),
         ("affine_scale", C.c_float),
         ("affine_shift", C.c_float),
-        ("_pad", C.c_int32),
+        ("bert_io", C.c_int32),
     ]
+
+
+# enum spi_bert_io (spi_model_config.bert_io)
+BERT_OUT_POOLER, BERT_OUT_MEAN, BERT_NO_HIDDEN, BERT_TOKEN_TYPES = 1, 2, 4, 8
 
 
 # name -> (restype, argtypes): every function declared in include/spi_codelet.h
@@ -249,6 +253,14 @@ _PROTOS = {
     "spi_op_bert_embed": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spi_op_bert_embed_types": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "spi_op_bert_pooler": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_void_p]),
+    "spi_op_masked_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_void_p]),
     "spi_op_mask_to_bias": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "spi_op_vit_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_void_p]),

@@ -128,6 +128,33 @@ PRECISIONS = {"fp16": N.PREC_F16, "f16": N.PREC_F16, "fp32": N.PREC_F32, "f32": 
               "fp16x3": N.PREC_F16X3, "f16x3": N.PREC_F16X3, "fp16m": N.PREC_F16M, "f16m": N.PREC_F16M}
 _FAMILIES = {None: N.FAMILY_AUTO, "auto": N.FAMILY_AUTO, "resnet": N.FAMILY_RESNET, "bert": N.FAMILY_BERT,
              "vit": N.FAMILY_VIT, "affine": N.FAMILY_AFFINE}
+BERT_IO = {"pooler": N.BERT_OUT_POOLER, "mean": N.BERT_OUT_MEAN, "no_hidden": N.BERT_NO_HIDDEN,
+           "token_types": N.BERT_TOKEN_TYPES}
+
+
+def bert_io_bits(bert_io) -> int:
+    """spi_model_config.bert_io from an int, one name or several: ("pooler", "mean", "no_hidden", "token_types")."""
+    if bert_io is None:
+        return 0
+    if isinstance(bert_io, int):
+        return bert_io
+    names = [bert_io] if isinstance(bert_io, str) else list(bert_io)
+    bits = 0
+    for name in names:
+        if name not in BERT_IO:
+            raise InferenceExecutionException(f"unknown bert_io name {name!r}; known: {sorted(BERT_IO)}")
+        bits |= BERT_IO[name]
+    return bits
+
+
+def _pointer_array(tensors, at_least: int = 1) -> C.Array:
+    """void*[]: device pointers, null-padded to at_least entries (a BERT replica's optional inputs)."""
+    ptrs = [t.data_ptr() for t in tensors]
+    return (C.c_void_p * max(at_least, len(ptrs)))(*ptrs)
+
+
+def _as_list(out) -> list:
+    return [out] if isinstance(out, torch.Tensor) else list(out)
 
 
 class ModelReplica:
@@ -136,14 +163,14 @@ class ModelReplica:
     def __init__(self, module: torch.nn.Module | str | None, device_id: int = 0, precision: str = "fp16",
                  max_batch: int = 8, family: str | None = None, num_heads: int = 0, seq_len: int = 0,
                  image_size: int = 0, eps: float = 0.0, affine: tuple[float, float] = (1.0, 0.0),
-                 graphs: bool = False):
+                 graphs: bool = False, bert_io=0):
         if isinstance(module, str):
             # The reference's on-disk format: torch::jit::load + the C++ weight
             # extractor in libspi_torch.so (inference_runner.cpp:243-275).
             from .libtorch import TorchScriptModule
             ts = TorchScriptModule(module)
             rep = ts.replica(device_id, precision, max_batch, family=family, num_heads=num_heads, seq_len=seq_len,
-                             image_size=image_size, eps=eps, graphs=graphs)
+                             image_size=image_size, eps=eps, graphs=graphs, bert_io=bert_io)
             self.__dict__.update(rep.__dict__)
             rep.handle = None  # ownership moved to self
             return
@@ -169,6 +196,7 @@ class ModelReplica:
         cfg.image_size = image_size
         cfg.eps = eps
         cfg.affine_scale, cfg.affine_shift = affine
+        cfg.bert_io = bert_io_bits(bert_io)
         err = C.create_string_buffer(512)
         h = lib.spi_model_create(device_id, C.byref(cfg), arr, len(tensors), err, len(err))
         if not h:
@@ -177,17 +205,19 @@ class ModelReplica:
         self.device_id = device_id
         self.precision = precision
         self.max_batch = max_batch
+        self.bert_io = cfg.bert_io
         if graphs:
             self.set_graphs(True)
 
     @classmethod
     def from_handle(cls, handle: int, device_id: int, precision: str, max_batch: int,
-                    graphs: bool = False) -> "ModelReplica":
+                    graphs: bool = False, bert_io: int = 0) -> "ModelReplica":
         self = cls.__new__(cls)
         self.handle = C.c_void_p(handle)
         self.device_id = device_id
         self.precision = precision
         self.max_batch = max_batch
+        self.bert_io = bert_io
         if graphs:
             self.set_graphs(True)
         return self
@@ -223,11 +253,12 @@ class ModelReplica:
     def flops(self, batch: int) -> float:
         return lib.spi_model_flops(self.handle, batch)
 
-    def profile(self, inputs: Sequence[torch.Tensor], out: torch.Tensor, stream: int,
-                max_ops: int = 4096) -> list[dict]:
-        """One forward with every launch bracketed by hipEvents on `stream` (measurement only)."""
-        ins = (C.c_void_p * max(1, len(inputs)))(*[x.data_ptr() for x in inputs])
-        outs = (C.c_void_p * 1)(out.data_ptr())
+    def profile(self, inputs: Sequence[torch.Tensor], out, stream: int, max_ops: int = 4096) -> list[dict]:
+        """One forward with every launch bracketed by hipEvents on `stream` (measurement only).
+        `out`, here and in launch_table / profile_op: the output tensor, or the list of them for a
+        BERT replica with bert_io outputs (in the replica's output order)."""
+        ins = _pointer_array(inputs, 3)
+        outs = _pointer_array(_as_list(out))
         ms = (C.c_float * max_ops)()
         fl = (C.c_double * max_ops)()
         by = (C.c_double * max_ops)()
@@ -242,11 +273,11 @@ class ModelReplica:
         return [dict(name=raw[i * name_len:(i + 1) * name_len].split(b"\0")[0].decode(), ms=ms[i], flops=fl[i],
                      bytes=by[i]) for i in range(n)]
 
-    def launch_table(self, inputs: Sequence[torch.Tensor], out: torch.Tensor, stream: int) -> list[dict]:
+    def launch_table(self, inputs: Sequence[torch.Tensor], out, stream: int) -> list[dict]:
         """One eager forward with every kernel launch recorded (measurement only): per launch its
         op (index, name), kernel (template id) and grid in workgroups."""
-        ins = (C.c_void_p * max(1, len(inputs)))(*[x.data_ptr() for x in inputs])
-        outs = (C.c_void_p * 1)(out.data_ptr())
+        ins = _pointer_array(inputs, 3)
+        outs = _pointer_array(_as_list(out))
         seq = int(inputs[0].shape[1]) if inputs[0].dim() >= 2 else 0
         size = 1 << 20
         while True:
@@ -265,12 +296,11 @@ class ModelReplica:
                              block=int(block)))
         return rows
 
-    def profile_op(self, inputs: Sequence[torch.Tensor], out: torch.Tensor, stream: int, name: str,
-                   reps: int = 200) -> dict:
+    def profile_op(self, inputs: Sequence[torch.Tensor], out, stream: int, name: str, reps: int = 200) -> dict:
         """One eager forward with op `name` launched `reps` times back to back between one pair
         of hipEvents on `stream`: its device time per launch (measurement only)."""
-        ins = (C.c_void_p * max(1, len(inputs)))(*[x.data_ptr() for x in inputs])
-        outs = (C.c_void_p * 1)(out.data_ptr())
+        ins = _pointer_array(inputs, 3)
+        outs = _pointer_array(_as_list(out))
         ms, fl, by = C.c_float(), C.c_double(), C.c_double()
         seq = int(inputs[0].shape[1]) if inputs[0].dim() >= 2 else 0
         rc = lib.spi_model_profile_op(self.handle, C.c_void_p(stream), int(inputs[0].shape[0]), seq, ins, outs,
@@ -498,16 +528,17 @@ class InferenceCodelet:
         return cls._run(lib.spi_hip_inference_func, buffers, params)
 
 
-def run_hip(replica: ModelReplica, inputs: Sequence[torch.Tensor], out: torch.Tensor,
-            stream: int | None = None, device_id: int | None = None, worker_id: int = 0,
-            sync: bool = True) -> N.CodeletArgs:
-    """Convenience: one codelet call over device tensors on `stream`."""
+def run_hip(replica: ModelReplica, inputs: Sequence[torch.Tensor], out, stream: int | None = None,
+            device_id: int | None = None, worker_id: int = 0, sync: bool = True) -> N.CodeletArgs:
+    """Convenience: one codelet call over device tensors on `stream`.  `out`: the output tensor, or
+    the list of output tensors of a BERT replica with bert_io outputs (hidden, pooler, mean order)."""
+    outs = _as_list(out)
     dev = replica.device_id if device_id is None else device_id
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
     params = make_params([list(x.shape) for x in inputs], [x.dtype for x in inputs], models_gpu=[replica],
-                         device_ids=[replica.device_id], output_types=[out.dtype])
-    bufs = [tensor_interface(x) for x in inputs] + [tensor_interface(out)]
+                         device_ids=[replica.device_id], output_types=[o.dtype for o in outs], num_outputs=len(outs))
+    bufs = [tensor_interface(x) for x in inputs] + [tensor_interface(o) for o in outs]
     with worker_context(worker_id, dev, stream):
         args = InferenceCodelet.hip_inference_func(bufs, params)
     if sync:

@@ -442,11 +442,18 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restr
   }
 }
 
+// The token-type table row of embedding row `row`: the clamped segment id, or 0 without ids.
+__device__ __forceinline__ size_t type_row(const int64_t* types, int row, int type_vocab) {
+  if (!types) return 0;
+  const int64_t t = types[row];
+  return (size_t)(t < 0 ? 0 : (t >= type_vocab ? type_vocab - 1 : t));
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bert_embed_kernel(
     const int64_t* ids, const float* word, const float* pos, const float* type0,
     const float* g, const float* b, float* yf, T* yt, int B, int S, int D, int vocab,
-    float eps, const int64_t* mask, float* mask_bias) {
+    float eps, const int64_t* mask, float* mask_bias, const int64_t* types, int type_vocab) {
   constexpr int VPL = 16;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -457,11 +464,12 @@ __global__ __launch_bounds__(256) void bert_embed_kernel(
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
   const float* w = word + (size_t)id * D;
   const float* p = pos + (size_t)s * D;
+  const float* t = type0 + type_row(types, row, type_vocab) * D;
   float v[VPL];
 #pragma unroll
   for (int j = 0; j < VPL; ++j) {
     const int c = lane + 64 * j;
-    v[j] = c < D ? (w[c] + type0[c]) + p[c] : 0.f;
+    v[j] = c < D ? (w[c] + t[c]) + p[c] : 0.f;
   }
   ln_row<T, VPL>(v, D, g, b, eps, yf + (size_t)row * D, yt ? yt + (size_t)row * D : nullptr,
                  lane);
@@ -477,7 +485,8 @@ __global__ __launch_bounds__(256) void bert_embed_vec_kernel(const int64_t* ids,
                                                              const float* __restrict__ g,
                                                              const float* __restrict__ b, float* yf, T* yt, int B,
                                                              int S, int vocab, float eps, const int64_t* mask,
-                                                             float* mask_bias) {
+                                                             float* mask_bias, const int64_t* types,
+                                                             int type_vocab) {
   constexpr int D = NV * 256;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -489,7 +498,7 @@ __global__ __launch_bounds__(256) void bert_embed_vec_kernel(const int64_t* ids,
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
   const float4* w4 = reinterpret_cast<const float4*>(word + (size_t)id * D);
   const float4* p4 = reinterpret_cast<const float4*>(pos + (size_t)s * D);
-  const float4* t4 = reinterpret_cast<const float4*>(type0);
+  const float4* t4 = reinterpret_cast<const float4*>(type0 + type_row(types, row, type_vocab) * D);
   const float4* g4 = reinterpret_cast<const float4*>(g);
   const float4* b4 = reinterpret_cast<const float4*>(b);
   float4 v[NV], gg[NV], bb[NV];
@@ -843,7 +852,8 @@ void layernorm(const float* x, int ldx, const float* g, const float* b, float* y
 
 void bert_embed(const int64_t* ids, const float* word, const float* pos, const float* type0,
                 const float* g, const float* b, float* yf, void* yt, int B, int S, int D,
-                int vocab, float eps, bool f16, hipStream_t s, const int64_t* mask, float* mask_bias) {
+                int vocab, float eps, bool f16, hipStream_t s, const int64_t* mask, float* mask_bias,
+                const int64_t* types, int type_vocab) {
   // both kernels store every row through yf (the vector one unconditionally, the scalar one through
   // yf + row D, which is non-null past row 0)
   if (!yf) throw std::invalid_argument("bert_embed: the fp32 output yf is required");
@@ -853,24 +863,24 @@ void bert_embed(const int64_t* ids, const float* word, const float* pos, const f
       (!yt || (reinterpret_cast<uintptr_t>(yt) & (f16 ? 7 : 15)) == 0)) {
     if (D == 768 && f16)
       SPI_LAUNCH((bert_embed_vec_kernel<_Float16, 3>), grid, dim3(256), 0, s, ids, word, pos, type0, g, b, yf,
-                 (_Float16*)yt, B, S, vocab, eps, mask, mask_bias);
+                 (_Float16*)yt, B, S, vocab, eps, mask, mask_bias, types, type_vocab);
     else if (D == 768)
       SPI_LAUNCH((bert_embed_vec_kernel<float, 3>), grid, dim3(256), 0, s, ids, word, pos, type0, g, b, yf,
-                 (float*)yt, B, S, vocab, eps, mask, mask_bias);
+                 (float*)yt, B, S, vocab, eps, mask, mask_bias, types, type_vocab);
     else if (f16)
       SPI_LAUNCH((bert_embed_vec_kernel<_Float16, 4>), grid, dim3(256), 0, s, ids, word, pos, type0, g, b, yf,
-                 (_Float16*)yt, B, S, vocab, eps, mask, mask_bias);
+                 (_Float16*)yt, B, S, vocab, eps, mask, mask_bias, types, type_vocab);
     else
       SPI_LAUNCH((bert_embed_vec_kernel<float, 4>), grid, dim3(256), 0, s, ids, word, pos, type0, g, b, yf,
-                 (float*)yt, B, S, vocab, eps, mask, mask_bias);
+                 (float*)yt, B, S, vocab, eps, mask, mask_bias, types, type_vocab);
     return;
   }
   if (f16)
     SPI_LAUNCH((bert_embed_kernel<_Float16>), grid, dim3(256), 0, s, ids, word, pos,
-                       type0, g, b, yf, (_Float16*)yt, B, S, D, vocab, eps, mask, mask_bias);
+                       type0, g, b, yf, (_Float16*)yt, B, S, D, vocab, eps, mask, mask_bias, types, type_vocab);
   else
     SPI_LAUNCH((bert_embed_kernel<float>), grid, dim3(256), 0, s, ids, word, pos,
-                       type0, g, b, yf, (float*)yt, B, S, D, vocab, eps, mask, mask_bias);
+                       type0, g, b, yf, (float*)yt, B, S, D, vocab, eps, mask, mask_bias, types, type_vocab);
 }
 
 void mask_to_bias(const int64_t* mask, float* bias, int n, hipStream_t s) {

@@ -26,8 +26,9 @@ std::mutex g_capture_mu;
 enum RnBuf { kRnIngest, kRnAct0, kRnAct1, kRnAct2, kRnAct3, kRnAct4, kRnPooled, kRnBufs };
 // BERT: hidden rows fp32 (fold: the pre-LN2 rows b as two fp16 planes) and their compute-type copy;
 // qkv; ctx; the attention block's output a, fp32 (fold: the pre-LN1 rows as two planes); the FFN
-// hidden rows; the LayerNorm-fold row statistics S1 (of a) and S2 (of b).
-enum BertBuf { kBtHidden, kBtHidden16, kBtQkv, kBtCtx, kBtAttn, kBtFfn, kBtStats1, kBtStats2, kBtBufs };
+// hidden rows; the LayerNorm-fold row statistics S1 (of a) and S2 (of b); the final LayerNorm's
+// class-token rows, fp32 (SPI_BERT_NO_HIDDEN with the pooler alone).
+enum BertBuf { kBtHidden, kBtHidden16, kBtQkv, kBtCtx, kBtAttn, kBtFfn, kBtStats1, kBtStats2, kBtCls, kBtBufs };
 // ViT: patches; projected patches f32; residual stream x f32 (fold: two fp16 planes); LN output; qkv;
 // ctx; mlp hidden; the LayerNorm'd class-token rows; the LayerNorm-fold row statistics of x.
 enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, kVtStats, kVtBufs };
@@ -42,6 +43,7 @@ struct Workspace {
   size_t partial_floats = 0;
   int* counters = nullptr;  // split-K tickets (zeroed once; the reducer re-zeroes its slot)
   bool has_mask = false;
+  const int64_t* mask_ids = nullptr;  // BERT: the task's attention_mask (the prologue's; read by the mean pool)
   int final_buf = kRnPooled;  // ResNet: buffer holding the last stage's output
   int final_hw = 0;           // ... and its pixels per image (avgpool window)
   std::map<int, hipGraphExec_t> graphs;
@@ -83,7 +85,7 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
   if (ni < 1 || ni > num_inputs_max())
     throw std::runtime_error("model expects " + std::to_string(num_inputs_max()) + " input(s), got " +
                              std::to_string(ni));
-  if (no != 1) throw std::runtime_error("Mismatch between model outputs and StarPU buffers");
+  if (no != num_outputs()) throw std::runtime_error("Mismatch between model outputs and StarPU buffers");
   const int64_t B = a.dims[0][0];
   if (B < 1 || B > m_.max_batch)
     throw std::runtime_error("batch " + std::to_string(B) + " exceeds replica max_batch " +
@@ -94,6 +96,7 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
     return e;
   };
   size_t expect_out = 0;
+  size_t expect_more[2] = {0, 0};  // BERT: the outputs after the first (bert_io)
   if (m_.family == SPI_FAMILY_AFFINE) {
     if (a.input_types[0] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Input type mismatch");
     if (in_bytes[0] < (size_t)elems(0) * 4) throw std::runtime_error("[ERROR] Input buffer too small");
@@ -109,7 +112,7 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
                                (u8 ? " or [B," + sz + "," + sz + ",3]" : ""));
     if (in_bytes[0] < (size_t)elems(0) * (u8 ? 1 : 4)) throw std::runtime_error("[ERROR] Input buffer too small");
     expect_out = (size_t)B * m_.classes * 4;
-  } else {  // BERT: input_ids [B,S] int64, optional attention_mask [B,S] int64
+  } else {  // BERT: input_ids [B,S] int64, optional attention_mask and (bert_io) token_type_ids, [B,S] int64
     for (int i = 0; i < ni; ++i) {
       if (a.input_types[i] != SPI_DTYPE_I64) throw std::runtime_error("[ERROR] Input type mismatch");
       if (a.num_dims[i] != 2 || a.dims[i][0] != B || a.dims[i][1] != a.dims[0][1])
@@ -119,10 +122,15 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
     const int64_t S = a.dims[0][1];
     if (S < 1 || S > m_.seq || S > m_.maxpos)
       throw std::runtime_error("sequence length " + std::to_string(S) + " exceeds " + std::to_string(m_.seq));
-    expect_out = (size_t)B * S * m_.D * 4;
+    // hidden [B,S,D] unless SPI_BERT_NO_HIDDEN, then the selected [B,D] sentence outputs
+    expect_out = (m_.bert_io & SPI_BERT_NO_HIDDEN) ? (size_t)B * m_.D * 4 : (size_t)B * S * m_.D * 4;
+    expect_more[0] = expect_more[1] = (size_t)B * m_.D * 4;
   }
-  if (a.output_types[0] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Output type mismatch");
-  if (out_bytes[0] != expect_out) throw std::runtime_error("Output buffer size mismatch in bytes");
+  for (int i = 0; i < no; ++i) {
+    if (a.output_types[i] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Output type mismatch");
+    if (out_bytes[i] != (i == 0 ? expect_out : expect_more[i - 1]))
+      throw std::runtime_error("Output buffer size mismatch in bytes");
+  }
 }
 
 int Model::input_kind(const spi_codelet_args& a) const {
@@ -174,6 +182,7 @@ double Model::flops(int64_t B) const {
            4.0 * B * S * S * m_.D;
     if (m_.family == SPI_FAMILY_VIT)
       f += 2.0 * B * m_.npatch * (double)m_.D * m_.patch_proj.k + 2.0 * B * m_.head.n * m_.head.k;
+    if (m_.bert_io & SPI_BERT_OUT_POOLER) f += 2.0 * B * (double)m_.D * m_.D;
   }
   return f;
 }
@@ -447,6 +456,7 @@ std::vector<size_t> Model::workspace_sizes_bert(size_t& partial) const {
   sz[kBtAttn] = T * D * 4;
   sz[kBtFfn] = T * m_.ffn * es;
   sz[kBtStats1] = sz[kBtStats2] = T * (D / 64) * 8;
+  sz[kBtCls] = (m_.bert_io & SPI_BERT_NO_HIDDEN) ? (size_t)m_.max_batch * D * 4 : 0;
   partial = std::max(partial, layers_partial((int)T));
   return sz;
 }
@@ -656,18 +666,43 @@ void Model::body_bert_folded(Workspace& w, int B, int S, hipStream_t s) {
   }
 }
 
-void Model::epilogue_bert(Workspace& w, int B, int S, void* out, hipStream_t s) {
+// The last LayerNorm and the outputs bert_io selects, in the order hidden, pooler, mean.  With the
+// hidden state selected the LayerNorm writes it as before and the sentence outputs read those fp32
+// rows.  Without it (SPI_BERT_NO_HIDDEN) the mean needs every row, so the LayerNorm goes into the fp32
+// workspace buffer that is dead after the last FFN2 (the fold's a planes, else the residual rows);
+// the pooler alone needs the B class-token rows only (row stride S D, as ViT's layernorm_cls).
+void Model::epilogue_bert(Workspace& w, int B, int S, void* const* out, hipStream_t s) {
   const LnW& l = m_.tf.back().ln2;
-  const int D = m_.D, T = B * S;
-  prof_op(s, "layernorm_out", 0, (double)T * D * 8, [&] {
+  const int D = m_.D, T = B * S, io = m_.bert_io;
+  const bool hidden = !(io & SPI_BERT_NO_HIDDEN), pooler = (io & SPI_BERT_OUT_POOLER) != 0,
+             mean = (io & SPI_BERT_OUT_MEAN) != 0;
+  const bool cls_only = !hidden && !mean;
+  int o = 0;
+  float* rows = hidden     ? static_cast<float*>(out[o++])
+                : cls_only ? static_cast<float*>(w.bufs[kBtCls])
+                           : static_cast<float*>(w.bufs[m_.ln_fold ? kBtAttn : kBtHidden]);
+  const int nrows = cls_only ? B : T, ldx = cls_only ? S * D : D;
+  prof_op(s, cls_only ? "layernorm_cls" : "layernorm_out", 0, (double)nrows * D * 8, [&] {
     // the last layer's pre-LN2 rows: the two-plane b under the LayerNorm fold, else a
     if (m_.ln_fold)
-      layernorm_planes(static_cast<const _Float16*>(w.bufs[kBtHidden]), (size_t)T * D, D, ptr<float>(l.g),
-                       ptr<float>(l.b), static_cast<float*>(out), nullptr, D, T, D, m_.eps, m_.f16, s);
+      layernorm_planes(static_cast<const _Float16*>(w.bufs[kBtHidden]), (size_t)T * D, ldx, ptr<float>(l.g),
+                       ptr<float>(l.b), rows, nullptr, D, nrows, D, m_.eps, m_.f16, s);
     else
-      layernorm(static_cast<float*>(w.bufs[kBtAttn]), D, ptr<float>(l.g), ptr<float>(l.b), static_cast<float*>(out),
-                nullptr, D, T, D, m_.eps, m_.f16, s);
+      layernorm(static_cast<float*>(w.bufs[kBtAttn]), ldx, ptr<float>(l.g), ptr<float>(l.b), rows, nullptr, D, nrows,
+                D, m_.eps, m_.f16, s);
   });
+  if (pooler) {
+    float* y = static_cast<float*>(out[o++]);
+    prof_op(s, "bert_pooler", 2.0 * B * D * (double)D, (double)D * D * 4 + (double)B * D * 8, [&] {
+      bert_pooler(rows, cls_only ? (size_t)D : (size_t)S * D, ptr<float>(m_.pool_w), ptr<float>(m_.pool_b), y, B, D, s);
+    });
+  }
+  if (mean) {
+    float* y = static_cast<float*>(out[o++]);
+    prof_op(s, "bert_mean_pool", 2.0 * T * D, (double)T * D * 4 + (double)B * D * 4, [&] {
+      masked_mean(rows, w.has_mask ? w.mask_ids : nullptr, y, B, S, D, s);
+    });
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -758,11 +793,16 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
       // the attention mask's additive bias is written by the embedding kernel (round 6: one launch
       // fewer per forward than a separate mask_to_bias)
       w.has_mask = in[1] != nullptr;
-      return prof_op(s, "bert_embed", 0, T * D * (4 * 3 + 4 + (f16 ? 2 : 0)) + (w.has_mask ? T * 12 : 0), [&] {
-        bert_embed(static_cast<const int64_t*>(in[0]), ptr<float>(m_.word), ptr<float>(m_.pos), ptr<float>(m_.type0),
-                   ptr<float>(m_.emb_ln.g), ptr<float>(m_.emb_ln.b), static_cast<float*>(w.bufs[kBtHidden]),
-                   f16 ? w.bufs[kBtHidden16] : nullptr, B, S, D, m_.vocab, m_.eps, f16, s,
-                   w.has_mask ? static_cast<const int64_t*>(in[1]) : nullptr, w.has_mask ? w.mask_bias : nullptr);
+      w.mask_ids = static_cast<const int64_t*>(in[1]);
+      // SPI_BERT_TOKEN_TYPES: the whole type table and, when the task brings them, its segment ids
+      const bool typed = (m_.bert_io & SPI_BERT_TOKEN_TYPES) != 0;
+      const int64_t* types = typed ? static_cast<const int64_t*>(in[2]) : nullptr;
+      return prof_op(s, "bert_embed", 0, T * D * (4 * 3 + 4 + (f16 ? 2 : 0)) + (w.has_mask ? T * 12 : 0) + (types ? T * 8 : 0), [&] {
+        bert_embed(static_cast<const int64_t*>(in[0]), ptr<float>(m_.word), ptr<float>(m_.pos),
+                   ptr<float>(typed ? m_.type_table : m_.type0), ptr<float>(m_.emb_ln.g), ptr<float>(m_.emb_ln.b),
+                   static_cast<float*>(w.bufs[kBtHidden]), f16 ? w.bufs[kBtHidden16] : nullptr, B, S, D, m_.vocab,
+                   m_.eps, f16, s, w.has_mask ? w.mask_ids : nullptr, w.has_mask ? w.mask_bias : nullptr, types,
+                   m_.type_vocab);
       });
     }
     case SPI_FAMILY_VIT:
@@ -786,7 +826,7 @@ void Model::epilogue(Workspace& w, int B, int S, void* const* out, hipStream_t s
       if (pooled_fc(w.final_hw)) return run_pooled_fc(w.bufs[w.final_buf], B, w.final_hw, out[0], w, s);
       return run_gemm(m_.fc, w.bufs[kRnPooled], B, m_.feat, out[0], m_.classes, true, Act::None, nullptr, false, 0, w,
                       s);
-    case SPI_FAMILY_BERT: return epilogue_bert(w, B, S, out[0], s);
+    case SPI_FAMILY_BERT: return epilogue_bert(w, B, S, out, s);
     case SPI_FAMILY_VIT:
       return run_gemm(m_.head, w.bufs[kVtCls], B, m_.D, out[0], m_.classes, true, Act::None, nullptr, false, 0, w, s);
   }

@@ -87,7 +87,14 @@ class Model {
                  int reps, float* ms, double* flops, double* bytes);
 
  private:
-  int num_inputs_max() const { return m_.family == SPI_FAMILY_BERT ? 2 : 1; }
+  int num_inputs_max() const {
+    return m_.family != SPI_FAMILY_BERT ? 1 : (m_.bert_io & SPI_BERT_TOKEN_TYPES) ? 3 : 2;
+  }
+  // BERT: the outputs bert_io selects, in order hidden, pooler, mean
+  int num_outputs() const {
+    if (m_.family != SPI_FAMILY_BERT) return 1;
+    return !(m_.bert_io & SPI_BERT_NO_HIDDEN) + !!(m_.bert_io & SPI_BERT_OUT_POOLER) + !!(m_.bert_io & SPI_BERT_OUT_MEAN);
+  }
   Workspace* workspace(hipStream_t s);
   hipGraphExec_t graph(Workspace& w, int batch, int S, hipStream_t s);
   // Forward: prologue (reads the task's input buffers) -> body (workspace only, graph-capturable)
@@ -106,7 +113,7 @@ class Model {
   void body_bert_folded(Workspace& w, int B, int S, hipStream_t s);
   void body_vit(Workspace& w, int B, hipStream_t s);
   void body_vit_folded(Workspace& w, int B, hipStream_t s);
-  void epilogue_bert(Workspace& w, int B, int S, void* out, hipStream_t s);
+  void epilogue_bert(Workspace& w, int B, int S, void* const* out, hipStream_t s);
   // The LayerNorm fold of one transformer GEMM (ln_fold.hpp).
   struct LnSpec {
     const float* in_stats = nullptr;  // A rows are pre-LN: their chunk statistics (L.c1 folded in)

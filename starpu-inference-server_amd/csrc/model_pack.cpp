@@ -386,6 +386,24 @@ void Packer::build_bert(const PMap& p) {
     stack_qkv(pre);
     m.tf[i].qkv = pack_linear_folded(qw.data(), qb.data(), 3 * D, D, p, layer(i - 1) + "output.LayerNorm");
   }
+  // bert_io appends only: a replica without bits keeps the blob above, byte for byte
+  m.type_vocab = (int)te->shape[0];
+  if (m.bert_io & SPI_BERT_TOKEN_TYPES) {
+    if (te->ndim != 2 || te->shape[1] != D) throw std::runtime_error("bert: token_type_embeddings.weight must be [types][D]");
+    m.type_table = pack_vec(fdata(te), (int)numel(te));
+  }
+  if (m.bert_io & SPI_BERT_OUT_POOLER) {
+    for (const char* nm : {"pooler.dense.weight", "pooler.dense.bias"})
+      if (!has(p, nm))
+        throw std::runtime_error(std::string("bert_io: SPI_BERT_OUT_POOLER needs parameter '") + nm +
+                                 "' (a model built with add_pooling_layer=False has no pooler)");
+    const spi_named_tensor* pw = need(p, "pooler.dense.weight");
+    const spi_named_tensor* pb = need(p, "pooler.dense.bias");
+    if (pw->ndim != 2 || pw->shape[0] != D || pw->shape[1] != D || numel(pb) != D)
+      throw std::runtime_error("bert: pooler.dense must be [D][D] with a [D] bias");
+    m.pool_w = pack_vec(fdata(pw), (int)numel(pw));
+    m.pool_b = pack_vec(fdata(pb), D);
+  }
 }
 
 void Packer::build_vit(const PMap& p) {
@@ -466,6 +484,14 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     else if (ends_with(p, "layer1.0.conv1.weight")) m.family = SPI_FAMILY_RESNET;
     else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT parameter names");
   }
+  if (const int io = cfg.bert_io) {  // spi_codelet.h: enum spi_bert_io
+    constexpr int known = SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | SPI_BERT_NO_HIDDEN | SPI_BERT_TOKEN_TYPES;
+    if (io & ~known) throw std::runtime_error("bert_io: unknown bits " + std::to_string(io & ~known));
+    if (m.family != SPI_FAMILY_BERT) throw std::runtime_error("bert_io is set, but the model is not a BERT");
+    if ((io & SPI_BERT_NO_HIDDEN) && !(io & (SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN)))
+      throw std::runtime_error("bert_io: SPI_BERT_NO_HIDDEN leaves no output; select SPI_BERT_OUT_POOLER or SPI_BERT_OUT_MEAN");
+    m.bert_io = io;
+  }
   pk.blob.add(nullptr, 256);  // offset 0: zero line read by the GEMM for padded chunks
   std::ostringstream os;
   if (m.family == SPI_FAMILY_AFFINE) {
@@ -495,6 +521,14 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
   }
   os << (m.mixed ? " f16m" : m.prec == Prec::F16 ? " f16" : m.prec == Prec::F16X3 ? " f16x3" : " f32") << " maxB"
      << m.max_batch;
+  if (m.bert_io) {
+    std::string outs;
+    for (const auto& o : {std::make_pair(!(m.bert_io & SPI_BERT_NO_HIDDEN), "hidden"),
+                          std::make_pair((m.bert_io & SPI_BERT_OUT_POOLER) != 0, "pooler"),
+                          std::make_pair((m.bert_io & SPI_BERT_OUT_MEAN) != 0, "mean")})
+      if (o.first) outs += (outs.empty() ? "" : ",") + std::string(o.second);
+    os << " out[" << outs << "] in[ids,mask" << ((m.bert_io & SPI_BERT_TOKEN_TYPES) ? ",types]" : "]");
+  }
   m.desc = os.str();
   m.blob = std::move(pk.blob.data);
   m.blob_bytes = m.blob.size();

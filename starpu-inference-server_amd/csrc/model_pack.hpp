@@ -75,6 +75,11 @@ struct PackedModel {
   // separate LayerNorm launches): no LN launch inside the encoder stack
   bool ln_fold = false;
   size_t word = 0, pos = 0, type0 = 0;
+  // BERT outputs / inputs (spi_model_config.bert_io, SPI_BERT_* bits); 0 leaves the blob as it was.
+  // SPI_BERT_TOKEN_TYPES appends the whole fp32 [type_vocab][D] table, SPI_BERT_OUT_POOLER
+  // pooler.dense as plain fp32 [D][D] plus its bias.
+  int bert_io = 0, type_vocab = 1;
+  size_t type_table = 0, pool_w = 0, pool_b = 0;
   LnW emb_ln, final_ln;
   std::vector<TfLayer> tf;
   // ViT

@@ -1,6 +1,7 @@
 // Stand-alone check of the host-only packer (make pack_check): packs three small models whose
 // tensors are synthesised here with the closed-form fill of tests/golden/make_replica_digests.py
-// and prints the digests, which equal that table's resnet_basic / bert_d128 / vit_d128 entries.
+// and prints the digests, which equal that table's resnet_basic / bert_d128 / vit_d128 entries; then the
+// BERT once more with every spi_model_config.bert_io bit set, checking what the bits append to the blob.
 // Built with the address and undefined-behaviour sanitizers, no HIP.
 #include <cstdio>
 #include <deque>
@@ -79,5 +80,21 @@ int main() {
       const spi::PackedModel m = spi::pack_model(cfg, c.t->t.data(), (int)c.t->t.size());
       std::printf("%s|%s| %016llx %zu %s\n", c.name, pr.name, (unsigned long long)m.digest, m.blob_bytes, m.desc.c_str());
     }
+  // bert_io: the same BERT plus its pooler, packed with every bit set.  The blob only grows by the
+  // appended fp32 type table [2][128] and pooler [128][128] + [128], each on its own 256-byte line.
+  bt.linear("bert.pooler.dense", 128, 128);
+  spi_model_config cfg{};
+  cfg.family = SPI_FAMILY_AUTO, cfg.precision = SPI_PREC_F16, cfg.max_batch = 8, cfg.num_heads = 2, cfg.seq_len = 16;
+  const spi::PackedModel plain = spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+  cfg.bert_io = SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | SPI_BERT_NO_HIDDEN | SPI_BERT_TOKEN_TYPES;
+  const spi::PackedModel io = spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+  std::printf("bert_d128|fp16|bert_io=15 %016llx %zu %s\n", (unsigned long long)io.digest, io.blob_bytes, io.desc.c_str());
+  const size_t grown = (2 * 128 + 128 * 128 + 128) * sizeof(float);
+  if (io.blob_bytes < plain.blob_bytes + grown || io.blob_bytes > plain.blob_bytes + grown + 3 * 256 ||
+      io.digest == plain.digest || io.type_table < plain.blob_bytes || io.pool_w <= io.type_table ||
+      io.pool_b + 128 * sizeof(float) != io.blob_bytes) {
+    std::fprintf(stderr, "bert_io packing: unexpected blob growth %zu -> %zu\n", plain.blob_bytes, io.blob_bytes);
+    return 1;
+  }
   return 0;
 }

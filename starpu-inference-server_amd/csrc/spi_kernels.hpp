@@ -147,11 +147,21 @@ void layernorm(const float* x, int ldx, const float* g, const float* b,
                hipStream_t s);
 // BERT embeddings: LN(word[ids] + pos[s] + type[0]) -> fp32 + compute type; with a mask, each
 // token's additive attention bias too (mask_to_bias's, one launch fewer per forward).  yf is
-// required (throws on null); yt may be null.
+// required (throws on null); yt may be null.  With types (int64 [B,S] segment ids), type0 is the
+// whole [type_vocab][D] table and row (b, s) adds its row clamp(types[b][s], 0, type_vocab - 1);
+// null types add row 0, the same sums in the same order.
 void bert_embed(const int64_t* ids, const float* word, const float* pos,
                 const float* type0, const float* g, const float* b, float* yf,
                 void* yt, int B, int S, int D, int vocab, float eps, bool f16,
-                hipStream_t s, const int64_t* mask = nullptr, float* mask_bias = nullptr);
+                hipStream_t s, const int64_t* mask = nullptr, float* mask_bias = nullptr,
+                const int64_t* types = nullptr, int type_vocab = 1);
+// BERT sentence outputs (bert_pool.hip): fp32, fixed summation order, D % 64 == 0 and D <= 1024.
+// Pooler: y[b][n] = tanh(bias[n] + sum_k h[b ld + k] W[n][k]); W fp32 [D][D], y [B][D].
+void bert_pooler(const float* h, size_t ld, const float* W, const float* bias, float* y, int B, int D,
+                 hipStream_t s);
+// Masked mean: y[b] = sum_s m[b][s] h[b][s] / max(sum_s m[b][s], 1e-9), m = (mask != 0); a null mask
+// counts every token.  h [B][S][D], y [B][D].
+void masked_mean(const float* h, const int64_t* mask, float* y, int B, int S, int D, hipStream_t s);
 // int64 attention mask [B,S] -> additive fp32 bias [B,S] (0 or finfo.min).
 void mask_to_bias(const int64_t* mask, float* bias, int n, hipStream_t s);
 // ViT: image (NCHW fp32, or 8-bit pixels of kind src, C = 3) -> patch rows [B*P, C*ps*ps] (compute type).

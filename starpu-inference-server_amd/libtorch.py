@@ -20,7 +20,7 @@ import os
 import numpy as np
 
 from . import _native as N
-from .codelet import InferenceExecutionException, ModelReplica, PRECISIONS, _FAMILIES, spi_dtype
+from .codelet import InferenceExecutionException, ModelReplica, PRECISIONS, _FAMILIES, bert_io_bits, spi_dtype
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPI_TORCH_LIB") or os.path.join(_HERE, "libspi_torch.so")
@@ -103,7 +103,7 @@ class TorchScriptModule:
 
     def replica(self, device_id: int = 0, precision: str = "fp16", max_batch: int = 8, family: str | None = None,
                 num_heads: int = 0, seq_len: int = 0, image_size: int = 0, eps: float = 0.0,
-                graphs: bool = False) -> ModelReplica:
+                graphs: bool = False, bert_io=0) -> ModelReplica:
         cfg = N.ModelConfig()
         cfg.family = _FAMILIES[family]
         cfg.precision = PRECISIONS[precision]
@@ -112,11 +112,12 @@ class TorchScriptModule:
         cfg.seq_len = seq_len
         cfg.image_size = image_size
         cfg.eps = eps
+        cfg.bert_io = bert_io_bits(bert_io)
         err = C.create_string_buffer(512)
         h = lib.spi_torch_create_replica(self.handle, device_id, C.byref(cfg), err, len(err))
         if not h:
             raise InferenceExecutionException(f"model replica creation failed: {err.value.decode()}")
-        return ModelReplica.from_handle(h, device_id, precision, max_batch, graphs)
+        return ModelReplica.from_handle(h, device_id, precision, max_batch, graphs, cfg.bert_io)
 
     def bench(self, inputs: list[np.ndarray], output_bytes: list[int], workers: int = 1, threads: int = 0,
               seconds: float = 5.0, max_tasks: int = 0, output_types=None) -> dict:

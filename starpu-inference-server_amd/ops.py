@@ -349,6 +349,28 @@ def bert_embed(prec, ids, word, pos, type0, gamma, beta, yf, yt, B, S, D, eps, m
     return yf, yt
 
 
+def bert_embed_types(prec, ids, word, pos, type_table, type_ids, gamma, beta, yf, yt, B, S, D, eps, mask=None,
+                     mask_bias=None, stream=None):
+    """bert_embed with segment ids: type_table fp32 [type_vocab][D], type_ids int64 [B S] or None (row 0)."""
+    _check(lib.spi_op_bert_embed_types(PREC[prec], _ptr(ids), _ptr(word), _ptr(pos), _ptr(type_table),
+                                       type_table.shape[0], _ptr(type_ids), _ptr(gamma), _ptr(beta), _ptr(yf), _ptr(yt),
+                                       B, S, D, word.shape[0], pos.shape[0], eps, _ptr(mask), _ptr(mask_bias),
+                                       _stream(stream)))
+    return yf, yt
+
+
+def bert_pooler(h, ld, W, bias, out, B, D, stream=None):
+    """out fp32 [B][D] = tanh(bias + h_rows W^T): row b of h starts ld floats after row b - 1 (fp32 throughout)."""
+    _check(lib.spi_op_bert_pooler(_ptr(h), ld, _ptr(W), _ptr(bias), _ptr(out), B, D, _stream(stream)))
+    return out
+
+
+def masked_mean(h, mask, out, B, S, D, stream=None):
+    """out fp32 [B][D] = masked mean over S of h fp32 [B][S][D]; mask int64 [B][S] or None (every token)."""
+    _check(lib.spi_op_masked_mean(_ptr(h), _ptr(mask), _ptr(out), B, S, D, _stream(stream)))
+    return out
+
+
 def mask_to_bias(mask, bias, n, stream=None):
     _check(lib.spi_op_mask_to_bias(_ptr(mask), _ptr(bias), n, _stream(stream)))
     return bias

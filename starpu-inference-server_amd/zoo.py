@@ -253,6 +253,31 @@ class BertWrapper(nn.Module):
         return self.bert(input_ids=input_ids, attention_mask=attention_mask, return_dict=False)[0]
 
 
+class BertTupleWrapper(nn.Module):
+    """HF's own output: (last_hidden_state, pooler_output), what a replica with bert_io "pooler" serves."""
+
+    def __init__(self, bert: nn.Module):
+        super().__init__()
+        self.bert = bert
+
+    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor):
+        out = self.bert(input_ids=input_ids, attention_mask=attention_mask, return_dict=False)
+        return out[0], out[1]
+
+
+class BertSegmentsWrapper(nn.Module):
+    """BertWrapper with the third input of sentence-pair tasks (bert_io "token_types")."""
+
+    def __init__(self, bert: nn.Module):
+        super().__init__()
+        self.bert = bert
+
+    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor,
+                token_type_ids: torch.Tensor) -> torch.Tensor:
+        return self.bert(input_ids=input_ids, attention_mask=attention_mask, token_type_ids=token_type_ids,
+                         return_dict=False)[0]
+
+
 def bert(layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072,
          vocab: int = 30522, max_position: int = 512, seed: int = 0, init_std: float = 0.02) -> BertWrapper:
     import logging
@@ -308,5 +333,5 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
 # name is not an identifier, so give the zoo's modules a loadable qualified name
 # (a traced/scripted model must round-trip through .pt like the reference's).
 for _cls in (BasicBlock, Bottleneck, ResNet, MLPBlock, EncoderBlock, Encoder, VisionTransformer, BertWrapper,
-             AddConstant):
+             BertTupleWrapper, BertSegmentsWrapper, AddConstant):
     _cls.__module__ = "spi_zoo"
