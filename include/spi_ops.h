@@ -58,6 +58,50 @@ int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_
                   int32_t stride, int32_t pad, const float* bias, const void* residual,
                   void* y, int32_t act, void* workspace, void* stream);
 
+/* ---- hi + lo fp16 weights (the fp16m layers: GemmDesc::krep = 2) ----
+ * A [N][K] fp32 matrix packed for fp16 activations at ~22 weight bits: rows padded to Npad = 128k, and per
+ * 64 logical k one 128-element packed block [64 hi | 64 lo], hi = fp16(w), lo = fp16(w - hi), so
+ * Kpad = 2 round_up(K, 64).  The kernel stages each A k-step twice, against the hi and the lo block, and
+ * accumulates both in fp32.  Padding (k >= K, rows N..Npad) is zero: this layout never carries the
+ * weight-resident conv's image rows, and spi_op_conv2d_hilo never routes to that kernel. */
+size_t spi_op_packed_bytes_hilo(int32_t N, int32_t K, int32_t* Npad, int32_t* Kpad);
+int spi_op_pack_weight_hilo(const float* w_host, int32_t N, int32_t K, void* dst_host);
+
+/* spi_op_gemm at precision fp16 on hi + lo weights (W_packed from spi_op_pack_weight_hilo): A fp16,
+ * residual fp16 unless res_f32, C fp16 unless out_f32.  Always the general kernel (gemm.hip). */
+int spi_op_gemm_hilo(const void* A, int32_t M, int32_t K, int32_t lda, const void* W_packed, int32_t N,
+                     const float* bias, const void* residual, int32_t res_f32, int32_t ldr, void* C,
+                     int32_t out_f32, int32_t ldc, int32_t act, void* workspace, void* stream);
+
+/* spi_op_conv2d at precision fp16 on hi + lo weights: x fp16, Cin a power of two >= 64 (one filter tap
+ * per k-step), KH KW <= 31; residual fp16 unless res_f32, y fp16 unless out_f32. */
+int spi_op_conv2d_hilo(const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* W_packed,
+                       int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* bias,
+                       const void* residual, int32_t res_f32, void* y, int32_t out_f32, int32_t act,
+                       void* workspace, void* stream);
+
+/* One conv of spi_op_conv_pair. */
+typedef struct spi_op_conv_spec {
+  const void* W_packed; /* spi_op_pack_weight at the call's precision, or spi_op_pack_weight_hilo when hilo */
+  int32_t Cout, KH, KW, stride, pad;
+  const float* bias;    /* fp32 [Cout] or null */
+  int32_t act;          /* 0 none, 1 relu, 2 gelu */
+  int32_t hilo;         /* hi + lo weights (precision fp16 only; Cin >= 64, KH KW <= 31) */
+  int32_t out_f32;      /* y is fp32 (not with the split layout) */
+  void* y;              /* [B][OH][OW][Cout] */
+} spi_op_conv_spec;
+
+/* Two convs on one input x [B][H][W][Cin] -- a ResNet block's first conv and its downsample conv -- as the
+ * model runs them: one grouped launch when their plans share a kernel instance (a joint split-K plan,
+ * conv 1's slabs and tickets behind conv 0's in the workspace), else one launch each.  No residual.
+ * precision, x and Cin as spi_op_conv2d.  plan_out (host, nullable) receives 22 integers in
+ * spi_debug_conv_pair_plan's order -- the two 8-field plans that launch, grouped, workgroups of both,
+ * conv 1's slab and ticket offsets, the summed workspace floats and ticket slots -- for the descriptors
+ * this call runs (hilo included, which the debug export cannot express). */
+int spi_op_conv_pair(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                     const spi_op_conv_spec* c0, const spi_op_conv_spec* c1, void* workspace, void* stream,
+                     int64_t* plan_out);
+
 /* Fused global average pool + linear layer (ResNet avgpool + fc in one launch):
  * x [B][HW][C] (fp32 / fp16 / split by precision, HW <= 64), W packed from the
  * [N][C] fc weight; y fp32 [B][N] = act(mean_hw(x) . W^T + bias). */
@@ -110,7 +154,7 @@ int spi_op_layernorm(int32_t precision, const float* x, const float* gamma, cons
 /* Host arithmetic of the fold for y = LN(x) W^T + b: w_folded [N][K] = W diag(gamma) (fp32),
  * bias_out [N] = b + W beta, c1_out [N] = sum_k of w_folded as packed -- rounded to fp16 for precision
  * fp16 (hi + lo when hilo), else the fp32 values.  b may be null.  All host fp32 arrays; pack w_folded
- * with spi_op_pack_weight. */
+ * with spi_op_pack_weight (spi_op_pack_weight_hilo when hilo). */
 int spi_op_fold_linear(int32_t precision, const float* w_host, const float* b_host, int32_t N, int32_t K,
                        const float* gamma_host, const float* beta_host, int32_t hilo, float* w_folded_out,
                        float* bias_out, float* c1_out);
@@ -137,6 +181,15 @@ int spi_op_gemm_ln(const void* A, int32_t M, int32_t K, int32_t lda, const void*
                    int32_t res_kind, int32_t ldr, const float* res_stats, const float* res_g, const float* res_b,
                    float eps, void* C, int32_t out_kind, int32_t ldc, size_t plane, float* out_stats, void* c16,
                    int32_t ld16, int32_t act, void* workspace, void* stream);
+
+/* spi_op_gemm_ln on hi + lo weights (the fp16m transformers' GEMMs): W_packed from spi_op_pack_weight_hilo
+ * of spi_op_fold_linear(hilo = 1)'s w_folded, c1 from the same call.  Same parameters, same rules; always
+ * the general kernel. */
+int spi_op_gemm_ln_hilo(const void* A, int32_t M, int32_t K, int32_t lda, const void* W_packed, int32_t N,
+                        const float* bias, const float* in_stats, const float* c1, const void* residual,
+                        int32_t res_kind, int32_t ldr, const float* res_stats, const float* res_g,
+                        const float* res_b, float eps, void* C, int32_t out_kind, int32_t ldc, size_t plane,
+                        float* out_stats, void* c16, int32_t ld16, int32_t act, void* workspace, void* stream);
 
 /* Row LayerNorm over rows held in two fp16 planes (x = hi + lo), D <= 1024, input row stride ldx:
  * yf fp32 and/or yt (fp16 when precision fp16, else fp32), row stride ldy. */

@@ -162,6 +162,29 @@ class ModelConfig(C.Structure):
 BERT_OUT_POOLER, BERT_OUT_MEAN, BERT_NO_HIDDEN, BERT_TOKEN_TYPES = 1, 2, 4, 8
 
 
+class ConvSpec(C.Structure):
+    """spi_op_conv_spec (include/spi_ops.h): one conv of spi_op_conv_pair."""
+
+    _fields_ = [
+        ("W_packed", C.c_void_p),
+        ("Cout", C.c_int32),
+        ("KH", C.c_int32),
+        ("KW", C.c_int32),
+        ("stride", C.c_int32),
+        ("pad", C.c_int32),
+        ("bias", C.c_void_p),
+        ("act", C.c_int32),
+        ("hilo", C.c_int32),
+        ("out_f32", C.c_int32),
+        ("y", C.c_void_p),
+    ]
+
+
+_GEMM_LN_ARGS = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                 C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
+                 C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                 C.c_void_p, C.c_void_p]
+
 # name -> (restype, argtypes): every function declared in include/spi_codelet.h
 _PROTOS = {
     "spi_hip_inference_func": (None, [C.c_void_p, C.c_void_p]),
@@ -232,10 +255,19 @@ _PROTOS = {
                                    C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "spi_op_fold_linear": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "spi_op_gemm_ln": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p,
-                                 C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spi_op_gemm_ln": (C.c_int, _GEMM_LN_ARGS),
+    "spi_op_gemm_ln_hilo": (C.c_int, _GEMM_LN_ARGS),
+    "spi_op_packed_bytes_hilo": (C.c_size_t, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "spi_op_pack_weight_hilo": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "spi_op_gemm_hilo": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p]),
+    "spi_op_conv2d_hilo": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spi_op_conv_pair": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.POINTER(ConvSpec), C.POINTER(ConvSpec), C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_int64)]),
     "spi_op_layernorm_planes": (C.c_int, [C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                           C.c_void_p]),

@@ -123,14 +123,17 @@ int spi_op_gemm(int32_t precision, const void* A, int32_t M, int32_t K, int32_t 
   });
 }
 
-int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* Wp,
-                  int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* bias,
-                  const void* residual, void* y, int32_t act, void* workspace, void* stream) {
-  spi::Prec p;
+namespace {
+
+// The descriptor of one op-level conv, as Model::conv_call builds a layer's; hilo: hi + lo weights.
+// Returns an error message, or null.
+const char* conv_desc_of(int32_t precision, spi::Prec p, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                         int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t act, bool hilo, bool out_f32,
+                         bool res_f32, spi::GemmDesc* out) {
   const int min_cin = precision == 1 ? 8 : 4;  // one 16-byte chunk: 8 fp16 or 4 fp32
-  if (!prec_of(precision, &p) || !x || !Wp || !y || !workspace || B <= 0 || Cin < min_cin ||
-      (Cin & (Cin - 1)) || Cout <= 0 || KH <= 0 || KW <= 0 || stride <= 0 || pad < 0 || act < 0 || act > 2)
-    return fail("invalid conv arguments");
+  if (B <= 0 || H <= 0 || W <= 0 || Cin < min_cin || (Cin & (Cin - 1)) || Cout <= 0 || KH <= 0 || KW <= 0 ||
+      stride <= 0 || pad < 0 || act < 0 || act > 2)
+    return "invalid conv arguments";
   spi::GemmDesc d;
   d.conv = true;
   d.H = H;
@@ -142,7 +145,7 @@ int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_
   d.pad = pad;
   d.OH = (H + 2 * pad - KH) / stride + 1;
   d.OW = (W + 2 * pad - KW) / stride + 1;
-  if (d.OH <= 0 || d.OW <= 0) return fail("empty conv output");
+  if (H + 2 * pad < KH || W + 2 * pad < KW || d.OH <= 0 || d.OW <= 0) return "empty conv output";
   d.M = B * d.OH * d.OW;
   d.N = Cout;
   d.K = KH * KW * Cin;
@@ -150,13 +153,37 @@ int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_
   d.ldc = Cout;
   d.ldr = Cout;
   d.act = static_cast<spi::Act>(act);
-  // W_packed comes from spi_op_pack_weight (spi_ops.h), which writes the image rows
-  d.w_image = spi::packed_has_wres_image(p, Cout, d.K, spi::round_up_to(Cout, 128), d.Kpad);
+  d.out_f32 = out_f32;
+  d.res_f32 = res_f32;
+  if (hilo) {
+    if (precision != 1) return "hi + lo weights are an fp16 layout";
+    if (Cin < 64 || KH * KW > 31) return "hi + lo conv needs Cin >= 64 and <= 31 filter taps";
+    d.krep = 2;
+    d.Kpad *= 2;
+  } else {
+    // W_packed comes from spi_op_pack_weight (spi_ops.h), which writes the image rows
+    d.w_image = spi::packed_has_wres_image(p, Cout, d.K, spi::round_up_to(Cout, 128), d.Kpad);
+  }
   if (precision == kSplitPrecision) {
     if (Cin < 32 || Cout % 32 || KH * KW > 31)
-      return fail("split conv needs Cin >= 32, Cout a multiple of 32 and <= 31 filter taps");
+      return "split conv needs Cin >= 32, Cout a multiple of 32 and <= 31 filter taps";
+    if (out_f32 || res_f32) return "the split layout has no fp32 operands";
     d.a_split = d.out_split = true;
   }
+  *out = d;
+  return nullptr;
+}
+
+}  // namespace
+
+int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* Wp,
+                  int32_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* bias,
+                  const void* residual, void* y, int32_t act, void* workspace, void* stream) {
+  spi::Prec p;
+  if (!prec_of(precision, &p) || !x || !Wp || !y || !workspace) return fail("invalid conv arguments");
+  spi::GemmDesc d;
+  if (const char* e = conv_desc_of(precision, p, B, H, W, Cin, Cout, KH, KW, stride, pad, act, false, false, false, &d))
+    return fail(e);
   if (!spi::gemm_workspace_fits(d, p, kSlabFloats, kTickets))
     return fail("conv too large for the op workspace");
   spi::GemmPtrs ptrs = scratch(workspace);
@@ -167,6 +194,124 @@ int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_
   ptrs.C = y;
   return guarded([&] {
     spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+// ---- hi + lo fp16 weights (GemmDesc::krep = 2) ----
+
+size_t spi_op_packed_bytes_hilo(int32_t N, int32_t K, int32_t* Npad, int32_t* Kpad) {
+  if (N <= 0 || K <= 0) return 0;
+  const int np = spi::round_up_to(N, 128), kp = 2 * spi::round_up_to(K, 64);
+  if (Npad) *Npad = np;
+  if (Kpad) *Kpad = kp;
+  return spi::packed_bytes(spi::Prec::F16, np, kp);
+}
+
+int spi_op_pack_weight_hilo(const float* w, int32_t N, int32_t K, void* dst) {
+  if (!w || !dst || N <= 0 || K <= 0) return fail("invalid pack arguments");
+  const int np = spi::round_up_to(N, 128), kp = 2 * spi::round_up_to(K, 64);
+  // as Packer::pack_weight (model_pack.cpp): a [N][kp] matrix of packed elements; kp is a multiple
+  // of 128, so never the 576 columns that carry the weight-resident conv's image rows
+  spi::pack_matrix_into(static_cast<char*>(dst), N, kp, np, kp, spi::Prec::F16, [&](int n, int k) {
+    return spi::hilo_element(k, K, [&](int kk) { return w[(size_t)n * K + kk]; });
+  });
+  return 0;
+}
+
+int spi_op_gemm_hilo(const void* A, int32_t M, int32_t K, int32_t lda, const void* W, int32_t N, const float* bias,
+                     const void* residual, int32_t res_f32, int32_t ldr, void* C, int32_t out_f32, int32_t ldc,
+                     int32_t act, void* workspace, void* stream) {
+  if (!A || !W || !C || !workspace || M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N || act < 0 || act > 2 ||
+      (residual && ldr < N))
+    return fail("invalid gemm_hilo arguments");
+  spi::GemmDesc d;
+  d.M = M;
+  d.N = N;
+  d.K = K;
+  d.Kpad = 2 * spi::round_up_to(K, 64);
+  d.krep = 2;
+  d.lda = lda;
+  d.ldc = ldc;
+  d.ldr = ldr;
+  d.act = static_cast<spi::Act>(act);
+  d.out_f32 = out_f32 != 0;
+  d.res_f32 = res_f32 != 0;
+  if (!spi::gemm_workspace_fits(d, spi::Prec::F16, kSlabFloats, kTickets))
+    return fail("gemm too large for the op workspace");
+  spi::GemmPtrs ptrs = scratch(workspace);
+  ptrs.A = A;
+  ptrs.W = W;
+  ptrs.bias = bias;
+  ptrs.res = residual;
+  ptrs.C = C;
+  return guarded([&] {
+    spi::gemm(d, ptrs, spi::Prec::F16, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_conv2d_hilo(const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* Wp, int32_t Cout,
+                       int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* bias, const void* residual,
+                       int32_t res_f32, void* y, int32_t out_f32, int32_t act, void* workspace, void* stream) {
+  if (!x || !Wp || !y || !workspace) return fail("invalid conv arguments");
+  spi::GemmDesc d;
+  if (const char* e = conv_desc_of(1, spi::Prec::F16, B, H, W, Cin, Cout, KH, KW, stride, pad, act, true,
+                                   out_f32 != 0, res_f32 != 0, &d))
+    return fail(e);
+  if (!spi::gemm_workspace_fits(d, spi::Prec::F16, kSlabFloats, kTickets))
+    return fail("conv too large for the op workspace");
+  spi::GemmPtrs ptrs = scratch(workspace);
+  ptrs.A = x;
+  ptrs.W = Wp;
+  ptrs.bias = bias;
+  ptrs.res = residual;
+  ptrs.C = y;
+  return guarded([&] {
+    spi::gemm(d, ptrs, spi::Prec::F16, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_conv_pair(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                     const spi_op_conv_spec* c0, const spi_op_conv_spec* c1, void* workspace, void* stream,
+                     int64_t* plan_out) {
+  spi::Prec p;
+  if (!prec_of(precision, &p) || !x || !workspace) return fail("invalid conv_pair arguments");
+  if (!c0 || !c1) return fail("conv_pair: null conv spec");
+  const spi_op_conv_spec* c[2] = {c0, c1};
+  spi::GemmDesc d[2];
+  spi::GemmPtrs ptrs[2];
+  for (int i = 0; i < 2; ++i) {
+    if (!c[i]->W_packed || !c[i]->y) return fail("conv_pair: a spec without weights or output");
+    if (const char* e = conv_desc_of(precision, p, B, H, W, Cin, c[i]->Cout, c[i]->KH, c[i]->KW, c[i]->stride,
+                                     c[i]->pad, c[i]->act, c[i]->hilo != 0, c[i]->out_f32 != 0, false, &d[i]))
+      return fail(e);
+    ptrs[i] = scratch(workspace);
+    ptrs[i].A = x;
+    ptrs[i].W = c[i]->W_packed;
+    ptrs[i].bias = c[i]->bias;
+    ptrs[i].C = c[i]->y;
+  }
+  if (!spi::gemm_workspace_fits(d[0], p, kSlabFloats, kTickets, &d[1]))
+    return fail("conv pair too large for the op workspace");
+  return guarded([&] {
+    if (plan_out) {
+      const spi::PairPlan pp = spi::plan_pair(d[0], d[1], p);
+      const spi::Plan* q[2] = {&pp.q0, &pp.q1};
+      for (int i = 0; i < 2; ++i) {
+        const int v[8] = {q[i]->bm, q[i]->bn, q[i]->stages, q[i]->splits, q[i]->halo, q[i]->win, q[i]->nw,
+                          q[i]->k_per_split};
+        for (int j = 0; j < 8; ++j) plan_out[i * 8 + j] = v[j];
+      }
+      plan_out[16] = pp.grouped;
+      plan_out[17] = pp.wgs;
+      plan_out[18] = (int64_t)pp.slab_off;
+      plan_out[19] = (int64_t)pp.ticket_off;
+      plan_out[20] = (int64_t)pp.partial_floats;
+      plan_out[21] = (int64_t)pp.counter_slots;
+    }
+    spi::gemm_pair(d[0], ptrs[0], d[1], ptrs[1], p, static_cast<hipStream_t>(stream));
     return check_launch();
   });
 }
@@ -297,11 +442,14 @@ int spi_op_fold_linear(int32_t precision, const float* w, const float* b, int32_
   return 0;
 }
 
-int spi_op_gemm_ln(const void* A, int32_t M, int32_t K, int32_t lda, const void* W, int32_t N, const float* bias,
-                   const float* in_stats, const float* c1, const void* residual, int32_t res_kind, int32_t ldr,
-                   const float* res_stats, const float* res_g, const float* res_b, float eps, void* C,
-                   int32_t out_kind, int32_t ldc, size_t plane, float* out_stats, void* c16, int32_t ld16,
-                   int32_t act, void* workspace, void* stream) {
+namespace {
+
+// spi_op_gemm_ln and its hi + lo weight twin (krep = 2: W packed by spi_op_pack_weight_hilo)
+int gemm_ln(int krep, const void* A, int32_t M, int32_t K, int32_t lda, const void* W, int32_t N, const float* bias,
+            const float* in_stats, const float* c1, const void* residual, int32_t res_kind, int32_t ldr,
+            const float* res_stats, const float* res_g, const float* res_b, float eps, void* C, int32_t out_kind,
+            int32_t ldc, size_t plane, float* out_stats, void* c16, int32_t ld16, int32_t act, void* workspace,
+            void* stream) {
   if (!A || !W || !C || !workspace || M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N || act < 0 || act > 2 ||
       out_kind < SPI_KIND_F16 || out_kind > SPI_KIND_PLANES ||
       (residual ? res_kind < SPI_KIND_F16 || res_kind > SPI_KIND_PLANES || ldr < N : res_kind != SPI_KIND_NONE))
@@ -313,7 +461,8 @@ int spi_op_gemm_ln(const void* A, int32_t M, int32_t K, int32_t lda, const void*
   d.M = M;
   d.N = N;
   d.K = K;
-  d.Kpad = spi::round_up_to(K, 64);
+  d.krep = krep;
+  d.Kpad = spi::round_up_to(K, 64) * krep;
   d.wplane = (size_t)spi::round_up_to(N, 128) * d.Kpad;
   d.lda = lda;
   d.ldc = ldc;
@@ -357,6 +506,26 @@ int spi_op_gemm_ln(const void* A, int32_t M, int32_t K, int32_t lda, const void*
     spi::gemm(d, ptrs, spi::Prec::F16, static_cast<hipStream_t>(stream));
     return check_launch();
   });
+}
+
+}  // namespace
+
+int spi_op_gemm_ln(const void* A, int32_t M, int32_t K, int32_t lda, const void* W, int32_t N, const float* bias,
+                   const float* in_stats, const float* c1, const void* residual, int32_t res_kind, int32_t ldr,
+                   const float* res_stats, const float* res_g, const float* res_b, float eps, void* C,
+                   int32_t out_kind, int32_t ldc, size_t plane, float* out_stats, void* c16, int32_t ld16,
+                   int32_t act, void* workspace, void* stream) {
+  return gemm_ln(1, A, M, K, lda, W, N, bias, in_stats, c1, residual, res_kind, ldr, res_stats, res_g, res_b, eps, C,
+                 out_kind, ldc, plane, out_stats, c16, ld16, act, workspace, stream);
+}
+
+int spi_op_gemm_ln_hilo(const void* A, int32_t M, int32_t K, int32_t lda, const void* W, int32_t N, const float* bias,
+                        const float* in_stats, const float* c1, const void* residual, int32_t res_kind, int32_t ldr,
+                        const float* res_stats, const float* res_g, const float* res_b, float eps, void* C,
+                        int32_t out_kind, int32_t ldc, size_t plane, float* out_stats, void* c16, int32_t ld16,
+                        int32_t act, void* workspace, void* stream) {
+  return gemm_ln(2, A, M, K, lda, W, N, bias, in_stats, c1, residual, res_kind, ldr, res_stats, res_g, res_b, eps, C,
+                 out_kind, ldc, plane, out_stats, c16, ld16, act, workspace, stream);
 }
 
 int spi_op_layernorm_planes(int32_t precision, const void* xh, size_t plane, int32_t ldx, const float* g,

@@ -104,6 +104,78 @@ def conv2d(prec, x_nhwc, W_packed, cout, kh, kw, stride, pad, bias=None, residua
     return out
 
 
+# ---- hi + lo fp16 weights (the fp16m layers, GemmDesc::krep = 2) and the grouped conv pair ----
+
+
+def pack_weight_hilo_host(w: np.ndarray | torch.Tensor) -> np.ndarray:
+    """[N][K] fp32 -> the hi + lo packed image as a host fp16 array [Npad][Kpad] (Kpad = 2 round_up(K, 64):
+    per 64 logical k a block [64 hi | 64 lo])."""
+    w = np.ascontiguousarray(np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float32))
+    n, k = w.shape
+    npad, kpad = C.c_int32(), C.c_int32()
+    nbytes = lib.spi_op_packed_bytes_hilo(n, k, C.byref(npad), C.byref(kpad))
+    host = np.empty(nbytes, dtype=np.uint8)
+    _check(lib.spi_op_pack_weight_hilo(w.ctypes.data, n, k, host.ctypes.data))
+    return host.view(np.float16).reshape(npad.value, kpad.value)
+
+
+def pack_weight_hilo(w: np.ndarray | torch.Tensor, device="cuda") -> torch.Tensor:
+    """[N][K] fp32 -> hi + lo packed device buffer (uint8 tensor)."""
+    return torch.from_numpy(pack_weight_hilo_host(w).reshape(-1).view(np.uint8)).to(device)
+
+
+def gemm_hilo(A, W_packed, N_, bias=None, residual=None, out=None, out_f32=True, act=None, ws=None, stream=None):
+    """gemm("fp16", ...) on hi + lo weights (pack_weight_hilo): A fp16; the residual's and out's dtype say
+    whether they are fp32."""
+    M, K = A.shape
+    if out is None:
+        out = torch.empty(M, N_, device=A.device, dtype=torch.float32 if out_f32 else torch.float16)
+    ws = workspace(A.device) if ws is None else ws
+    _check(lib.spi_op_gemm_hilo(_ptr(A), M, K, A.stride(0), _ptr(W_packed), N_, _ptr(bias), _ptr(residual),
+                                int(residual is not None and residual.dtype == torch.float32),
+                                residual.stride(0) if residual is not None else 0, _ptr(out),
+                                int(out.dtype == torch.float32), out.stride(0), ACT[act], _ptr(ws), _stream(stream)))
+    return out
+
+
+def conv2d_hilo(x_nhwc, W_packed, cout, kh, kw, stride, pad, bias=None, residual=None, act=None, ws=None,
+                stream=None, out=None, out_f32=False):
+    """conv2d("fp16", ...) on hi + lo weights: x fp16 NHWC, Cin >= 64; fp32 residual / output by dtype."""
+    B, H, W_, cin = x_nhwc.shape
+    oh, ow = (H + 2 * pad - kh) // stride + 1, (W_ + 2 * pad - kw) // stride + 1
+    if out is None:
+        out = torch.empty(B, oh, ow, cout, device=x_nhwc.device, dtype=torch.float32 if out_f32 else torch.float16)
+    ws = workspace(x_nhwc.device) if ws is None else ws
+    _check(lib.spi_op_conv2d_hilo(_ptr(x_nhwc), B, H, W_, cin, _ptr(W_packed), cout, kh, kw, stride, pad, _ptr(bias),
+                                  _ptr(residual), int(residual is not None and residual.dtype == torch.float32),
+                                  _ptr(out), int(out.dtype == torch.float32), ACT[act], _ptr(ws), _stream(stream)))
+    return out
+
+
+PAIR_PLAN_FIELDS = ("bm", "bn", "stages", "splits", "halo", "win", "nw", "k_per_split")
+
+
+def conv_spec(W_packed, cout, k, stride, pad, y, bias=None, act=None, hilo=False, out_f32=False):
+    """One conv of conv_pair (spi_op_conv_spec): a k x k filter, output buffer y."""
+    return N.ConvSpec(W_packed.data_ptr(), cout, k, k, stride, pad, None if bias is None else bias.data_ptr(),
+                      ACT[act], int(hilo), int(out_f32), y.data_ptr())
+
+
+def conv_pair(prec, x_nhwc, spec0, spec1, ws, stream=None):
+    """Two convs on one input as the ResNet forward runs a block's conv1 and downsample conv (grouped into
+    one launch when their plans allow).  spec0 / spec1: conv_spec(); the tensors they were built from must
+    stay alive until the call returns.  Returns the plan that ran: {"q0", "q1" (dicts of
+    PAIR_PLAN_FIELDS), "grouped", "wgs", "slab_off", "ticket_off", "partial_floats", "counter_slots"}."""
+    B, H, W_, cin = x_nhwc.shape
+    plan = (C.c_int64 * 22)()
+    _check(lib.spi_op_conv_pair(PREC[prec], _ptr(x_nhwc), B, H, W_, cin, None if spec0 is None else C.byref(spec0),
+                                None if spec1 is None else C.byref(spec1), _ptr(ws), _stream(stream), plan))
+    v = [int(t) for t in plan]
+    return {"q0": dict(zip(PAIR_PLAN_FIELDS, v[:8])), "q1": dict(zip(PAIR_PLAN_FIELDS, v[8:16])),
+            "grouped": bool(v[16]), "wgs": v[17], "slab_off": v[18], "ticket_off": v[19], "partial_floats": v[20],
+            "counter_slots": v[21]}
+
+
 def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None):
     D = heads * 64
     ctx = torch.empty(B * S, D, device=qkv.device, dtype=qkv.dtype)
@@ -266,15 +338,17 @@ def fold_linear(prec, w, b, gamma, beta, hilo=False):
 
 def gemm_ln(A, W_packed, N_, out, out_kind, M=None, K=None, lda=None, bias=None, in_stats=None, c1=None,
             residual=None, res_kind=None, ldr=None, res_stats=None, res_g=None, res_b=None, eps=1e-5, ldc=None,
-            plane=0, out_stats=None, c16=None, ld16=None, act=None, ws=None, stream=None):
+            plane=0, out_stats=None, c16=None, ld16=None, act=None, ws=None, stream=None, hilo=False):
     """spi_op_gemm_ln on caller-owned buffers (tensors used as plain HBM; strides default to N / K).
-    c1 may be a tensor or a raw device address (int)."""
+    c1 may be a tensor or a raw device address (int).  hilo: W_packed holds hi + lo weights
+    (pack_weight_hilo of fold_linear(hilo=True)'s), spi_op_gemm_ln_hilo."""
     M = A.shape[0] if M is None else M
     K = A.shape[1] if K is None else K
     ws = workspace(A.device) if ws is None else ws
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     c1p = C.c_void_p(c1) if isinstance(c1, int) else _ptr(c1)
-    _check(lib.spi_op_gemm_ln(_ptr(A), M, K, K if lda is None else lda, _ptr(W_packed), N_, _ptr(bias),
+    fn = lib.spi_op_gemm_ln_hilo if hilo else lib.spi_op_gemm_ln
+    _check(fn(_ptr(A), M, K, K if lda is None else lda, _ptr(W_packed), N_, _ptr(bias),
                               _ptr(in_stats), c1p, _ptr(residual), KIND[res_kind], N_ if ldr is None else ldr,
                               _ptr(res_stats), _ptr(res_g), _ptr(res_b), eps, _ptr(out), KIND[out_kind],
                               N_ if ldc is None else ldc, plane, _ptr(out_stats), _ptr(c16),

@@ -1,6 +1,7 @@
 """Plain float64 / bit-exact references of the ops behind include/spi_ops.h that the GPU op tests
-(test_qkv_attention_ops_gpu.py, test_elementwise_ops_gpu.py) compare the HIP kernels with, plus the
-inputs those tests share.  Nothing here touches a GPU; test_op_refs.py checks every reference
+(test_qkv_attention_ops_gpu.py, test_elementwise_ops_gpu.py, test_conv_pair_ops_gpu.py,
+test_hilo_weight_ops_gpu.py, the hi + lo consumer of test_ln_fold_ops_gpu.py) compare the HIP kernels with,
+plus the inputs and case lists those tests share.  Nothing here touches a GPU; test_op_refs.py checks every reference
 against the torch op it restates, so the GPU bars rest on checked ground.
 """
 import numpy as np
@@ -124,6 +125,184 @@ def emulate_qkv_attention(A16, W16, bias, mask_bias, B, S, heads, scale, stats=N
     p = torch.exp(s - s.max(-1, keepdim=True).values)
     o = (p.half().float() @ v) / p.sum(-1, keepdim=True)
     return o.permute(0, 2, 1, 3).reshape(B * S, D).half().numpy()
+
+
+# ---------------------------------------------------------------------------------------------
+# hi + lo fp16 weights (GemmDesc::krep = 2) and the grouped conv pair
+#
+# Every krep reference multiplies hilo_values(w): exactly the two fp16 numbers the kernel multiplies, summed.
+# What is left between the kernel and the float64 reference is the fp32 accumulation alone, so the fp32
+# output bar (1e-5) applies, and a kernel that dropped or misplaced the lo half sits above 1e-4
+# (test_op_refs.test_krep_cases_discriminate checks both sides for every case below).
+
+
+def hi_values(w):
+    """float64 fp16(w): what a plain fp16 pack holds."""
+    return np.asarray(w, np.float32).astype(np.float16).astype(np.float64)
+
+
+def hilo_values(w):
+    """float64 fp16(w) + fp16(w - fp16(w)): the weight a hi + lo pack holds."""
+    w = np.asarray(w, np.float32)
+    hi = w.astype(np.float16)
+    return hi.astype(np.float64) + (w - hi.astype(np.float32)).astype(np.float16).astype(np.float64)
+
+
+def hilo_layout(w):
+    """numpy construction of the hi + lo packed image of a [N][K] fp32 matrix: fp16 [Npad][Kpad], Npad =
+    round_up(N, 128), Kpad = 2 round_up(K, 64); logical k = 64 blk + j has hi at blk 128 + j, lo 64 further."""
+    w = np.asarray(w, np.float32)
+    n, k = w.shape
+    npad, kblk = -(-n // 128) * 128, -(-k // 64)
+    hi = np.zeros((npad, kblk * 64), np.float16)
+    lo = np.zeros((npad, kblk * 64), np.float16)
+    hi[:n, :k] = w.astype(np.float16)
+    lo[:n, :k] = (w - hi[:n, :k].astype(np.float32)).astype(np.float16)
+    img = np.stack([hi.reshape(npad, kblk, 64), lo.reshape(npad, kblk, 64)], axis=2)  # [Npad][blk][hi | lo][64]
+    return np.ascontiguousarray(img.reshape(npad, kblk * 128))
+
+
+# dense: (M, N, K); the chooser splits the last three into 4 to 6 slices
+KREP_DENSE = [(64, 64, 192), (100, 96, 160), (50, 1000, 96), (8, 128, 768), (197, 128, 1024), (64, 64, 1152)]
+KREP_FORMS = ["plain", "res32", "relu"]
+KREP_GELU = (100, 96, 160)  # fp16 output
+# SPI_GEMM_PLAN = "bm,bn,stages,splits" forced on one shape each; the first: 14 packed steps, and a 5-way
+# split has to round to whole (hi, lo) pairs -- 4 slices
+KREP_FORCED = [("64,64,2,5", (100, 96, 448)), ("64,64,3,3", (64, 64, 1152)), ("128,64,3,2", (197, 128, 1024)),
+               ("128,128,2,1", (50, 1000, 96))]
+# conv: (B, H, Cin, Cout, k, stride, pad)
+KREP_CONV = [(1, 12, 64, 128, 1, 2, 0), (1, 28, 128, 256, 1, 2, 0), (3, 11, 128, 256, 1, 2, 0),
+             (2, 13, 64, 128, 3, 2, 1)]
+KREP_CONV_RES = (1, 28, 128, 256, 1, 2, 0)  # fp32 residual, fp16 output
+# folded consumer: (M, N, K)
+KREP_FOLD = [(M, N, K) for M in (1, 100) for (N, K) in ((128, 64), (256, 192), (384, 640), (256, 1024))]
+
+# conv pairs: (B, H, Cin, (Cout0, k0, stride0, pad0), (Cout1, k1, stride1, pad1)) -> precisions
+_ALL = ("fp32", "fp16", "fp16x3", "fp16x3s")
+PAIR_CASES = [
+    ((1, 12, 64, (128, 3, 2, 1), (128, 1, 2, 0)), _ALL),
+    ((2, 13, 64, (128, 3, 2, 1), (128, 1, 2, 0)), _ALL),
+    ((1, 28, 128, (256, 3, 2, 1), (256, 1, 2, 0)), _ALL),
+    ((1, 14, 256, (512, 3, 2, 1), (512, 1, 2, 0)), _ALL),
+    ((4, 28, 128, (256, 3, 2, 1), (256, 1, 2, 0)), _ALL),
+    ((3, 11, 128, (64, 1, 1, 0), (256, 1, 2, 0)), _ALL),
+    ((1, 10, 512, (256, 1, 1, 0), (1024, 1, 2, 0)), _ALL),
+    ((1, 14, 1024, (512, 1, 1, 0), (2048, 1, 2, 0)), _ALL),
+    ((8, 56, 64, (128, 3, 2, 1), (128, 1, 2, 0)), ("fp16", "fp16x3s")),
+    ((6, 56, 256, (128, 1, 1, 0), (512, 1, 2, 0)), ("fp16", "fp16x3s")),
+    ((1, 9, 32, (64, 3, 2, 1), (64, 1, 2, 0)), ("fp16",)),
+    ((1, 28, 128, (128, 3, 1, 1), (256, 1, 1, 0)), ("fp16",)),
+]
+PAIR_PARAMS = [(c, p) for c, precs in PAIR_CASES for p in precs]
+# the fp16 cases whose conv 1 can carry hi + lo weights (Cin >= 64)
+PAIR_HILO_CASES = [c for c, precs in PAIR_CASES if "fp16" in precs and c[2] >= 64]
+
+
+def pair_id(case):
+    B, H, cin, c0, c1 = case
+    return f"{B}x{H}x{cin}-{c0[0]}k{c0[1]}s{c0[2]}-{c1[0]}k{c1[1]}s{c1[2]}"
+
+
+def krep_dense_case(M, N, K):
+    """Inputs shared by every form of a dense shape: fp16-exact A of N(0, 1), W of N(0, 1 / K), bias and an
+    fp32 residual at a quarter of the output's sigma (so they shift the normalisation by little)."""
+    rng = np.random.default_rng(M * 7 + N * 3 + K)
+    A16 = rng.standard_normal((M, K)).astype(np.float16)
+    W = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    b = (0.25 * rng.standard_normal(N)).astype(np.float32)
+    R = (0.25 * rng.standard_normal((M, N))).astype(np.float32)
+    return A16, W, b, R
+
+
+def gelu64(x):
+    t = torch.from_numpy(np.asarray(x, np.float64))
+    return (0.5 * t * (1 + torch.erf(t / 2 ** 0.5))).numpy()
+
+
+def epilogue64(acc, bias=None, res=None, act=None):
+    y = np.asarray(acc, np.float64)
+    if bias is not None:
+        y = y + np.asarray(bias, np.float64)
+    if res is not None:
+        y = y + np.asarray(res, np.float64)
+    return {None: y, "relu": np.maximum(y, 0), "gelu": gelu64(y)}[act]
+
+
+def dense_acc64(A, Wv):
+    """float64 A . Wv^T on the values as given."""
+    return np.asarray(A, np.float64) @ np.asarray(Wv, np.float64).T
+
+
+def dense_acc32_hilo(A16, W):
+    """The krep = 2 k-loop's arithmetic in torch on the CPU: fp32 accumulation of A . hi^T and A . lo^T."""
+    a = torch.from_numpy(np.asarray(A16, np.float32))
+    w = np.asarray(W, np.float32)
+    hi = w.astype(np.float16)
+    lo = (w - hi.astype(np.float32)).astype(np.float16)
+    return (a @ torch.from_numpy(hi.astype(np.float32)).T + a @ torch.from_numpy(lo.astype(np.float32)).T).numpy()
+
+
+def conv_case(B, H, cin, convs, seed=None):
+    """Inputs of convs on one NHWC input: x fp32 [B][H][H][cin] of N(0, 1) and per conv (cout, k, stride, pad)
+    the weight [cout][k][k][cin] of He scale (its reshape to [cout][k k cin] is the matrix to pack) and a
+    bias of N(0, 1)."""
+    rng = np.random.default_rng(B * 1000 + H * 10 + cin if seed is None else seed)
+    x = rng.standard_normal((B, H, H, cin)).astype(np.float32)
+    ws = []
+    for cout, k, _, _ in convs:
+        w = (rng.standard_normal((cout, k, k, cin)) * np.sqrt(2.0 / (cin * k * k))).astype(np.float32)
+        ws.append((w, rng.standard_normal(cout).astype(np.float32)))
+    return x, ws
+
+
+def conv_acc(x_vals, w_vals, stride, pad, dtype=torch.float64):
+    """NHWC conv of x_vals [B][H][W][C] with w_vals [cout][k][k][C] on the values as given, in dtype
+    (float64: the reference; float32: an fp32-accumulated emulation) -> numpy [B][OH][OW][cout]."""
+    x = torch.from_numpy(np.ascontiguousarray(x_vals)).to(dtype).permute(0, 3, 1, 2)
+    w = torch.from_numpy(np.ascontiguousarray(w_vals)).to(dtype).permute(0, 3, 1, 2)
+    return torch.nn.functional.conv2d(x, w, None, stride, pad).permute(0, 2, 3, 1).contiguous().numpy()
+
+
+def conv_acc32_hilo(x16, w, stride, pad):
+    """fp32 accumulation of the conv against fp16(w) and against the lo half, summed (the krep = 2 loop)."""
+    w = np.asarray(w, np.float32)
+    hi = w.astype(np.float16)
+    lo = (w - hi.astype(np.float32)).astype(np.float16)
+    x = np.asarray(x16, np.float32)
+    return conv_acc(x, hi.astype(np.float32), stride, pad, torch.float32) + \
+        conv_acc(x, lo.astype(np.float32), stride, pad, torch.float32)
+
+
+def krep_fold_case(ops, M, N, K):
+    """A LayerNorm + linear layer folded for hi + lo weights: rows of make_rows behind gamma = 1 + 0.3 N with
+    three gains of 8, beta = 0.1 N with three of +-3 (test_ln_fold_ops_gpu.make_ln).  Returns A16, the
+    statistics of the fp32 rows (fp32), W' (fp32, to pack hi + lo), bias', c1."""
+    rng = np.random.default_rng(N * 11 + K)
+    W = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    b = rng.standard_normal(N).astype(np.float32)
+    gamma = (1 + 0.3 * rng.standard_normal(K)).astype(np.float32)
+    beta = (0.1 * rng.standard_normal(K)).astype(np.float32)
+    gamma[[1, K // 2, K - 3]] = 8.0
+    beta[[2, K // 3, K - 1]] = [3.0, -3.0, 3.0]
+    wf, bias, c1 = ops.fold_linear("fp16", W, b, gamma, beta, hilo=True)
+    x = make_rows(np.random.default_rng(M * 13 + N + K), M, K)
+    stats = ops.chunk_stats(x.astype(np.float64)).astype(np.float32)
+    return x.astype(np.float16), stats, wf, bias, c1
+
+
+def fold_consumer64(acc, stats, c1, bias, eps=EPS):
+    """The consumer epilogue rstd (acc - mean c1) + bias' in float64."""
+    mean, rstd = combine_stats64(stats, eps)
+    return rstd[:, None] * (np.asarray(acc, np.float64) - mean[:, None] * np.asarray(c1, np.float64)) + \
+        np.asarray(bias, np.float64)
+
+
+def fold_consumer32(acc32, stats, c1, bias, eps=EPS):
+    """The same epilogue in fp32 on an fp32 accumulator."""
+    mean, rstd = combine_stats64(stats, eps)
+    mean, rstd = mean.astype(np.float32), rstd.astype(np.float32)
+    return rstd[:, None] * (np.asarray(acc32, np.float32) - mean[:, None] * np.asarray(c1, np.float32)) + \
+        np.asarray(bias, np.float32)
 
 
 # ---------------------------------------------------------------------------------------------

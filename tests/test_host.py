@@ -220,3 +220,35 @@ def test_fold_linear_packing_arithmetic(N, K, hilo, with_b):
     assert np.array_equal(c1_f32, wf_ref.astype(np.float64).sum(1).astype(np.float32))
     with pytest.raises(ops.OpError):
         ops.fold_linear("fp32", w, b, gamma, beta, hilo=True)
+
+
+@pytest.mark.parametrize("N,K", [(64, 64), (70, 96), (128, 160), (200, 576), (1000, 96)])
+def test_pack_weight_hilo_layout(N, K):
+    """spi_op_pack_weight_hilo against a numpy construction of the layout (op_refs.hilo_layout): per 64
+    logical k a 128-element block, hi = fp16(w) at blk 128 + j and lo = fp16(w - hi) 64 further; the K tail
+    (K = 96, 160: half a block) and the rows N..Npad are zero -- a 64 x 576 matrix included, whose plain
+    fp16 pack carries the weight-resident conv's image there; sizes from spi_op_packed_bytes_hilo."""
+    import ctypes as C
+    import importlib
+    import op_refs as R
+    ops = importlib.import_module("starpu-inference-server_amd.ops")
+    npad, kpad = C.c_int32(), C.c_int32()
+    nbytes = ops.lib.spi_op_packed_bytes_hilo(N, K, C.byref(npad), C.byref(kpad))
+    assert (npad.value, kpad.value) == (-(-N // 128) * 128, 2 * (-(-K // 64) * 64))
+    assert nbytes == npad.value * kpad.value * 2
+    w = (np.random.default_rng(N + K).standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    img = ops.pack_weight_hilo_host(w)
+    assert img.shape == (npad.value, kpad.value) and img.dtype == np.float16
+    np.testing.assert_array_equal(img.view(np.uint16), R.hilo_layout(w).view(np.uint16))
+    # spelled out once more without the helper: element (n, k) and its lo half, the tail, the padding rows
+    n, k = N - 1, K - 1
+    hi = np.float16(w[n, k])
+    assert img[n, (k // 64) * 128 + k % 64] == hi
+    assert img[n, (k // 64) * 128 + 64 + k % 64] == np.float16(w[n, k] - np.float32(hi))
+    if K % 64:
+        blk = K // 64
+        assert not img[:, blk * 128 + K % 64:blk * 128 + 64].any() and not img[:, blk * 128 + 64 + K % 64:].any()
+    assert not img[N:].any()
+    assert (img[:N, 64:128] != 0).mean() > 0.9  # the lo half is there
+    with pytest.raises(ops.OpError):
+        ops.pack_weight_hilo_host(np.zeros((0, 8), np.float32))

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+import op_refs
+
 pytestmark = pytest.mark.gpu
 
 EPS = 1e-5
@@ -207,6 +209,40 @@ def test_consumer_general_kernel(ops, ws, M, N, K, act):
     """gemm.hip's consumer fold at 1, 3, 10, 16 chunks (ln_row_stats' all-loads-first form) and 17 (its
     loop form, past every model's width), one row / ragged tiles."""
     run_consumer(ops, ws, M, N, K, act, want_g256=False)
+
+
+def run_consumer_hilo(ops, ws, M, N, K, act, out_dtype):
+    """run_consumer on hi + lo weights (the fp16m transformers: krep = 2): W', bias' and c1 from
+    fold_linear(hilo=True), W' packed by pack_weight_hilo, the reference on hilo_values(W')."""
+    A16, stats, wf, bias, c1 = op_refs.krep_fold_case(ops, M, N, K)
+    ref = op_refs.fold_consumer64(A16.astype(np.float64) @ op_refs.hilo_values(wf).T, stats, c1, bias, EPS)
+    if act == "gelu":
+        ref = gelu64(ref)
+    out = (C.c_longlong * 14)()
+    flags = (ACT_F if act else 0) | (OUT_F32_F if out_dtype == torch.float32 else 0) | (K // 64) << 8
+    assert ops.lib.spi_debug_gemm_plan(1, M, N, K, K, 2, 0, C.c_uint(flags), out) == 0
+    assert int(out[0]) == 0, f"routing: krep = 2 on gemm256 (tile height {int(out[0])})"
+    y = guarded(M, N, dtype=out_dtype)
+    ops.gemm_ln(torch.from_numpy(A16).cuda(), ops.pack_weight_hilo(wf), N, y,
+                "fp32" if out_dtype == torch.float32 else "fp16", bias=torch.from_numpy(bias).cuda(),
+                in_stats=torch.from_numpy(stats).cuda(), c1=torch.from_numpy(c1).cuda(), eps=EPS, act=act, ws=ws,
+                hilo=True)
+    assert_guard(y, M, "C")
+    e = nerr(y[:M].float().cpu().numpy(), ref)
+    print(f"consumer hi + lo {M}x{N}x{K} {act} splits={int(out[7])}: {e:.3e}")
+    return e
+
+
+@pytest.mark.parametrize("M,N,K", op_refs.KREP_FOLD)
+def test_consumer_hilo_weights(ops, ws, M, N, K):
+    """The consumer fold over the hi + lo k-loop at 1, 3, 10 and 16 chunks into an fp32 output: the bar that
+    sees the lo half (test_op_refs.test_krep_folded_consumer_discriminates: without it > 1e-4)."""
+    assert run_consumer_hilo(ops, ws, M, N, K, None, torch.float32) < TOL32
+
+
+@pytest.mark.parametrize("M,N,K", [(100, 384, 640)])
+def test_consumer_hilo_weights_gelu_fp16_out(ops, ws, M, N, K):
+    assert run_consumer_hilo(ops, ws, M, N, K, "gelu", torch.float16) < TOL16
 
 
 @pytest.mark.parametrize("K", [128, 384, 640, 1024])

@@ -95,6 +95,86 @@ def test_combine_stats_restated(ops):
     np.testing.assert_allclose(R.combine_stats64(st, R.EPS)[1], 1 / np.sqrt(x.var(1) + R.EPS), rtol=1e-12)
 
 
+# ---- hi + lo weights (krep = 2) -----------------------------------------------------------------
+
+# What the krep GPU tests (test_hilo_weight_ops_gpu.py, the fp16m pair of test_conv_pair_ops_gpu.py, the
+# folded consumer of test_ln_fold_ops_gpu.py) can tell apart at their 1e-5 bar: a contraction over fp16(w)
+# alone must sit above HI_ONLY_MIN from the hi + lo float64 reference, an fp32-accumulated emulation of the
+# right arithmetic below EMU32_MAX.  Measured here over every case: hi only 1.1e-4 to 5.4e-4, emulation
+# 1e-7 to 1.2e-6.
+HI_ONLY_MIN, EMU32_MAX = 1e-4, 3e-6
+
+
+def _dense_sides(form, M, N, K):
+    A16, W, b, Rr = R.krep_dense_case(M, N, K)
+    res, act = (Rr if form == "res32" else None), {"relu": "relu", "gelu": "gelu"}.get(form)
+    ref = R.epilogue64(R.dense_acc64(A16, R.hilo_values(W)), b, res, act)
+    hi = R.epilogue64(R.dense_acc64(A16, R.hi_values(W)), b, res, act)
+    emu = R.epilogue64(R.dense_acc32_hilo(A16, W), b, res, act)
+    return ref, hi, emu
+
+
+def _conv_sides(B, H, cin, cout, k, stride, pad, res=False):
+    x, [(w, b)] = R.conv_case(B, H, cin, [(cout, k, stride, pad)])
+    x16 = x.astype(np.float16)
+    ref = R.conv_acc(x16, R.hilo_values(w), stride, pad)
+    r = np.random.default_rng(H + cout).standard_normal(ref.shape).astype(np.float32) if res else None
+    return (R.epilogue64(ref, b, r), R.epilogue64(R.conv_acc(x16, R.hi_values(w), stride, pad), b, r),
+            R.epilogue64(R.conv_acc32_hilo(x16, w, stride, pad), b, r))
+
+
+def _pair_sides(case):
+    """Conv 1 of a pair case, on the weights the pair test draws for it."""
+    B, H, cin, c0, c1 = case
+    x, wb = R.conv_case(B, H, cin, [c0, c1])
+    x16, (w, b) = x.astype(np.float16), wb[1]
+    return (R.epilogue64(R.conv_acc(x16, R.hilo_values(w), c1[2], c1[3]), b),
+            R.epilogue64(R.conv_acc(x16, R.hi_values(w), c1[2], c1[3]), b),
+            R.epilogue64(R.conv_acc32_hilo(x16, w, c1[2], c1[3]), b))
+
+
+def _fold_sides(ops, M, N, K):
+    A16, stats, wf, bias, c1 = R.krep_fold_case(ops, M, N, K)
+    return (R.fold_consumer64(R.dense_acc64(A16, R.hilo_values(wf)), stats, c1, bias),
+            R.fold_consumer64(R.dense_acc64(A16, R.hi_values(wf)), stats, c1, bias),
+            R.fold_consumer32(R.dense_acc32_hilo(A16, wf), stats, c1, bias))
+
+
+KREP_SIDES = (
+    [(f"dense-{M}x{N}x{K}-{f}", _dense_sides, (f, M, N, K)) for (M, N, K) in R.KREP_DENSE for f in R.KREP_FORMS]
+    + [("dense-gelu", _dense_sides, ("gelu",) + R.KREP_GELU)]
+    + [(f"forced-{plan}", _dense_sides, ("plain",) + shape) for plan, shape in R.KREP_FORCED]
+    + [("conv-" + "x".join(map(str, c)), _conv_sides, c) for c in R.KREP_CONV]
+    + [("conv-res", _conv_sides, R.KREP_CONV_RES + (True,))]
+    + [("pair-" + R.pair_id(c), _pair_sides, (c,)) for c in R.PAIR_HILO_CASES])
+
+
+@pytest.mark.parametrize("what,sides,args", KREP_SIDES, ids=[s[0] for s in KREP_SIDES])
+def test_krep_cases_discriminate(what, sides, args):
+    ref, hi, emu = sides(*args)
+    e_hi, e_emu = R.nerr(hi, ref), R.nerr(emu, ref)
+    print(f"{what}: hi only {e_hi:.3e}, fp32 emulation {e_emu:.3e}")
+    assert e_hi > HI_ONLY_MIN and e_emu < EMU32_MAX
+
+
+@pytest.mark.parametrize("M,N,K", R.KREP_FOLD)
+def test_krep_folded_consumer_discriminates(ops, M, N, K):
+    ref, hi, emu = _fold_sides(ops, M, N, K)
+    e_hi, e_emu = R.nerr(hi, ref), R.nerr(emu, ref)
+    print(f"fold {M}x{N}x{K}: hi only {e_hi:.3e}, fp32 emulation {e_emu:.3e}")
+    assert e_hi > HI_ONLY_MIN and e_emu < EMU32_MAX
+
+
+def test_hilo_values_are_what_the_pack_holds(ops):
+    """hilo_values against the packed image itself, and |lo| <= ulp(hi) / 2."""
+    w = (np.random.default_rng(8).standard_normal((70, 96)) * 3).astype(np.float32)
+    img = ops.pack_weight_hilo_host(w).astype(np.float64)
+    blocks = img[:70].reshape(70, 2, 2, 64)  # [n][blk][hi | lo][64]
+    np.testing.assert_array_equal((blocks[:, :, 0] + blocks[:, :, 1]).reshape(70, 128)[:, :96], R.hilo_values(w))
+    assert (np.abs(R.hilo_values(w) - R.hi_values(w)) <= np.spacing(np.abs(w.astype(np.float16))).astype(np.float64) / 2).all()
+    assert R.nerr(R.hilo_values(w), w.astype(np.float64)) < 2.0 ** -21
+
+
 # ---- the HBM-bound kernels ----------------------------------------------------------------------
 
 
