@@ -26,7 +26,15 @@
 // write-through (sc1) and the last to arrive (relaxed agent-scope ticket) sums
 // them with sc1 loads and runs the epilogue -- no second launch, no cache-wide
 // fences (cdna_hip_programming.md, "In-launch split-K reduction").
+//
+// This file holds the kernels, the table of their instances and the launch.  What the host does
+// before a launch is host-only code, checked without a GPU: the plan (gemm_plan.cpp), the desc
+// checks and the kernel arguments (gemm_args.cpp), and in gemm_args.hpp the argument structs and the
+// workgroup -> (tile, slice) decode, which the kernels below and the CPU tests both call.
+// The diagnostic builds' macros and readers are gemm_diag.hpp.
 #include "device_math.hpp"
+#include "gemm_args.hpp"
+#include "gemm_diag.hpp"
 #include "gemm_plan.hpp"
 #include "ln_fold.hpp"
 #include "spi_kernels.hpp"
@@ -45,155 +53,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-
-// Diagnostic build only (-DSPI_GEMM_STAMPS): per-block s_memtime phase totals.
-#ifdef SPI_GEMM_STAMPS
-__device__ unsigned long long g_gemm_stamps[65536 * 8];
-#define SPI_STAMP(v)                                                                         \
-  do {                                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");               \
-    __builtin_amdgcn_sched_barrier(0);                                                       \
-  } while (0)
-#else
-#define SPI_STAMP(v) \
-  do {               \
-  } while (0)
-#endif
-// Diagnostic build only (-DSPI_GEMM_TIMELINE): four s_memrealtime stamps per
-// workgroup (entry, k-loop start, k-loop end, exit; 100 MHz) and the hardware
-// ids (HW_ID: CU / SE; XCC_ID), so tools/gemm_timeline.py can split a launch
-// into dispatch skew, prologue, loop and epilogue and see how workgroups pack
-// onto CUs.  The real kernel has none of this.
-#ifdef SPI_GEMM_TIMELINE
-__device__ unsigned long long g_gemm_timeline[65536 * 8];
-// launches made by a thread inside spi_debug_gemm_timeline_enable(1) .. (0) carry KArgs::tl = 1
-// (Model::profile_op on the repeated op), so other streams' launches never stamp
-int& tl_thread() {
-  static thread_local int on = 0;
-  return on;
-}
-#define SPI_RT(v)                                                                  \
-  do {                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory"); \
-    __builtin_amdgcn_sched_barrier(0);                                             \
-  } while (0)
-#else
-#define SPI_RT(v) \
-  do {            \
-  } while (0)
-#endif
-
-// Diagnostic builds: -DSPI_DIAG_NO_DMA issues no LDS-DMA (the tiles hold stale
-// bytes), -DSPI_DIAG_NO_MFMA reads the fragments but issues no MFMA; timed
-// against the real kernel (tools/ab_gemm.py) they split a launch into data
-// movement and matrix work.  Outputs of both are meaningless.
-#ifdef SPI_DIAG_NO_DMA
-#define SPI_DMA(src, dst, sz, off, aux) \
-  do {                                  \
-    (void)(src);                        \
-    (void)(dst);                        \
-  } while (0)
-#else
-#define SPI_DMA(src, dst, sz, off, aux) __builtin_amdgcn_global_load_lds(src, dst, sz, off, aux)
-#endif
-// Diagnostic build -DSPI_DIAG_L2A: every A-operand DMA reads from the first 64 KiB
-// of A (same instruction count and addressing work, almost no L2-miss traffic);
-// timed against the real kernel it separates memory-side traffic from the rest.
-// Diagnostic builds -DSPI_DIAG_NO_DMA_A / _W: drop only the A-operand (incl.
-// halo) or only the weight DMAs.
-#ifdef SPI_DIAG_NO_DMA_A
-#define SPI_DMA_A(src, dst, sz, off, aux) \
-  do {                                    \
-    (void)(src);                          \
-    (void)(dst);                          \
-  } while (0)
-#else
-#define SPI_DMA_A SPI_DMA
-#endif
-#ifdef SPI_DIAG_NO_DMA_W
-#define SPI_DMA_W(src, dst, sz, off, aux) \
-  do {                                    \
-    (void)(src);                          \
-    (void)(dst);                          \
-  } while (0)
-#else
-#define SPI_DMA_W SPI_DMA
-#endif
-#ifdef SPI_DIAG_L2A
-#define SPI_A_SRC(ptr_) \
-  (reinterpret_cast<const char*>(a.p.A) + ((reinterpret_cast<const char*>(ptr_) - reinterpret_cast<const char*>(a.p.A)) & 0xFFF0))
-#else
-#define SPI_A_SRC(ptr_) (ptr_)
-#endif
-
-// n / d for 0 <= n < 2^31 by one high multiply (host-computed magic, Granlund-Montgomery
-// round-up form: 2^s < d <= 2^(s+1), magic = ceil(2^(32+s) / d) < 2^32, exact since the
-// magic's error (< d) times n stays below 2^(32+s)); d = 1 is magic 0.  The prologue of a
-// launch divides a dozen times (tile decode, output row -> image / row / column), and the
-// compiler's generic 32-bit division is ~40 instructions of dependent SALU / VALU each.
-struct FastDiv {
-  unsigned magic;
-  int shift;
-};
-__host__ __device__ inline FastDiv make_fastdiv(unsigned d) {
-  if (d <= 1) return FastDiv{0u, 0};
-  int s = 0;
-  while ((2ull << s) < d) ++s;  // 2^s < d <= 2^(s+1)
-  return FastDiv{(unsigned)(((1ull << (32 + s)) + d - 1) / d), s};
-}
-__device__ __forceinline__ int fdiv(int n, FastDiv f) {
-  return f.magic ? (int)(__umulhi((unsigned)n, f.magic) >> f.shift) : n;
-}
-
-struct KArgs {
-  GemmDesc d;
-  GemmPtrs p;
-  int k_per_split;  // elements, multiple of the k-step
-  int tiles_m, tiles_n;
-  int tiles;
-  int cin_shift;
-  int kw_mul;       // ceil(65536 / KW): cell / KW == (cell * kw_mul) >> 16 for cell < 2^12
-  int cell_uniform; // conv with Cin >= k-step: one (kh, kw) cell per step
-  int vec_ok;       // C / residual rows allow 16-byte vectors of 8 elements (epilogue)
-  int xg_m, xg_n;   // XCD rectangles: tile rows in xg_m groups x tile columns in xg_n groups
-  // the rectangles' first tile row per row group (rg_m0[xg_m] = tiles_m) and first tile
-  // column per column group (cg_n0[xg_n] = tile columns), and the row-group heights as
-  // FastDivs: the decode is compares and high multiplies, no loop, no division
-  int rg_m0[9], cg_n0[9];
-  FastDiv fd_rows[8];
-  FastDiv fd_split;      // / splits
-  FastDiv fd_ohw, fd_ow;  // conv: output row m -> image, then row / column
-  FastDiv fd_tiles;       // grouped launches: / tiles
-  FastDiv fd_period, fd_hwp;  // halo kinds: / h_period, / h_hwp
-  int imgs;                   // conv: images (M / (OH * OW))
-  // halo conv (kConvHalo): tile row block tm is the band of h_th "virtual" output
-  // rows u in [tm * h_th, (tm + 1) * h_th) x the full width.  Virtual rows stack the
-  // images with a period of h_period rows: image u / h_period, output row
-  // u % h_period - h_off (valid when in [0, OH)).  Aligned bands (h_off 0,
-  // h_period = bands per image x h_th) stay inside one image; stacked bands
-  // (h_off 1, h_period = OH + 2: a zero row above and below every image) may span
-  // several images, so one tile can cover whole small maps of several images and
-  // the weights are re-read by fewer tiles.  The band's input rows (+1 pixel of
-  // padding around) form an h_hwp-wide halo image of h_hp pixels; h_nblk channel
-  // blocks, h_bps of them per split-K slice
-  int h_th, h_period, h_off, h_hwp, h_hp, h_nblk, h_bps;
-  int win_nblk_shift;  // window kind (kConvTapW): log2 of the channel blocks per tap
-  int splits;  // split-K slices (the grid holds tiles x splits workgroups of this problem)
-#ifdef SPI_GEMM_TIMELINE
-  int tl;  // stamp this launch (tools/gemm_timeline.py)
-#endif
-};
-
-// One launch, one or two independent problems of the same kernel instance (a
-// grouped launch: ResNet's downsample 1x1 conv beside its block's first conv,
-// both reading the block input).  Workgroups [0, wgs0) run a[0], the rest a[1].
-struct KGroup {
-  KArgs a[2];
-  int wgs0;
-};
 
 template <int MODE>
 struct Traits;
@@ -217,11 +76,10 @@ struct Traits<(int)Prec::F16X3> {  // A: 32 fp32; W: [32 hi | 32 lo] (RB = 256 m
   using Out = float;
   static constexpr int RB = 128, ESTEP = 32, EPC = 4;
 };
-// Kernel-internal mode: F16X3 whose A (and residual) are activations already
+// Kernel-internal mode kF16X3S (gemm_args.hpp): F16X3 whose A (and residual) are activations already
 // stored split, [32 hi fp16 | 32 lo fp16] per 32 channels (GemmDesc::a_split).
 // Byte-for-byte the same addressing as fp32 A (a 32-k block is 128 bytes either
 // way), so only the fragment reads differ: A is read exactly like W.
-constexpr int kF16X3S = 3;
 template <>
 struct Traits<kF16X3S> : Traits<(int)Prec::F16X3> {};
 
@@ -316,11 +174,10 @@ __device__ __forceinline__ u32x4 rd_chunk(const char* img, int row, int c) {
 // Separate instantiations keep each kind's loop free of the others.
 enum : int { kDense = 0, kConvTap = 1, kConvGen = 2, kConvHalo = 3, kConvHaloS = 4, kConvTapW = 5 };
 
-// Split-K is compiled into the 64x64 and 128x64 tiles and the halo kinds (no plan
-// rule splits 128x128; the reducer costs 36-120 VGPRs there).  Launch bounds ask
+// Split-K is compiled into the tiles split_k_compiled names (gemm_args.hpp).  Launch bounds ask
 // for the occupancy each tile reaches within its registers: 4 / 3 / 2 waves per SIMD.
 template <int BM, int BN, int KIND>
-constexpr bool kSplitK = (BM == 64 && BN == 64) || (BM == 128 && BN == 64) || KIND == kConvHalo || KIND == kConvHaloS;
+constexpr bool kSplitK = split_k_compiled(BM, BN, KIND == kConvHalo || KIND == kConvHaloS);
 
 // kConvHalo.  An implicit-GEMM conv stages each (tap, channel block) A tile
 // separately: every input pixel crosses the CU nine times, and the vector-memory
@@ -443,52 +300,10 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
   // wave index in an SGPR: every LDS-DMA destination (M0) is then scalar math.
   const int tid = KG == 1 ? (int)threadIdx.x : (int)threadIdx.x & (NT - 1), lane = tid & 63,
             wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // XCD-aware remap: consecutive tiles (same weight columns) land on one XCD's L2.
-  // hl: the workgroup's dispatch index inside this problem's range; the hardware deals
-  // dispatch indices round-robin to the 8 XCDs, so hl & 7 names the XCD.  Number each
-  // XCD's workgroups consecutively (bijective, chunks of q or q + 1).
-  int tile = lin, kslice = kslice_in;
-  const auto xcd_order = [](int idx, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, x = idx & 7, l = idx >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + l;
-  };
-  if (kSplitK<BM, BN, KIND> && a.splits > 1) {
-    // split-K: cut that order into tiles of `splits` consecutive slices
-    const int wgid = xcd_order(hl, a.tiles * a.splits);
-    tile = fdiv(wgid, a.fd_split);
-    kslice = wgid - tile * a.splits;
-  } else if (a.tiles >= 16) {
-    tile = xcd_order(tile, a.tiles);
-  }
-  // Tile of linear index `tile`: the tile grid is cut into xg_m x xg_n
-  // rectangles (row groups i-major), each walked with tm fastest; the chunk of
-  // consecutive indices an XCD receives is then (about) one rectangle, so each
-  // A row block is fetched by xg_n XCD L2s and each W column block by xg_m
-  // (xg_m = 1: every XCD reads all of A -- the plain column-major order).
-  int tm, tn;
-  {
-    const int TN = a.tiles_n;
-    int mlo = 0, mhi = a.rg_m0[1];
-    FastDiv fdm = a.fd_rows[0];
-#pragma unroll
-    for (int i = 1; i < 8; ++i)  // row group: the last whose first tile index is <= tile
-      if (i < a.xg_m && a.rg_m0[i] * TN <= tile) {
-        mlo = a.rg_m0[i];
-        mhi = a.rg_m0[i + 1];
-        fdm = a.fd_rows[i];
-      }
-    const int mi = mhi - mlo;
-    const int l2 = tile - mlo * TN;  // index inside row group i: mi x TN tiles
-    const int c = fdiv(l2, fdm);     // which tile column it falls in
-    int nlo = 0;
-#pragma unroll
-    for (int j = 1; j < 8; ++j)
-      if (j < a.xg_n && a.cg_n0[j] <= c) nlo = a.cg_n0[j];
-    const int loc = l2 - mi * nlo;
-    const int lq = fdiv(loc, fdm);
-    tm = mlo + (loc - lq * mi);
-    tn = nlo + lq;
-  }
+  // which tile and slice this workgroup owns: the XCD-aware decode of gemm_args.hpp
+  const TileAt at = decode_tile(a, kSplitK<BM, BN, KIND>, lin, kslice_in, hl);
+  [[maybe_unused]] const int tile = at.tile;
+  const int tm = at.tm, tn = at.tn, kslice = at.kslice;
   const int n0 = tn * BN;
   SPI_RT(rt_p1);
   // m_lim: first row past this tile's valid rows.  Halo tiles map their rows to
@@ -1681,13 +1496,13 @@ __global__ __launch_bounds__(64 * NW, (kMinWaves<BM, BN, STAGES, KIND, NW>)) voi
   // two loaded values -- SGPR spills to VGPR lanes and the tile decode's FastDiv tables copied to
   // scratch and read back with a dynamic offset (40 bytes of scratch per lane, round 6)
   const int lin = blockIdx.x;
-  if (lin >= g.wgs0) {
+  if (pair_problem(g, lin)) {
     const int l1 = lin - g.wgs0;
-    const int kslice = fdiv(l1, g.a[1].fd_tiles);
-    gemm_body<MODE, BM, BN, STAGES, KIND, NW>(g.a[1], kslice, l1 - kslice * g.a[1].tiles, l1);
+    const PairAt w = pair_slice(g.a[1], l1);
+    gemm_body<MODE, BM, BN, STAGES, KIND, NW>(g.a[1], w.kslice, w.lin, l1);
   } else {
-    const int kslice = fdiv(lin, g.a[0].fd_tiles);
-    gemm_body<MODE, BM, BN, STAGES, KIND, NW>(g.a[0], kslice, lin - kslice * g.a[0].tiles, lin);
+    const PairAt w = pair_slice(g.a[0], lin);
+    gemm_body<MODE, BM, BN, STAGES, KIND, NW>(g.a[0], w.kslice, w.lin, lin);
   }
 }
 
@@ -1698,76 +1513,39 @@ static_assert(kHaloHQ<64, kConvHaloS, 4> * 4 * 8 == kHaloPixelsSmall && kHaloHQ<
               kHaloHQ<128, kConvHalo, 4> * 4 * 8 == kHaloPixels128 && kHaloHQ<256, kConvHalo, 8> * 8 * 8 == kHaloPixels256,
               "gemm_plan.hpp: halo buffer capacities");
 
-constexpr Prec prec_of_mode(int mode) { return mode == kF16X3S ? Prec::F16X3 : (Prec)mode; }
-
-int ilog2(int v) {
-  int s = 0;
-  while ((1 << s) < v) ++s;
-  return s;
+// The instance table of the ring kinds: the plan's (BM, BN, STAGES) as integral constants.  One
+// problem (launch_tile) and a grouped pair (dispatch_pair) pick their kernel through it, so a
+// grouped launch and its two-launch fallback cannot disagree about the tiles that exist.
+template <int V>
+using IC = std::integral_constant<int, V>;
+template <class F>
+void with_tile(const Plan& pl, F&& f) {
+  if (pl.bm == 128 && pl.bn == 128) {
+    f(IC<128>{}, IC<128>{}, IC<2>{});
+  } else if (pl.bm == 128 && pl.stages == 2) {
+    f(IC<128>{}, IC<64>{}, IC<2>{});
+  } else if (pl.bm == 128) {
+    f(IC<128>{}, IC<64>{}, IC<3>{});
+  } else if (pl.stages == 2) {
+    f(IC<64>{}, IC<64>{}, IC<2>{});
+  } else if (pl.stages == 4) {
+    f(IC<64>{}, IC<64>{}, IC<4>{});
+  } else {
+    f(IC<64>{}, IC<64>{}, IC<3>{});
+  }
 }
 
-template <int MODE, int BM, int BN, int STAGES, int NW = 4>
+template <int MODE, int BM, int BN, int STAGES>
 void launch_tile(const KArgs& a, dim3 grid, hipStream_t s) {
   if (a.cell_uniform) {
-    SPI_LAUNCH((gemm_kernel<MODE, BM, BN, STAGES, kConvTap, NW>), grid, dim3(64 * NW), 0, s, a);
+    SPI_LAUNCH((gemm_kernel<MODE, BM, BN, STAGES, kConvTap>), grid, dim3(256), 0, s, a);
   } else if (a.d.conv) {
-    if constexpr (MODE != kF16X3S)  // split A needs one tap per step (checked in gemm())
-      SPI_LAUNCH((gemm_kernel<MODE, BM, BN, STAGES, kConvGen, NW>), grid, dim3(64 * NW), 0, s, a);
+    if constexpr (MODE != kF16X3S) {  // split A needs one tap per step (validate_gemm)
+      SPI_LAUNCH((gemm_kernel<MODE, BM, BN, STAGES, kConvGen>), grid, dim3(256), 0, s, a);
+    }
   } else {
-    SPI_LAUNCH((gemm_kernel<MODE, BM, BN, STAGES, kDense, NW>), grid, dim3(64 * NW), 0, s, a);
+    SPI_LAUNCH((gemm_kernel<MODE, BM, BN, STAGES, kDense>), grid, dim3(256), 0, s, a);
   }
-}
-
-// Kernel arguments of one problem under its plan.
-template <int MODE>
-KArgs make_args(const GemmDesc& d, const GemmPtrs& p, const Plan& pl) {
-  KArgs a{};
-  a.d = d;
-  a.p = p;
-  a.k_per_split = pl.k_per_split;
-  a.splits = pl.splits;
-  a.tiles = plan_tiles(d, pl);
-  a.tiles_m = a.tiles / ((d.N + pl.bn - 1) / pl.bn);
-#ifdef SPI_GEMM_TIMELINE
-  a.tl = tl_thread();
-#endif
-  const int TM = a.tiles_m, TN = a.tiles / a.tiles_m;
-  a.tiles_n = TN;
-  xcd_groups(d, MODE == kF16X3S ? Prec::F16X3 : (Prec)MODE, TM, TN, a.xg_m, a.xg_n);
-  if (pl.splits > 1) {  // split-K grids: the plain column-major order
-    a.xg_m = 1;
-    a.xg_n = std::min(8, TN);
-  }
-  for (int i = 0; i <= 8; ++i) {
-    a.rg_m0[i] = std::min(i, a.xg_m) * TM / a.xg_m;
-    a.cg_n0[i] = std::min(i, a.xg_n) * TN / a.xg_n;
-  }
-  for (int i = 0; i < 8; ++i) a.fd_rows[i] = make_fastdiv((unsigned)std::max(1, a.rg_m0[i + 1] - a.rg_m0[i]));
-  a.fd_split = make_fastdiv((unsigned)std::max(1, pl.splits));
-  a.fd_tiles = make_fastdiv((unsigned)std::max(1, a.tiles));
-  if (d.conv) {
-    a.fd_ohw = make_fastdiv((unsigned)(d.OH * d.OW));
-    a.fd_ow = make_fastdiv((unsigned)d.OW);
-    a.imgs = d.M / (d.OH * d.OW);
-  }
-  a.cin_shift = d.conv ? ilog2(d.Cin) : 0;
-  a.kw_mul = (65536 + d.KW - 1) / d.KW;
-  a.cell_uniform = cell_uniform(d, prec_of_mode(MODE));
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  a.vec_ok = d.ldc % 8 == 0 && al16(p.C) && (!p.res || (d.ldr % 8 == 0 && al16(p.res))) && (!p.bias || al16(p.bias));
-  if (pl.halo) {
-    a.h_th = pl.th;
-    a.h_period = pl.period;
-    a.h_off = pl.off;
-    a.h_hwp = d.W + 2 * d.pad;
-    a.h_hp = (pl.th + 2) * a.h_hwp;
-    a.h_nblk = d.Cin / Traits<MODE>::ESTEP;
-    a.h_bps = pl.bps;
-    a.fd_period = make_fastdiv((unsigned)std::max(1, pl.period));
-    a.fd_hwp = make_fastdiv((unsigned)a.h_hwp);
-  }
-  if (pl.win) a.win_nblk_shift = ilog2(d.Cin / Traits<MODE>::ESTEP);
-  return a;
 }
 
 // One problem under its plan: grid tiles x splits.
@@ -1776,14 +1554,15 @@ void dispatch(const Plan& pl, const KArgs& g, hipStream_t s) {
   const dim3 grid(g.tiles, pl.splits);
   if (pl.halo) {
     if constexpr (MODE != (int)Prec::F16X3) {  // fp32 A is split at fragment read: not a halo mode
-      if (pl.bm == 256)
+      if (pl.bm == 256) {
         SPI_LAUNCH((gemm_kernel<MODE, 256, 64, 3, kConvHalo, 8>), grid, dim3(512), 0, s, g);
-      else if (pl.bm == 128)
+      } else if (pl.bm == 128) {
         SPI_LAUNCH((gemm_kernel<MODE, 128, 64, 3, kConvHalo>), grid, dim3(256), 0, s, g);
-      else if (pl.halo == 2)
+      } else if (pl.halo == 2) {
         SPI_LAUNCH((gemm_kernel<MODE, 64, 64, 3, kConvHaloS>), grid, dim3(256), 0, s, g);
-      else
+      } else {
         SPI_LAUNCH((gemm_kernel<MODE, 64, 64, 3, kConvHalo>), grid, dim3(256), 0, s, g);
+      }
     }
     return;
   }
@@ -1795,52 +1574,43 @@ void dispatch(const Plan& pl, const KArgs& g, hipStream_t s) {
         if (pl.bm != 64 || pl.k_per_split % (6 * ES) || g.d.Kpad % (6 * ES))
           throw std::logic_error("window kind with K groups: slices of an even number of super-steps");
         SPI_LAUNCH((gemm_kernel<MODE, 64, 64, 3, kConvTapW, 8>), grid, dim3(512), 0, s, g);
-      } else if (pl.bm == 128)
+      } else if (pl.bm == 128) {
         SPI_LAUNCH((gemm_kernel<MODE, 128, 64, 3, kConvTapW>), grid, dim3(256), 0, s, g);
-      else
+      } else {
         SPI_LAUNCH((gemm_kernel<MODE, 64, 64, 3, kConvTapW>), grid, dim3(256), 0, s, g);
+      }
     }
     return;
   }
-  if (pl.bm == 128 && pl.bn == 128)
-    launch_tile<MODE, 128, 128, 2>(g, grid, s);
-  else if (pl.bm == 128 && pl.stages == 2)
-    launch_tile<MODE, 128, 64, 2>(g, grid, s);
-  else if (pl.bm == 128)
-    launch_tile<MODE, 128, 64, 3>(g, grid, s);
-  else if (pl.stages == 2)
-    launch_tile<MODE, 64, 64, 2>(g, grid, s);
-  else if (pl.stages == 4)
-    launch_tile<MODE, 64, 64, 4>(g, grid, s);
-  else
-    launch_tile<MODE, 64, 64, 3>(g, grid, s);
+  with_tile(pl, [&](auto bm, auto bn, auto st) {
+    launch_tile<MODE, decltype(bm)::value, decltype(bn)::value, decltype(st)::value>(g, grid, s);
+  });
 }
 
 // Two tap-walk conv problems sharing pl's tile shape and ring depth: one launch.
 template <int MODE>
 void dispatch_pair(const Plan& pl, const KGroup& g, int wgs, hipStream_t s) {
   const dim3 grid(wgs);
-  if (pl.bm == 128 && pl.bn == 128)
-    SPI_LAUNCH((gemm_kernel_pair<MODE, 128, 128, 2, kConvTap>), grid, dim3(256), 0, s, g);
-  else if (pl.bm == 128 && pl.stages == 2)
-    SPI_LAUNCH((gemm_kernel_pair<MODE, 128, 64, 2, kConvTap>), grid, dim3(256), 0, s, g);
-  else if (pl.bm == 128)
-    SPI_LAUNCH((gemm_kernel_pair<MODE, 128, 64, 3, kConvTap>), grid, dim3(256), 0, s, g);
-  else if (pl.stages == 2)
-    SPI_LAUNCH((gemm_kernel_pair<MODE, 64, 64, 2, kConvTap>), grid, dim3(256), 0, s, g);
-  else if (pl.stages == 4)
-    SPI_LAUNCH((gemm_kernel_pair<MODE, 64, 64, 4, kConvTap>), grid, dim3(256), 0, s, g);
-  else
-    SPI_LAUNCH((gemm_kernel_pair<MODE, 64, 64, 3, kConvTap>), grid, dim3(256), 0, s, g);
+  with_tile(pl, [&](auto bm, auto bn, auto st) {
+    SPI_LAUNCH((gemm_kernel_pair<MODE, decltype(bm)::value, decltype(bn)::value, decltype(st)::value, kConvTap>), grid,
+               dim3(256), 0, s, g);
+  });
+}
+
+// make_args' arguments as launched: a timeline build marks the launches of a stamping thread
+KArgs stamped(KArgs a) {
+#ifdef SPI_GEMM_TIMELINE
+  a.tl = tl_thread();
+#endif
+  return a;
 }
 
 template <int MODE>
 void launch(const GemmDesc& d, const GemmPtrs& p, const Plan& pl, hipStream_t s) {
-  dispatch<MODE>(pl, make_args<MODE>(d, p, pl), s);
+  dispatch<MODE>(pl, stamped(make_args(MODE, d, p, pl)), s);
 }
 
-// Two problems in one launch when plan_pair groups them, else one launch each; problem 1's
-// split-K slabs and tickets follow problem 0's in the workspace.
+// Two problems in one launch when plan_pair groups them, else one launch each.
 template <int MODE>
 void launch_pair(const GemmDesc& d0, const GemmPtrs& p0, const GemmDesc& d1, const GemmPtrs& p1, hipStream_t s) {
   const PairPlan pp = plan_pair(d0, d1, prec_of_mode(MODE));
@@ -1849,124 +1619,51 @@ void launch_pair(const GemmDesc& d0, const GemmPtrs& p0, const GemmDesc& d1, con
     launch<MODE>(d1, p1, pp.q1, s);
     return;
   }
-  KGroup g{};
-  g.a[0] = make_args<MODE>(d0, p0, pp.q0);
-  GemmPtrs p1s = p1;
-  if (pp.q0.splits > 1) {  // keep clear of problem 0's slabs / tickets
-    p1s.partial = p0.partial + pp.slab_off;
-    p1s.counters = p0.counters + pp.ticket_off;
-  }
-  g.a[1] = make_args<MODE>(d1, p1s, pp.q1);
-  g.wgs0 = pp.wgs0;
+  KGroup g = make_group(MODE, d0, p0, d1, p1, pp);
+  g.a[0] = stamped(g.a[0]);
+  g.a[1] = stamped(g.a[1]);
   dispatch_pair<MODE>(pp.q0, g, pp.wgs, s);
 }
 
-}  // namespace
+// The kernel mode of a launch as an integral constant.
+template <class F>
+void with_mode(int mode, F&& f) {
+  switch (mode) {
+    case (int)Prec::F32: return f(IC<(int)Prec::F32>{});
+    case (int)Prec::F16: return f(IC<(int)Prec::F16>{});
+    case (int)Prec::F16X3: return f(IC<(int)Prec::F16X3>{});
+    case kF16X3S: return f(IC<kF16X3S>{});  // split A: one (kh, kw) cell per 32-k step, fp32's addressing
+  }
+}
 
-#ifdef SPI_GEMM_STAMPS
-extern "C" int spi_debug_gemm_stamps(unsigned long long* host, size_t n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_stamps), n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-#endif
-#ifdef SPI_GEMM_TIMELINE
-extern "C" int spi_debug_gemm_timeline(unsigned long long* host, size_t n) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_timeline), n * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
-}
-extern "C" void spi_debug_gemm_timeline_enable(int on, hipStream_t) { tl_thread() = on; }
-extern "C" int spi_debug_gemm_timeline_clear(void) {
-  static unsigned long long zeros[65536 * 8];
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_timeline), zeros, sizeof(zeros)) == hipSuccess ? 0 : 1;
-}
-#endif
-
-namespace {
-void check_desc(const GemmDesc& d, Prec prec) {
-  if (d.pool_rows && (d.conv || d.pool_rows > 64 || d.M % d.pool_rows))
-    throw std::invalid_argument("pooled GEMM: dense A, pool_rows <= 64 dividing M");
-  if (d.krep != 1 && (d.krep != 2 || prec != Prec::F16 || d.Kpad % (2 * estep_of(prec)) ||
-                      (d.conv && (d.Cin < estep_of(prec) || d.KH * d.KW > 31))))
-    throw std::invalid_argument("krep = 2 needs F16, a packed Kpad of whole step pairs and dense or one-tap-per-step A");
-  if (prec == Prec::F16X3 && d.a_split && d.conv && (d.Cin < 32 || d.KH * d.KW > 31))
-    throw std::invalid_argument("split activations need Cin >= 32 and <= 31 filter taps");
-}
 }  // namespace
 
 void gemm_pair(const GemmDesc& d0, const GemmPtrs& p0, const GemmDesc& d1, const GemmPtrs& p1, Prec prec,
                hipStream_t s) {
-  check_desc(d0, prec);
-  check_desc(d1, prec);
+  validate_gemm(d0, p0, prec);
+  validate_gemm(d1, p1, prec);
   if (prec == Prec::F16X3 && d0.a_split != d1.a_split) {
     gemm(d0, p0, prec, s);
     gemm(d1, p1, prec, s);
     return;
   }
-  switch (prec) {
-    case Prec::F16:
-      launch_pair<(int)Prec::F16>(d0, p0, d1, p1, s);
-      break;
-    case Prec::F32:
-      launch_pair<(int)Prec::F32>(d0, p0, d1, p1, s);
-      break;
-    case Prec::F16X3:
-      if (d0.a_split)
-        launch_pair<kF16X3S>(d0, p0, d1, p1, s);
-      else
-        launch_pair<(int)Prec::F16X3>(d0, p0, d1, p1, s);
-      break;
-  }
+  with_mode(mode_of(prec, d0.a_split), [&](auto m) { launch_pair<decltype(m)::value>(d0, p0, d1, p1, s); });
 }
 
 void gemm(const GemmDesc& d, const GemmPtrs& p, Prec prec, hipStream_t s) {
-  check_desc(d, prec);
-  if (d.ln_in_chunks > 0 || d.res_ln_chunks > 0 || d.ln_out) {
-    // the fold lives in the dense fp16 kernels' vector epilogue: whole 128-column tiles,
-    // 16-byte aligned rows everywhere it reads or writes
-    const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool ok = prec == Prec::F16 && !d.conv && !d.pool_rows && d.N % 128 == 0 &&
-                    d.ldc % 8 == 0 && al16(p.C) && (!p.bias || al16(p.bias)) &&
-                    (!p.res || (d.ldr % 8 == 0 && al16(p.res))) &&
-                    (d.ln_in_chunks == 0 || (p.ln.in_stats && p.ln.c1 && al16(p.ln.c1))) &&
-                    (d.res_ln_chunks == 0 ||
-                     (p.res && (d.res_f32 || d.res_planes) && p.ln.res_stats && al16(p.ln.res_g) && al16(p.ln.res_b))) &&
-                    (!d.ln_out || (p.ln.out_stats && (p.ln.c16 ? al16(p.ln.c16) && d.ld16 % 8 == 0 : d.out_planes)));
-    if (!ok) throw std::invalid_argument("LayerNorm fold: dense fp16 GEMM, N % 128 == 0, aligned vectors");
-  }
-  if (d.res_planes || d.out_planes) {
-    // two fp16 planes: the F16 dense epilogue, 16-byte aligned rows and plane offset
-    if (prec != Prec::F16 || d.conv || d.pool_rows || d.plane % 8 || (d.res_planes && (!p.res || d.res_f32)) ||
-        (d.out_planes && (d.out_f32 || d.out_f16)))
-      throw std::invalid_argument("two-plane residual / output: dense fp16 GEMM, plane offset a multiple of 8");
-    // a two-plane output keeps an fp16-typed residual in two planes too (Model::run_gemm's rule; an
-    // fp32 residual -- the stream's first block -- is the one other kind)
-    if (d.out_planes && p.res && !d.res_f32 && !d.res_planes)
-      throw std::invalid_argument("two-plane output: the residual is fp32 or two planes");
-  }
+  validate_gemm(d, p, prec);
   const GemmPlan g = plan_gemm(d, prec);
   // gemm256's producer epilogue exists over an fp32 residual into fp32 and over two planes in place
   // of form (the transformers' out-proj / FFN2); any other producer keeps the general kernel, as the
   // plan cannot tell: it does not see the residual pointer
   const bool g256_producer_ok = !d.ln_out || (p.res && ((d.res_f32 && d.out_f32) || (d.res_planes && d.out_planes)));
-  switch (prec) {
-    case Prec::F16:
-      if (conv_wres_eligible(d, prec, p))
-        conv_wres(d, p, s);
-      else if (g.g256_bm && g256_producer_ok && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(p.W) & 15) == 0)  // 16-byte LDS-DMA pieces
-        gemm256(d, p, g.g256_splits, s, g.g256_bm, g.g256_nbuf, g.g256_order);
-      else
-        launch<(int)Prec::F16>(d, p, g.pl, s);
-      break;
-    case Prec::F32:
-      launch<(int)Prec::F32>(d, p, g.pl, s);
-      break;
-    case Prec::F16X3:
-      // split A relies on one (kh, kw) cell per 32-k step (byte-identical to fp32 addressing)
-      if (d.a_split)
-        launch<kF16X3S>(d, p, g.pl, s);
-      else
-        launch<(int)Prec::F16X3>(d, p, g.pl, s);
-      break;
-  }
+  if (prec == Prec::F16 && conv_wres_eligible(d, prec, p))
+    conv_wres(d, p, s);
+  else if (prec == Prec::F16 && g.g256_bm && g256_producer_ok && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 &&
+           (reinterpret_cast<uintptr_t>(p.W) & 15) == 0)  // 16-byte LDS-DMA pieces
+    gemm256(d, p, g.g256_splits, s, g.g256_bm, g.g256_nbuf, g.g256_order);
+  else
+    with_mode(mode_of(prec, d.a_split), [&](auto m) { launch<decltype(m)::value>(d, p, g.pl, s); });
 }
 
 }  // namespace spi

@@ -1,5 +1,6 @@
-// The GEMM / conv-as-implicit-GEMM problem descriptor: plain data, no HIP types, so the
-// host-only planner (gemm_plan.hpp) and the kernels (spi_kernels.hpp) share it.
+// The GEMM / conv-as-implicit-GEMM problem descriptor, its one conv and one dense builder, and the
+// pointers of a launch: plain data, no HIP types, so the host-only planner (gemm_plan.hpp), the
+// host-only argument builder (gemm_args.hpp) and the kernels (spi_kernels.hpp) share them.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -78,6 +79,64 @@ struct GemmDesc {
   bool res_planes = false;
   bool out_planes = false;
   size_t plane = 0;
+};
+
+
+// The desc of a conv over B NHWC images of H x W x Cin (Cin as packed: the padded channel count)
+// and of a dense [M, K] x [N, K]^T problem.  They compute the output size, M, K, the packed W row
+// length (krep = 2: hi + lo weights, twice as long) and the output strides; the caller sets what is
+// its own: activation, operand formats, w_image, the fold fields.
+inline GemmDesc conv_desc(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int krep) {
+  GemmDesc d;
+  d.conv = true;
+  d.H = H, d.W = W, d.Cin = Cin;
+  d.KH = KH, d.KW = KW;
+  d.stride = stride;
+  d.pad = pad;
+  d.OH = (H + 2 * pad - KH) / stride + 1;
+  d.OW = (W + 2 * pad - KW) / stride + 1;
+  d.M = B * d.OH * d.OW;
+  d.N = Cout;
+  d.K = KH * KW * Cin;
+  d.krep = krep;
+  d.Kpad = (d.K + 63) / 64 * 64 * krep;
+  d.ldc = d.ldr = Cout;
+  return d;
+}
+inline GemmDesc dense_desc(int M, int N, int K, int lda, int ldc, int ldr, int krep) {
+  GemmDesc d;
+  d.M = M;
+  d.N = N;
+  d.K = K;
+  d.krep = krep;
+  d.Kpad = (K + 63) / 64 * 64 * krep;
+  d.lda = lda;
+  d.ldc = ldc;
+  d.ldr = ldr;
+  return d;
+}
+
+// Pointers of the LayerNorm fold (GemmDesc::ln_in_chunks / res_ln_chunks / ln_out).
+struct LnPtrs {
+  const float* in_stats = nullptr;   // A rows' chunk statistics
+  const float* c1 = nullptr;         // [N] per-column sum of the folded weights
+  const float* res_stats = nullptr;  // residual rows' chunk statistics
+  const float* res_g = nullptr;      // residual LayerNorm gain / bias
+  const float* res_b = nullptr;
+  float* out_stats = nullptr;        // output rows' chunk statistics
+  _Float16* c16 = nullptr;           // fp16 copy of the output (none with GemmDesc::out_planes)
+};
+
+struct GemmPtrs {
+  const void* A = nullptr;
+  const void* W = nullptr;
+  const float* bias = nullptr;
+  const void* res = nullptr;
+  void* C = nullptr;
+  float* partial = nullptr;  // split-K slabs (gemm_partial_floats)
+  int* counters = nullptr;   // split-K arrival tickets, zero-initialised (gemm_counter_slots)
+  const void* zeros = nullptr;  // >= 256 zero bytes (padded / out-of-range chunks; conv_wres: a null bias)
+  LnPtrs ln;
 };
 
 }  // namespace spi

@@ -474,58 +474,16 @@ extern "C" void spi_debug_gemm_reload_env(void) {
   qkv_attn_reload_env();
 }
 
-namespace {
-GemmDesc debug_conv_desc(int precision, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
-  GemmDesc d;
-  d.conv = true;
-  d.H = H;
-  d.W = W;
-  d.Cin = Cin;
-  d.KH = KH;
-  d.KW = KW;
-  d.stride = stride;
-  d.pad = pad;
-  d.OH = (H + 2 * pad - KH) / stride + 1;
-  d.OW = (W + 2 * pad - KW) / stride + 1;
-  d.M = B * d.OH * d.OW;
-  d.N = Cout;
-  d.K = KH * KW * Cin;
-  d.Kpad = (d.K + 63) / 64 * 64;
+Prec case_prec(int precision) { return precision == 0 ? Prec::F32 : precision == 1 ? Prec::F16 : Prec::F16X3; }
+
+GemmDesc case_conv_desc(int precision, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad) {
+  GemmDesc d = conv_desc(B, H, W, Cin, Cout, KH, KW, stride, pad, 1);
   d.a_split = d.out_split = precision == 3;
   return d;
 }
-Prec debug_prec(int precision) { return precision == 0 ? Prec::F32 : precision == 1 ? Prec::F16 : Prec::F16X3; }
-template <class T>
-void put_plan(const Plan& pl, T* out) {
-  const int v[8] = {pl.bm, pl.bn, pl.stages, pl.splits, pl.halo, pl.win, pl.nw, pl.k_per_split};
-  for (int i = 0; i < 8; ++i) out[i] = v[i];
-}
-}  // namespace
 
-// The plan gemm() would pick for a conv (tests: which kind runs): out[0..7] = bm, bn, stages,
-// splits, halo kind, window kind, waves, k per slice.  precision as spi_ops.h (3 = split).
-extern "C" int spi_debug_conv_plan(int precision, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
-                                   int pad, int* out) {
-  if (!out || precision < 0 || precision > 3) return 1;
-  put_plan(choose_plan(debug_conv_desc(precision, B, H, W, Cin, Cout, KH, KW, stride, pad), debug_prec(precision)), out);
-  return 0;
-}
-
-// The whole plan of a dense problem.  flags: bit 0 an activation, 1 res_f32, 2 res_planes, 3 out_planes,
-// 4 out_f16, 5 out_f32, bits 8..15 ln_in_chunks, 16..23 res_ln_chunks.  out[0..3] = gemm256 tile height
-// (0: the general kernel), slices, k-tile buffers, tile order; out[4..11] = the general kernel's plan as
-// spi_debug_conv_plan; out[12], out[13] = split-K workspace floats, ticket slots.
-extern "C" int spi_debug_gemm_plan(int precision, int M, int N, int K, int lda, int krep, int pool_rows, unsigned flags,
-                                   long long* out) {
-  if (!out || precision < 0 || precision > 3 || M < 1 || N < 1 || K < 1 || krep < 1 || krep > 2) return 1;
-  GemmDesc d;
-  d.M = M;
-  d.N = N;
-  d.K = K;
-  d.Kpad = (K + 63) / 64 * 64 * krep;
-  d.lda = lda;
-  d.ldc = d.ldr = N;
-  d.krep = krep;
+GemmDesc case_dense_desc(int precision, int M, int N, int K, int lda, int krep, int pool_rows, unsigned flags) {
+  GemmDesc d = dense_desc(M, N, K, lda, N, N, krep);
   d.pool_rows = pool_rows;
   d.act = flags & 1 ? Act::Gelu : Act::None;
   d.res_f32 = flags >> 1 & 1;
@@ -536,7 +494,27 @@ extern "C" int spi_debug_gemm_plan(int precision, int M, int N, int K, int lda, 
   d.ln_in_chunks = flags >> 8 & 255;
   d.res_ln_chunks = flags >> 16 & 255;
   d.a_split = d.out_split = precision == 3;
-  const GemmPlan g = plan_gemm(d, debug_prec(precision));
+  return d;
+}
+
+// The plan gemm() would pick for a conv (tests: which kind runs): out[0..7] = bm, bn, stages,
+// splits, halo kind, window kind, waves, k per slice.  precision as spi_ops.h (3 = split).
+extern "C" int spi_debug_conv_plan(int precision, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                                   int pad, int* out) {
+  if (!out || precision < 0 || precision > 3) return 1;
+  put_plan(choose_plan(case_conv_desc(precision, B, H, W, Cin, Cout, KH, KW, stride, pad), case_prec(precision)), out);
+  return 0;
+}
+
+// The whole plan of a dense problem.  flags: bit 0 an activation, 1 res_f32, 2 res_planes, 3 out_planes,
+// 4 out_f16, 5 out_f32, bits 8..15 ln_in_chunks, 16..23 res_ln_chunks (gemm_plan.hpp).  out[0..3] = gemm256 tile height
+// (0: the general kernel), slices, k-tile buffers, tile order; out[4..11] = the general kernel's plan as
+// spi_debug_conv_plan; out[12], out[13] = split-K workspace floats, ticket slots.
+extern "C" int spi_debug_gemm_plan(int precision, int M, int N, int K, int lda, int krep, int pool_rows, unsigned flags,
+                                   long long* out) {
+  if (!out || precision < 0 || precision > 3 || M < 1 || N < 1 || K < 1 || krep < 1 || krep > 2) return 1;
+  const GemmDesc d = case_dense_desc(precision, M, N, K, lda, krep, pool_rows, flags);
+  const GemmPlan g = plan_gemm(d, case_prec(precision));
   out[0] = g.g256_bm;
   out[1] = g.g256_splits;
   out[2] = g.g256_nbuf;
@@ -554,9 +532,9 @@ extern "C" int spi_debug_conv_pair_plan(int precision, int B, int H, int W, int 
                                         int stride0, int pad0, int Cout1, int KH1, int KW1, int stride1, int pad1,
                                         long long* out) {
   if (!out || precision < 0 || precision > 3) return 1;
-  const GemmDesc d0 = debug_conv_desc(precision, B, H, W, Cin, Cout0, KH0, KW0, stride0, pad0);
-  const GemmDesc d1 = debug_conv_desc(precision, B, H, W, Cin, Cout1, KH1, KW1, stride1, pad1);
-  const Prec prec = debug_prec(precision);
+  const GemmDesc d0 = case_conv_desc(precision, B, H, W, Cin, Cout0, KH0, KW0, stride0, pad0);
+  const GemmDesc d1 = case_conv_desc(precision, B, H, W, Cin, Cout1, KH1, KW1, stride1, pad1);
+  const Prec prec = case_prec(precision);
   const PairPlan pp = plan_pair(d0, d1, prec);
   put_plan(pp.q0, out);
   put_plan(pp.q1, out + 8);

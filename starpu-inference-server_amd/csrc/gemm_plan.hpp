@@ -77,4 +77,19 @@ bool gemm_workspace_fits(const GemmDesc& d, Prec prec, size_t floats, size_t slo
 // k-values per staged step (W rows must be padded to a multiple of it).
 int gemm_kstep(Prec prec);
 
+// A plan as the 8 integers the debug exports and spi_op_conv_pair report: bm, bn, stages, splits,
+// halo kind, window kind, waves, k per slice.
+template <class T>
+void put_plan(const Plan& pl, T* out) {
+  const int v[8] = {pl.bm, pl.bn, pl.stages, pl.splits, pl.halo, pl.win, pl.nw, pl.k_per_split};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+}
+
+// The problems the debug exports (gemm_plan.cpp, gemm_args.cpp) are asked about.  precision as
+// spi_ops.h (3 = split activations); flags: bit 0 an activation, 1 res_f32, 2 res_planes,
+// 3 out_planes, 4 out_f16, 5 out_f32, bits 8..15 ln_in_chunks, 16..23 res_ln_chunks.
+Prec case_prec(int precision);
+GemmDesc case_conv_desc(int precision, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+GemmDesc case_dense_desc(int precision, int M, int N, int K, int lda, int krep, int pool_rows, unsigned flags);
+
 }  // namespace spi

@@ -191,35 +191,19 @@ double Model::flops(int64_t B) const {
 // Launch helpers
 // ---------------------------------------------------------------------------
 namespace {
+// A layer's desc: the shared builders (gemm_desc.hpp) on the packed layer's sizes.  The packer
+// (model_pack.cpp) sized the W rows; a row length the builder does not arrive at is a packing bug.
 GemmDesc conv_desc(const ConvW& c, int B, int H, int W, int& OH, int& OW) {
-  OH = (H + 2 * c.pad - c.kh) / c.stride + 1;
-  OW = (W + 2 * c.pad - c.kw) / c.stride + 1;
-  GemmDesc d;
-  d.M = B * OH * OW;
-  d.N = c.cout;
-  d.K = c.kh * c.kw * c.cin_pad;
-  d.Kpad = c.kpad;
-  d.ldc = d.ldr = c.cout;
-  d.conv = true;
-  d.H = H, d.W = W, d.OH = OH, d.OW = OW;
-  d.Cin = c.cin_pad;
-  d.KH = c.kh, d.KW = c.kw;
-  d.stride = c.stride;
-  d.pad = c.pad;
-  d.krep = c.krep;
+  GemmDesc d = spi::conv_desc(B, H, W, c.cin_pad, c.cout, c.kh, c.kw, c.stride, c.pad, c.krep);
+  if (d.Kpad != c.kpad) throw std::logic_error("conv_desc: the packed weight rows are not Kpad long");
+  OH = d.OH, OW = d.OW;
   d.w_image = c.w_image;
   return d;
 }
 
 GemmDesc linear_desc(const LinearW& L, int M, int lda, int ldc) {
-  GemmDesc d;
-  d.M = M;
-  d.N = L.n;
-  d.K = L.k;
-  d.Kpad = L.kpad;
-  d.lda = lda;
-  d.ldc = d.ldr = ldc;
-  d.krep = L.krep;
+  const GemmDesc d = dense_desc(M, L.n, L.k, lda, ldc, ldc, L.krep);
+  if (d.Kpad != L.kpad) throw std::logic_error("linear_desc: the packed weight rows are not Kpad long");
   return d;
 }
 

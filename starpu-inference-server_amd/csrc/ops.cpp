@@ -62,6 +62,24 @@ spi::GemmPtrs scratch(void* ws) {
   return p;
 }
 
+// The tail of every single-GEMM entry point: the workspace must hold the problem (too_large: the
+// message when it does not; null: a kind that is never split), then launch on the workspace's scratch.
+int run_gemm(const spi::GemmDesc& d, spi::Prec p, const void* A, const void* W, const float* bias, const void* res,
+             void* C, const spi::LnPtrs& ln, void* workspace, void* stream, const char* too_large) {
+  if (too_large && !spi::gemm_workspace_fits(d, p, kSlabFloats, kTickets)) return fail(too_large);
+  spi::GemmPtrs ptrs = scratch(workspace);
+  ptrs.A = A;
+  ptrs.W = W;
+  ptrs.bias = bias;
+  ptrs.res = res;
+  ptrs.C = C;
+  ptrs.ln = ln;
+  return guarded([&] {
+    spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -93,14 +111,7 @@ int spi_op_gemm(int32_t precision, const void* A, int32_t M, int32_t K, int32_t 
   if (!prec_of(precision, &p) || !A || !W || !C || !workspace || M <= 0 || N <= 0 || K <= 0 || lda < K ||
       ldc < N || act < 0 || act > 2)
     return fail("invalid gemm arguments");
-  spi::GemmDesc d;
-  d.M = M;
-  d.N = N;
-  d.K = K;
-  d.Kpad = spi::round_up_to(K, 64);
-  d.lda = lda;
-  d.ldc = ldc;
-  d.ldr = ldr;
+  spi::GemmDesc d = spi::dense_desc(M, N, K, lda, ldc, ldr, 1);
   d.act = static_cast<spi::Act>(act);
   d.out_f32 = out_f32 != 0;
   d.res_f32 = res_f32 != 0;
@@ -109,57 +120,28 @@ int spi_op_gemm(int32_t precision, const void* A, int32_t M, int32_t K, int32_t 
       return fail("split gemm needs K, N and strides multiples of 32, no fp32 operands");
     d.a_split = d.out_split = true;
   }
-  if (!spi::gemm_workspace_fits(d, p, kSlabFloats, kTickets))
-    return fail("gemm too large for the op workspace");
-  spi::GemmPtrs ptrs = scratch(workspace);
-  ptrs.A = A;
-  ptrs.W = W;
-  ptrs.bias = bias;
-  ptrs.res = residual;
-  ptrs.C = C;
-  return guarded([&] {
-    spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
-    return check_launch();
-  });
+  return run_gemm(d, p, A, W, bias, residual, C, {}, workspace, stream, "gemm too large for the op workspace");
 }
 
 namespace {
 
 // The descriptor of one op-level conv, as Model::conv_call builds a layer's; hilo: hi + lo weights.
 // Returns an error message, or null.
-const char* conv_desc_of(int32_t precision, spi::Prec p, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+const char* op_conv_desc(int32_t precision, spi::Prec p, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                          int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t act, bool hilo, bool out_f32,
                          bool res_f32, spi::GemmDesc* out) {
   const int min_cin = precision == 1 ? 8 : 4;  // one 16-byte chunk: 8 fp16 or 4 fp32
   if (B <= 0 || H <= 0 || W <= 0 || Cin < min_cin || (Cin & (Cin - 1)) || Cout <= 0 || KH <= 0 || KW <= 0 ||
       stride <= 0 || pad < 0 || act < 0 || act > 2)
     return "invalid conv arguments";
-  spi::GemmDesc d;
-  d.conv = true;
-  d.H = H;
-  d.W = W;
-  d.Cin = Cin;
-  d.KH = KH;
-  d.KW = KW;
-  d.stride = stride;
-  d.pad = pad;
-  d.OH = (H + 2 * pad - KH) / stride + 1;
-  d.OW = (W + 2 * pad - KW) / stride + 1;
+  spi::GemmDesc d = spi::conv_desc(B, H, W, Cin, Cout, KH, KW, stride, pad, hilo ? 2 : 1);
   if (H + 2 * pad < KH || W + 2 * pad < KW || d.OH <= 0 || d.OW <= 0) return "empty conv output";
-  d.M = B * d.OH * d.OW;
-  d.N = Cout;
-  d.K = KH * KW * Cin;
-  d.Kpad = spi::round_up_to(d.K, 64);
-  d.ldc = Cout;
-  d.ldr = Cout;
   d.act = static_cast<spi::Act>(act);
   d.out_f32 = out_f32;
   d.res_f32 = res_f32;
   if (hilo) {
     if (precision != 1) return "hi + lo weights are an fp16 layout";
     if (Cin < 64 || KH * KW > 31) return "hi + lo conv needs Cin >= 64 and <= 31 filter taps";
-    d.krep = 2;
-    d.Kpad *= 2;
   } else {
     // W_packed comes from spi_op_pack_weight (spi_ops.h), which writes the image rows
     d.w_image = spi::packed_has_wres_image(p, Cout, d.K, spi::round_up_to(Cout, 128), d.Kpad);
@@ -182,20 +164,9 @@ int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_
   spi::Prec p;
   if (!prec_of(precision, &p) || !x || !Wp || !y || !workspace) return fail("invalid conv arguments");
   spi::GemmDesc d;
-  if (const char* e = conv_desc_of(precision, p, B, H, W, Cin, Cout, KH, KW, stride, pad, act, false, false, false, &d))
+  if (const char* e = op_conv_desc(precision, p, B, H, W, Cin, Cout, KH, KW, stride, pad, act, false, false, false, &d))
     return fail(e);
-  if (!spi::gemm_workspace_fits(d, p, kSlabFloats, kTickets))
-    return fail("conv too large for the op workspace");
-  spi::GemmPtrs ptrs = scratch(workspace);
-  ptrs.A = x;
-  ptrs.W = Wp;
-  ptrs.bias = bias;
-  ptrs.res = residual;
-  ptrs.C = y;
-  return guarded([&] {
-    spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
-    return check_launch();
-  });
+  return run_gemm(d, p, x, Wp, bias, residual, y, {}, workspace, stream, "conv too large for the op workspace");
 }
 
 // ---- hi + lo fp16 weights (GemmDesc::krep = 2) ----
@@ -225,30 +196,12 @@ int spi_op_gemm_hilo(const void* A, int32_t M, int32_t K, int32_t lda, const voi
   if (!A || !W || !C || !workspace || M <= 0 || N <= 0 || K <= 0 || lda < K || ldc < N || act < 0 || act > 2 ||
       (residual && ldr < N))
     return fail("invalid gemm_hilo arguments");
-  spi::GemmDesc d;
-  d.M = M;
-  d.N = N;
-  d.K = K;
-  d.Kpad = 2 * spi::round_up_to(K, 64);
-  d.krep = 2;
-  d.lda = lda;
-  d.ldc = ldc;
-  d.ldr = ldr;
+  spi::GemmDesc d = spi::dense_desc(M, N, K, lda, ldc, ldr, 2);
   d.act = static_cast<spi::Act>(act);
   d.out_f32 = out_f32 != 0;
   d.res_f32 = res_f32 != 0;
-  if (!spi::gemm_workspace_fits(d, spi::Prec::F16, kSlabFloats, kTickets))
-    return fail("gemm too large for the op workspace");
-  spi::GemmPtrs ptrs = scratch(workspace);
-  ptrs.A = A;
-  ptrs.W = W;
-  ptrs.bias = bias;
-  ptrs.res = residual;
-  ptrs.C = C;
-  return guarded([&] {
-    spi::gemm(d, ptrs, spi::Prec::F16, static_cast<hipStream_t>(stream));
-    return check_launch();
-  });
+  return run_gemm(d, spi::Prec::F16, A, W, bias, residual, C, {}, workspace, stream,
+                  "gemm too large for the op workspace");
 }
 
 int spi_op_conv2d_hilo(const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin, const void* Wp, int32_t Cout,
@@ -256,21 +209,11 @@ int spi_op_conv2d_hilo(const void* x, int32_t B, int32_t H, int32_t W, int32_t C
                        int32_t res_f32, void* y, int32_t out_f32, int32_t act, void* workspace, void* stream) {
   if (!x || !Wp || !y || !workspace) return fail("invalid conv arguments");
   spi::GemmDesc d;
-  if (const char* e = conv_desc_of(1, spi::Prec::F16, B, H, W, Cin, Cout, KH, KW, stride, pad, act, true,
+  if (const char* e = op_conv_desc(1, spi::Prec::F16, B, H, W, Cin, Cout, KH, KW, stride, pad, act, true,
                                    out_f32 != 0, res_f32 != 0, &d))
     return fail(e);
-  if (!spi::gemm_workspace_fits(d, spi::Prec::F16, kSlabFloats, kTickets))
-    return fail("conv too large for the op workspace");
-  spi::GemmPtrs ptrs = scratch(workspace);
-  ptrs.A = x;
-  ptrs.W = Wp;
-  ptrs.bias = bias;
-  ptrs.res = residual;
-  ptrs.C = y;
-  return guarded([&] {
-    spi::gemm(d, ptrs, spi::Prec::F16, static_cast<hipStream_t>(stream));
-    return check_launch();
-  });
+  return run_gemm(d, spi::Prec::F16, x, Wp, bias, residual, y, {}, workspace, stream,
+                  "conv too large for the op workspace");
 }
 
 int spi_op_conv_pair(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t Cin,
@@ -284,7 +227,7 @@ int spi_op_conv_pair(int32_t precision, const void* x, int32_t B, int32_t H, int
   spi::GemmPtrs ptrs[2];
   for (int i = 0; i < 2; ++i) {
     if (!c[i]->W_packed || !c[i]->y) return fail("conv_pair: a spec without weights or output");
-    if (const char* e = conv_desc_of(precision, p, B, H, W, Cin, c[i]->Cout, c[i]->KH, c[i]->KW, c[i]->stride,
+    if (const char* e = op_conv_desc(precision, p, B, H, W, Cin, c[i]->Cout, c[i]->KH, c[i]->KW, c[i]->stride,
                                      c[i]->pad, c[i]->act, c[i]->hilo != 0, c[i]->out_f32 != 0, false, &d[i]))
       return fail(e);
     ptrs[i] = scratch(workspace);
@@ -298,12 +241,8 @@ int spi_op_conv_pair(int32_t precision, const void* x, int32_t B, int32_t H, int
   return guarded([&] {
     if (plan_out) {
       const spi::PairPlan pp = spi::plan_pair(d[0], d[1], p);
-      const spi::Plan* q[2] = {&pp.q0, &pp.q1};
-      for (int i = 0; i < 2; ++i) {
-        const int v[8] = {q[i]->bm, q[i]->bn, q[i]->stages, q[i]->splits, q[i]->halo, q[i]->win, q[i]->nw,
-                          q[i]->k_per_split};
-        for (int j = 0; j < 8; ++j) plan_out[i * 8 + j] = v[j];
-      }
+      spi::put_plan(pp.q0, plan_out);
+      spi::put_plan(pp.q1, plan_out + 8);
       plan_out[16] = pp.grouped;
       plan_out[17] = pp.wgs;
       plan_out[18] = (int64_t)pp.slab_off;
@@ -323,27 +262,12 @@ int spi_op_avgpool_fc(int32_t precision, const void* x, int32_t B, int32_t HW, i
       N <= 0 || act < 0 || act > 2)
     return fail("invalid avgpool_fc arguments");
   if (precision == kSplitPrecision && C % 32) return fail("split avgpool_fc needs C a multiple of 32");
-  spi::GemmDesc d;
-  d.M = B * HW;
-  d.N = N;
-  d.K = C;
-  d.Kpad = spi::round_up_to(C, 64);
-  d.lda = C;
-  d.ldc = N;
-  d.ldr = N;
+  spi::GemmDesc d = spi::dense_desc(B * HW, N, C, C, N, N, 1);
   d.act = static_cast<spi::Act>(act);
   d.out_f32 = true;
   d.pool_rows = HW;
   d.a_split = precision == kSplitPrecision;
-  spi::GemmPtrs ptrs = scratch(workspace);
-  ptrs.A = x;
-  ptrs.W = W;
-  ptrs.bias = bias;
-  ptrs.C = y;
-  return guarded([&] {
-    spi::gemm(d, ptrs, p, static_cast<hipStream_t>(stream));
-    return check_launch();
-  });
+  return run_gemm(d, p, x, W, bias, nullptr, y, {}, workspace, stream, nullptr);
 }
 
 size_t spi_op_stem_pool_bytes(void) { return spi::stem_pool_bytes(); }
@@ -457,16 +381,8 @@ int gemm_ln(int krep, const void* A, int32_t M, int32_t K, int32_t lda, const vo
   const bool consumer = in_stats || c1, res_ln = res_stats || res_g || res_b, producer = out_stats || c16;
   if ((consumer && K % 64) || ((res_ln || producer) && N % 64))
     return fail("gemm_ln: the LayerNorm fold works on whole 64-column chunks");
-  spi::GemmDesc d;
-  d.M = M;
-  d.N = N;
-  d.K = K;
-  d.krep = krep;
-  d.Kpad = spi::round_up_to(K, 64) * krep;
+  spi::GemmDesc d = spi::dense_desc(M, N, K, lda, ldc, ldr, krep);
   d.wplane = (size_t)spi::round_up_to(N, 128) * d.Kpad;
-  d.lda = lda;
-  d.ldc = ldc;
-  d.ldr = ldr;
   d.act = static_cast<spi::Act>(act);
   d.out_f32 = out_kind == SPI_KIND_F32;
   d.res_f32 = res_kind == SPI_KIND_F32;
@@ -493,19 +409,8 @@ int gemm_ln(int krep, const void* A, int32_t M, int32_t K, int32_t lda, const vo
     lp.out_stats = out_stats;
     lp.c16 = static_cast<_Float16*>(c16);
   }
-  if (!spi::gemm_workspace_fits(d, spi::Prec::F16, kSlabFloats, kTickets))
-    return fail("gemm too large for the op workspace");
-  spi::GemmPtrs ptrs = scratch(workspace);
-  ptrs.A = A;
-  ptrs.W = W;
-  ptrs.bias = bias;
-  ptrs.res = residual;
-  ptrs.C = C;
-  ptrs.ln = lp;
-  return guarded([&] {
-    spi::gemm(d, ptrs, spi::Prec::F16, static_cast<hipStream_t>(stream));
-    return check_launch();
-  });
+  return run_gemm(d, spi::Prec::F16, A, W, bias, residual, C, lp, workspace, stream,
+                  "gemm too large for the op workspace");
 }
 
 }  // namespace

@@ -32,29 +32,7 @@ inline const char* kernel_id() {
     hipLaunchKernelGGL(F, G, B, SH, S, __VA_ARGS__);                                                     \
   } while (0)
 
-// Pointers of the LayerNorm fold (GemmDesc::ln_in_chunks / res_ln_chunks / ln_out).
-struct LnPtrs {
-  const float* in_stats = nullptr;   // A rows' chunk statistics
-  const float* c1 = nullptr;         // [N] per-column sum of the folded weights
-  const float* res_stats = nullptr;  // residual rows' chunk statistics
-  const float* res_g = nullptr;      // residual LayerNorm gain / bias
-  const float* res_b = nullptr;
-  float* out_stats = nullptr;        // output rows' chunk statistics
-  _Float16* c16 = nullptr;           // fp16 copy of the output (none with GemmDesc::out_planes)
-};
-
-struct GemmPtrs {
-  const void* A = nullptr;
-  const void* W = nullptr;
-  const float* bias = nullptr;
-  const void* res = nullptr;
-  void* C = nullptr;
-  float* partial = nullptr;  // split-K slabs (gemm_partial_floats)
-  int* counters = nullptr;   // split-K arrival tickets, zero-initialised (gemm_counter_slots)
-  const void* zeros = nullptr;  // >= 256 zero bytes (padded / out-of-range chunks; conv_wres: a null bias)
-  LnPtrs ln;
-};
-
+// GemmDesc, GemmPtrs and LnPtrs: gemm_desc.hpp.
 // Plans, routing and workspace sizing (gemm_partial_floats / gemm_counter_slots / gemm_kstep /
 // gemm_workspace_fits) are host-only: gemm_plan.hpp.
 void gemm(const GemmDesc& d, const GemmPtrs& p, Prec prec, hipStream_t s);
