@@ -137,7 +137,11 @@ int spi_op_stem_pool_u8(int32_t precision, const uint8_t* x, int32_t nhwc, int32
 int spi_op_patchify(int32_t src_kind, const void* x, int32_t B, int32_t H, int32_t W, int32_t ps,
                     const float* scale_host, const float* shift_host, void* y, int32_t out_f16, void* stream);
 
-/* Multi-head attention over packed qkv [B*S][3*D] (fp16 or fp32), head_dim 64. */
+/* Multi-head attention over packed qkv [B*S][3*D] (fp16 or fp32), head_dim 64: ctx [B*S][D] =
+ * softmax(q k^T scale + mask_bias) v per (batch, head); mask_bias fp32 [B][S] added to every query's
+ * scores, or null.  Rejected before any launch: a precision other than 0 (fp32) or 1 (fp16), a null
+ * qkv or ctx, B, S or heads <= 0, B * heads > 65535 (the grid's y extent), qkv off 16-byte alignment
+ * (q / k / v rows are read in 16-byte chunks), ctx off 8-byte alignment (the fp16 kernels' stores). */
 int spi_op_attention(int32_t precision, const void* qkv, const float* mask_bias, void* ctx,
                      int32_t B, int32_t S, int32_t heads, float scale, void* stream);
 

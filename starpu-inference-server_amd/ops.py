@@ -176,11 +176,13 @@ def conv_pair(prec, x_nhwc, spec0, spec1, ws, stream=None):
             "counter_slots": v[21]}
 
 
-def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None):
+def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None, out=None):
+    """ctx [B S][64 heads] of packed qkv [B S][3 D]; out: the buffer to write (default: a fresh one).  prec may
+    be the integer precision code itself."""
     D = heads * 64
-    ctx = torch.empty(B * S, D, device=qkv.device, dtype=qkv.dtype)
+    ctx = torch.empty(B * S, D, device=qkv.device, dtype=qkv.dtype) if out is None else out
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    _check(lib.spi_op_attention(PREC[prec], _ptr(qkv), _ptr(mask_bias), _ptr(ctx), B, S, heads, scale,
+    _check(lib.spi_op_attention(PREC.get(prec, prec), _ptr(qkv), _ptr(mask_bias), _ptr(ctx), B, S, heads, scale,
                                 C.c_void_p(s)))
     return ctx
 

@@ -1,5 +1,5 @@
 """Plain float64 / bit-exact references of the ops behind include/spi_ops.h that the GPU op tests
-(test_qkv_attention_ops_gpu.py, test_elementwise_ops_gpu.py, test_conv_pair_ops_gpu.py,
+(test_qkv_attention_ops_gpu.py, test_attention_ops_gpu.py, test_elementwise_ops_gpu.py, test_conv_pair_ops_gpu.py,
 test_hilo_weight_ops_gpu.py, the hi + lo consumer of test_ln_fold_ops_gpu.py) compare the HIP kernels with,
 plus the inputs and case lists those tests share.  Nothing here touches a GPU; test_op_refs.py checks every reference
 against the torch op it restates, so the GPU bars rest on checked ground.
@@ -84,12 +84,37 @@ def combine_stats64(stats, eps):
     return mean, 1.0 / np.sqrt(m2 / (64.0 * s.shape[1]) + eps)
 
 
+def attention_ref(qkv, mask_bias, B, S, heads, scale):
+    """float64 softmax(q k^T scale + mask) v on the packed [B S][3 D] operand as given (mask_bias [B][S]
+    or None, added to every query's scores).  Returns float64 [B S][64 heads]."""
+    q, k, v = _heads(torch.from_numpy(np.ascontiguousarray(qkv, np.float64)), B, S, heads)
+    s = (q @ k.transpose(-1, -2)) * scale
+    if mask_bias is not None:
+        s = s + torch.from_numpy(np.asarray(mask_bias, np.float64).reshape(B, S))[:, None, None, :]
+    p = torch.exp(s - s.max(-1, keepdim=True).values)
+    o = (p @ v) / p.sum(-1, keepdim=True)
+    return o.permute(0, 2, 1, 3).reshape(B * S, heads * 64).numpy()
+
+
+def emulate_attention_f16(qkv16, mask_bias, B, S, heads, scale):
+    """The fp16 attention kernels' arithmetic (attention.hip, the tail of qkv_attn.hip) in torch on the CPU:
+    fp32 scores and softmax on the fp16 q / k, the row sum taken from the fp32 probabilities, fp16 P against
+    fp16 V accumulated in fp32, fp16 output.  (The kernels' summation order, their online rescaling and
+    __expf are what the GPU bar's slack over this is for.)"""
+    q, k, v = _heads(torch.from_numpy(np.ascontiguousarray(qkv16, np.float16)).float(), B, S, heads)
+    s = (q @ k.transpose(-1, -2)) * np.float32(scale)
+    if mask_bias is not None:
+        s = s + torch.from_numpy(np.asarray(mask_bias, np.float32).reshape(B, S))[:, None, None, :]
+    p = torch.exp(s - s.max(-1, keepdim=True).values)
+    o = (p.half().float() @ v) / p.sum(-1, keepdim=True)
+    return o.permute(0, 2, 1, 3).reshape(B * S, heads * 64).half().numpy()
+
+
 def qkv_attention_ref(A16, W16, bias, mask_bias, B, S, heads, scale, stats=None, c1=None, eps=None, round16=True):
     """float64 reference on the operands as given (A16 / W16 are normally fp16 arrays): q | k | v =
     A W^T + bias, or with the fold rstd (A W^T - mean c1) + bias with (mean, rstd) combined from the chunk
     statistics; rounded to fp16 where the kernel rounds (round16); softmax(q k^T scale + mask) v in
     float64.  Returns float64 [B S][64 heads]."""
-    D = heads * 64
     acc = np.asarray(A16, np.float64) @ np.asarray(W16, np.float64).T
     if stats is not None:
         mean, rstd = combine_stats64(stats, eps)
@@ -97,13 +122,7 @@ def qkv_attention_ref(A16, W16, bias, mask_bias, B, S, heads, scale, stats=None,
     qkv = acc + np.asarray(bias, np.float64)
     if round16:
         qkv = qkv.astype(np.float16).astype(np.float64)
-    q, k, v = _heads(torch.from_numpy(qkv), B, S, heads)
-    s = (q @ k.transpose(-1, -2)) * scale
-    if mask_bias is not None:
-        s = s + torch.from_numpy(np.asarray(mask_bias, np.float64).reshape(B, S))[:, None, None, :]
-    p = torch.exp(s - s.max(-1, keepdim=True).values)
-    o = (p @ v) / p.sum(-1, keepdim=True)
-    return o.permute(0, 2, 1, 3).reshape(B * S, D).numpy()
+    return attention_ref(qkv, mask_bias, B, S, heads, scale)
 
 
 def emulate_qkv_attention(A16, W16, bias, mask_bias, B, S, heads, scale, stats=None, c1=None, eps=None):
@@ -111,20 +130,92 @@ def emulate_qkv_attention(A16, W16, bias, mask_bias, B, S, heads, scale, stats=N
     epilogue in fp32, fp16 q / k / v, fp32 scores and softmax with the row sum taken from the fp32
     probabilities, fp16 P against fp16 V accumulated in fp32, fp16 output.  (The kernel's summation
     order, its online rescaling and __expf are what the GPU bar's slack over this is for.)"""
-    D = heads * 64
     acc = torch.from_numpy(np.asarray(A16, np.float16)).float() @ torch.from_numpy(np.asarray(W16, np.float16)).float().T
     if stats is not None:
         mean, rstd = combine_stats64(stats, eps)
         mean32, rstd32 = torch.from_numpy(mean.astype(np.float32)), torch.from_numpy(rstd.astype(np.float32))
         acc = rstd32[:, None] * (acc - mean32[:, None] * torch.from_numpy(np.asarray(c1, np.float32)))
     qkv = (acc + torch.from_numpy(np.asarray(bias, np.float32))).half().float()
-    q, k, v = _heads(qkv, B, S, heads)
-    s = (q @ k.transpose(-1, -2)) * np.float32(scale)
-    if mask_bias is not None:
-        s = s + torch.from_numpy(np.asarray(mask_bias, np.float32).reshape(B, S))[:, None, None, :]
-    p = torch.exp(s - s.max(-1, keepdim=True).values)
-    o = (p.half().float() @ v) / p.sum(-1, keepdim=True)
-    return o.permute(0, 2, 1, 3).reshape(B * S, D).half().numpy()
+    return emulate_attention_f16(qkv.numpy(), mask_bias, B, S, heads, scale)
+
+
+# ---------------------------------------------------------------------------------------------
+# the standalone attention kernels (attention.hip): what the model runs on the default ViT path, for every
+# fp32 transformer and for every sequence the fused kernel refuses (S > 256)
+
+# (B, S, heads): both sides of each kernel boundary (fp16: 4 waves up to 128 keys, the whole sequence staged
+# for 129..224, 64-key tiles from 225 on; fp32: 64-query x 64-key tiles throughout), up to 5 query blocks x
+# 10 key tiles
+ATTN_SHAPES = [(1, 1, 2), (2, 17, 3), (2, 127, 2), (2, 128, 2), (1, 129, 2), (2, 197, 3), (1, 224, 2), (1, 225, 2),
+               (1, 257, 2), (2, 384, 2), (1, 512, 3), (1, 577, 2)]
+ATTN_MASKS = [None, "head", "middle", "tail"]
+ATTN_CASES = [(B, S, h, kind) for (B, S, h) in ATTN_SHAPES for kind in ATTN_MASKS if kind is None or S > 1]
+# the near-exact cases (B = 2, heads = 2): each side of every multiple of 64 up to 256, then long sequences
+ATTN_EXACT_S = [1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193, 223, 224, 225, 255, 256, 257, 320, 385, 512,
+                577]
+ATTN_EXACT_VARIANTS = ["ones", "head", "tile", "all"]
+ATTN_EXACT_CASES = [(S, v) for S in ATTN_EXACT_S for v in ATTN_EXACT_VARIANTS
+                    if not (v == "head" and S == 1) and not (v == "tile" and S < 193)]
+# emulate_attention_f16's normalised max error against attention_ref over ATTN_CASES: the worst measured on
+# a CPU is 4.04e-4 ((1, 129, 2) "head"; 1.6e-4 .. 4.0e-4 over the list), and
+# test_op_refs.test_attention_emulation_within_bar holds every case to ATTN_EMU_TOL.  The fp16 GPU bar is 3x
+# the measured worst case.
+ATTN_EMU_WORST = 4.1e-4
+ATTN_EMU_TOL = 5e-4
+
+
+def attn_mask(B, S, kind):
+    """fp32 additive mask [B][S] (FMIN on a masked key) on the last sequence, or None.  "head": keys
+    0 .. min(69, S - 2), a whole first 64-key tile and the next one's edge (and, with B > 1, the first three
+    keys of sequence 0); "middle": keys 123 .. 196 clipped to S - 1, a whole interior tile and both
+    neighbours' edges (nothing for S <= 123: an all-zero mask); "tail": from S / 2 on."""
+    if kind is None:
+        return None
+    m = np.zeros((B, S), np.float32)
+    if kind == "head":
+        m[-1, :min(69, S - 2) + 1] = FMIN
+        if B > 1:
+            m[0, :min(3, S - 1)] = FMIN
+    elif kind == "middle":
+        m[-1, 123:min(197, S)] = FMIN
+    elif kind == "tail":
+        m[-1, S // 2:] = FMIN
+    else:
+        raise ValueError(kind)
+    return m
+
+
+def attn_case(B, S, heads):
+    """The parity operand: packed qkv fp32 [B S][3 D] of 1.5 N(0, 1) (scores of sigma about 2.25 at scale 1/8)."""
+    rng = np.random.default_rng(B * S + heads)
+    return (1.5 * rng.standard_normal((B * S, 3 * heads * 64))).astype(np.float32)
+
+
+def attn_exact_case(S, variant):
+    """A near-exact case, B = 2, heads = 2: q = 0, so every score is 0 and every probability 1 or 0; k random;
+    v random but for column 0 of each head, which holds 1 on a key that counts and -7 on a masked one.
+    ctx[:, 0] of each head is then a known quotient.  "ones": no mask, 1; "head" / "tile": attn_mask's "head"
+    / "middle" keys masked, still 1; "all": every key of the last sequence masked and its values drawn from
+    {1, -7}: their mean (kept off zero, the bar is relative).
+    Returns (qkv fp32 [2 S][384], exact in fp16; mask [2][S] or None; want float64 [2][S])."""
+    B, heads, D = 2, 2, 128
+    rng = np.random.default_rng(1000 + S)
+    qkv = (1.5 * rng.standard_normal((B, S, 3, heads, 64))).astype(np.float16).astype(np.float32)
+    qkv[:, :, 0] = 0
+    want = np.ones((B, S), np.float64)
+    if variant == "all":
+        mask = np.zeros((B, S), np.float32)
+        mask[1, :] = FMIN
+        v0 = np.ones((B, S), np.float32)
+        v0[1] = np.where(rng.random(S) < 0.4, -7, 1)
+        if v0[1].sum() == 0:
+            v0[1, 0] = -v0[1, 0] - 6  # 1 <-> -7
+        want[1, :] = v0[1].astype(np.float64).mean()
+    else:
+        mask = attn_mask(B, S, {"ones": None, "head": "head", "tile": "middle"}[variant])
+        v0 = np.ones((B, S), np.float32) if mask is None else np.where(mask != 0, -7, 1).astype(np.float32)
+    qkv[:, :, 2, :, 0] = v0[:, :, None]
+    return qkv.reshape(B * S, 3 * D), mask, want
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """The references of tests/op_refs.py against the torch ops they restate, without a GPU -- what makes
-the bars of test_qkv_attention_ops_gpu.py and test_elementwise_ops_gpu.py trustworthy -- and the
-emulation of qkv_attn.hip's arithmetic from which the fused kernel's GPU bar is taken."""
+the bars of test_qkv_attention_ops_gpu.py, test_attention_ops_gpu.py and test_elementwise_ops_gpu.py
+trustworthy -- and the emulations of qkv_attn.hip's and attention.hip's arithmetic from which the fp16
+attention kernels' GPU bars are taken."""
 import importlib
 
 import numpy as np
@@ -93,6 +94,80 @@ def test_combine_stats_restated(ops):
     for a, b in zip(R.combine_stats64(st, R.EPS), ops.combine_stats(st, R.EPS)):
         np.testing.assert_array_equal(a, b)
     np.testing.assert_allclose(R.combine_stats64(st, R.EPS)[1], 1 / np.sqrt(x.var(1) + R.EPS), rtol=1e-12)
+
+
+# ---- the standalone attention kernels -----------------------------------------------------------
+
+
+def _sdpa64(qkv, mask, B, S, heads, scale):
+    q, k, v = torch.from_numpy(qkv.astype(np.float64)).view(B, S, 3, heads, 64).permute(2, 0, 3, 1, 4)
+    m = None if mask is None else torch.from_numpy(mask).double()[:, None, None, :]
+    o = F.scaled_dot_product_attention(q, k, v, attn_mask=m, scale=scale)
+    return o.permute(0, 2, 1, 3).reshape(B * S, heads * 64).numpy()
+
+
+@pytest.mark.parametrize("B,S,heads,kind,scale", [(2, 17, 3, None, 0.125), (2, 197, 3, "head", 0.125),
+                                                  (1, 257, 2, "middle", 0.25), (2, 70, 2, "tail", 0.125)])
+def test_attention_ref_equals_sdpa_float64(B, S, heads, kind, scale):
+    qkv, mask = R.attn_case(B, S, heads), R.attn_mask(B, S, kind)
+    got = R.attention_ref(qkv, mask, B, S, heads, scale)
+    assert got.shape == (B * S, heads * 64) and got.dtype == np.float64
+    assert R.nerr(got, _sdpa64(qkv, mask, B, S, heads, scale)) < TOL64
+
+
+def test_attn_mask_kinds():
+    assert R.attn_mask(2, 300, None) is None
+    m = R.attn_mask(2, 300, "head") != 0
+    assert m[1, :70].all() and not m[1, 70:].any() and m[0, :3].all() and not m[0, 3:].any()
+    assert not (R.attn_mask(1, 300, "head") != 0)[0, 70:].any() and (R.attn_mask(1, 300, "head") != 0)[0, :70].all()
+    m = R.attn_mask(2, 17, "head") != 0  # keys 0 .. S - 2: the last key stays
+    assert m[1, :16].all() and not m[1, 16]
+    m = R.attn_mask(2, 300, "middle") != 0
+    assert m[1, 123:197].all() and m[1].sum() == 74 and not m[0].any()
+    assert (R.attn_mask(1, 150, "middle") != 0)[0].nonzero()[0].tolist() == list(range(123, 150))
+    assert not R.attn_mask(2, 100, "middle").any()
+    m = R.attn_mask(2, 225, "tail") != 0
+    assert m[1, 112:].all() and not m[1, :112].any() and not m[0].any()
+    for B, S, _, kind in R.ATTN_CASES:  # a masked value is FMIN, and no sequence of a parity case is masked whole
+        m = R.attn_mask(B, S, kind)
+        assert m is None or (set(np.unique(m)) <= {0.0, R.FMIN} and (m == 0).any(axis=1).all())
+    assert all(kind is None for (_, S, _, kind) in R.ATTN_CASES if S == 1)
+
+
+@pytest.mark.parametrize("B,S,heads,kind", R.ATTN_CASES)
+def test_attention_emulation_within_bar(B, S, heads, kind):
+    """The fp16 kernels' arithmetic on the CPU against the float64 reference on the same fp16 operand: the
+    figure the fp16 GPU bar of test_attention_ops_gpu.py is three times of."""
+    q16, mask = R.attn_case(B, S, heads).astype(np.float16), R.attn_mask(B, S, kind)
+    ref = R.attention_ref(q16, mask, B, S, heads, 0.125)
+    e = R.nerr(R.emulate_attention_f16(q16, mask, B, S, heads, 0.125), ref)
+    print(f"attention emulation B{B} S{S} H{heads} mask {kind}: {e:.3e}")
+    assert np.isfinite(ref).all() and e <= R.ATTN_EMU_TOL
+
+
+@pytest.mark.parametrize("S,variant", R.ATTN_EXACT_CASES)
+def test_attention_exact_cases_are_exact(S, variant):
+    """The near-exact inputs give the quotient they claim in the float64 reference, and the emulated fp16
+    arithmetic lands within the GPU test's 2^-10."""
+    qkv, mask, want = R.attn_exact_case(S, variant)
+    assert np.array_equal(qkv, qkv.astype(np.float16).astype(np.float32)) and (want != 0).all()
+    w = np.repeat(want.reshape(2 * S, 1), 2, axis=1)
+    ref = R.attention_ref(qkv, mask, 2, S, 2, 0.125)[:, ::64]
+    assert np.abs(ref / w - 1).max() < TOL64
+    emu = R.emulate_attention_f16(qkv, mask, 2, S, 2, 0.125).astype(np.float64)[:, ::64]
+    assert np.abs(emu / w - 1).max() <= 2.0 ** -10
+
+
+@pytest.mark.parametrize("S", R.ATTN_EXACT_S)
+def test_attention_exact_cases_discriminate(S):
+    """One zero-valued padding key let into the softmax of the all-ones case moves the result from 1 to
+    S / (S + 1): 1 / 578 = 1.7e-3 at the longest sequence, above the 2^-10 bar."""
+    qkv, _, _ = R.attn_exact_case(S, "ones")
+    leaky = np.zeros((2, S + 1, 384), np.float32)
+    leaky[:, :S] = qkv.reshape(2, S, 384)
+    got = R.attention_ref(leaky.reshape(-1, 384), None, 2, S + 1, 2, 0.125).reshape(2, S + 1, 128)[:, :S, ::64]
+    off = np.abs(got - 1)
+    assert abs(off.min() - 1 / (S + 1)) < TOL64 and off.min() > 1.5 * 2.0 ** -10
 
 
 # ---- hi + lo weights (krep = 2) -----------------------------------------------------------------

@@ -7,6 +7,9 @@ accumulation, fp32 residual stream / LN / softmax) 1e-3 for the model families
 at the reference configs.  Inputs are seeded synthetic data shaped like the
 reference's input generator (src/utils/input_generator.hpp:22-88).
 """
+import functools
+import importlib
+
 import numpy as np
 import pytest
 import torch
@@ -465,6 +468,90 @@ def test_vit_qkv_attention_fused(spi, zoo, gpu, img, patch, fold, monkeypatch):
     # the unfused QKV GEMM runs on gemm256 here (a different k order than the fused kernel's, so
     # some fp16 roundings of Q / K / V flip): 2.2e-4 measured at S = 197 with the fold
     assert e < 1e-3 and d < 5e-4, (e, d)
+
+
+def op_names(rep, inputs, out_shape):
+    """The op names of one profiled forward of the replica on the inputs."""
+    ins = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in inputs]
+    ops = rep.profile(ins, torch.empty(out_shape, device="cuda"), torch.cuda.current_stream().cuda_stream)
+    return {o["name"] for o in ops}
+
+
+def assert_standalone_route(names, S):
+    """Past 256 tokens the fused kernel refuses: the QKV GEMM, then the standalone attention kernels."""
+    assert f"attention_S{S}" in names and not any(n.startswith("qkv_attention_") for n in names), sorted(names)
+
+
+@functools.lru_cache(maxsize=None)
+def bert_long(S):
+    """The small long-sequence BERT, two sequences of S tokens with the last padded from about 0.6 S, and the
+    oracle's output, computed once."""
+    zoo = importlib.import_module("starpu-inference-server_amd.zoo")
+    m = zoo.bert(layers=2, hidden=128, heads=2, intermediate=256, init_std=0.05)
+    ids, mask = bert_inputs(np.random.default_rng(43 + S), 2, S, pad_from=int(0.6 * S))
+    return m, ids, mask, cpu_inference(m, [ids, mask])[0]
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16", "fp16m"])
+@pytest.mark.parametrize("S", [257, 384, 512])
+def test_bert_long_sequences(spi, gpu, S, prec, monkeypatch):
+    """BERT past the fused kernel's 256 rows (S = 257, 384, 512 on a seq_len = 512 replica): the QKV GEMM --
+    folded in fp16 -- feeding the standalone attention kernels over 5 to 8 key tiles, a padded tail that masks
+    whole trailing tiles, against the oracle; fp16 with and without the LayerNorm fold."""
+    m, ids, mask, ref = bert_long(S)
+    kw = dict(max_batch=2, seq_len=512)
+    outs = {}
+    for fold in (("1", "0") if prec == "fp16" else (None,)):
+        if fold is not None:
+            monkeypatch.setenv("SPI_LN_FOLD", fold)
+        rep = spi.ModelReplica(m, 0, prec, **kw)
+        outs[fold] = hip_forward(spi, rep, [ids, mask], ref.shape)
+        assert_standalone_route(op_names(rep, [ids, mask], ref.shape), S)
+        e = normalized_max_error(outs[fold], ref)
+        print(f"bert long S{S} {prec} fold {fold}: vs oracle {e:.3e}")
+        assert np.isfinite(outs[fold]).all() and e < TOL[prec], e
+    if prec == "fp16":
+        d = normalized_max_error(outs["1"], outs["0"])
+        print(f"bert long S{S} fp16: folded vs unfused {d:.3e}")
+        assert d < 1e-3, d
+
+
+def test_bert_one_replica_two_attention_routes(spi, gpu):
+    """One fp16 replica at seq_len = 512 serving S = 128, 384, 128, 384 with graphs on alternates between the
+    fused QKV + attention kernel and the QKV GEMM + standalone attention: every output is, bit for bit, that
+    of a fresh replica serving only that S."""
+    m = bert_long(384)[0]
+    kw = dict(max_batch=2, seq_len=512)
+    inputs = {S: bert_inputs(np.random.default_rng(47 + S), 2, S, pad_from=int(0.6 * S)) for S in (128, 384)}
+    ref = {S: cpu_inference(m, list(inputs[S]))[0] for S in inputs}
+    shape = {S: ref[S].shape for S in inputs}
+    fresh = {S: hip_forward(spi, spi.ModelReplica(m, 0, "fp16", **kw), list(inputs[S]), shape[S], graphs=True)
+             for S in inputs}
+    rep = spi.ModelReplica(m, 0, "fp16", **kw)
+    for S in (128, 384, 128, 384):
+        got = hip_forward(spi, rep, list(inputs[S]), shape[S], graphs=True)
+        assert np.isfinite(got).all()
+        np.testing.assert_array_equal(got, fresh[S], err_msg=f"S{S} after the other route")
+    assert "qkv_attention_S128" in op_names(rep, list(inputs[128]), shape[128])
+    assert_standalone_route(op_names(rep, list(inputs[384]), shape[384]), 384)
+    for S in inputs:
+        assert normalized_max_error(fresh[S], ref[S]) < TOL["fp16"]
+
+
+@pytest.mark.parametrize("prec", ["fp32", "fp16"])
+def test_vit_384px_seq577(spi, zoo, gpu, prec, monkeypatch):
+    """ViT at 384 / 16 (S = 577: 5 query blocks x 10 key tiles with a 1-key tail on the standalone attention
+    kernels), small width, the LayerNorm fold on."""
+    m = zoo.vit(image=384, patch=16, layers=2, heads=2, dim=128, mlp_dim=256)
+    x = image(np.random.default_rng(53), 2, 384)
+    ref = cpu_inference(m, [x])[0]
+    monkeypatch.setenv("SPI_LN_FOLD", "1")
+    rep = spi.ModelReplica(m, 0, prec, max_batch=2, image_size=384)
+    got = hip_forward(spi, rep, [x], ref.shape)
+    assert_standalone_route(op_names(rep, [x], ref.shape), 577)
+    err = normalized_max_error(got, ref)
+    print(f"vit-small 384px S577 {prec} err={err:.3e}")
+    assert np.isfinite(got).all() and err < TOL[prec]
 
 
 def test_affine_codelet_like_reference(spi, gpu):
