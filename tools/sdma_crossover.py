@@ -2,7 +2,7 @@
 """Where SDMA H2D stops paying: ResNet-18 / 34 / 50 / 101 / 152 at bs8 through the runtime's e2e
 closed loop (4 workers, 32 in flight) with the H2D on the SDMA engines vs on the worker streams,
 rounds interleaved in one process.  The models span 166 .. 26 KiB of fp32 input per GFLOP of the
-forward -- the quantity SPI_H2D_AUTO's rule thresholds (runtime.cpp).  Basic-block nets run the
+forward -- the quantity SPI_H2D_AUTO's rule thresholds (runtime_config.cpp).  Basic-block nets run the
 C2 mode (fp16m), bottleneck nets the C4 mode (fp16x3), as served."""
 import importlib
 import json
