@@ -9,6 +9,7 @@
 // Keys past S (ViT's 197 = 3*64 + 5) are masked to -inf, the BERT attention
 // mask arrives as an additive fp32 bias ((1 - m) * finfo(f32).min, the value
 // HF's BertModel adds).  head_dim is fixed at 64.
+#include "lds_dma.hpp"
 #include "spi_kernels.hpp"
 
 #include <cstdlib>
@@ -16,8 +17,6 @@
 namespace spi {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int HD = 64;
 constexpr int QT = 64;
@@ -228,7 +227,6 @@ __global__ __launch_bounds__(64 * NW) void attn_f16_swapped_kernel(const _Float1
                                                                const float* __restrict__ mask_bias,
                                                                _Float16* __restrict__ ctx, int S, int H,
                                                                float scale) {
-  typedef _Float16 half4 __attribute__((ext_vector_type(4)));
   typedef short short4v __attribute__((ext_vector_type(4)));
   typedef __attribute__((address_space(3))) short4v lds_s4;
   constexpr int LD = HD + 8;  // K / V row stride in elements (144 B: 16-byte rows, 8-byte tr reads)

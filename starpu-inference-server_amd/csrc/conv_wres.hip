@@ -22,6 +22,7 @@
 //     residual + ReLU + fp16 row vectors.
 // Per band it takes in (th + 2)(W + 2) x 128 B (29.7 KiB at W = 56) for
 // 2 x 112 x 64 x 576 FLOP: ~320 FLOP per byte, MFMA-bound per CU.
+#include "lds_dma.hpp"
 #include "spi_kernels.hpp"
 
 #include <algorithm>
@@ -31,11 +32,6 @@
 
 namespace spi {
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int kRowB = 128;                  // 64 fp16 channels = one pixel row / one W row per tap
 constexpr int kWImg = 64 * kRowB;           // one tap's [64 cout][64 cin] image: 8 KiB
@@ -63,33 +59,6 @@ struct WresArgs {
   int bands_per_img, bands;
 };
 
-__device__ __forceinline__ u32x4 rd_chunk(const char* img, int row, int c) {
-  return *reinterpret_cast<const u32x4*>(img + row * kRowB + ((c ^ (row & 7)) << 4));
-}
-
-template <int N>
-__device__ __forceinline__ void dma_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// One 1-KiB LDS-DMA piece (lane l's 16 bytes from `src` to dst + 16 l), issued in
-// inline asm so hipcc does not track it: with the builtin, hipcc cannot tell the
-// pending DMA from the LDS the next ds_reads touch and drains every DMA
-// (s_waitcnt vmcnt(0)) before them, which would serialise the next band's halo with
-// this band's k-loop.  The caller counts these with dma_wait_barrier<N>
-// (cdna_hip_programming.md 5.7, the M0-saving LDS-DMA recipe).
-__device__ __forceinline__ void glds16(const void* src, const char* dst) {
-  const lds_ptr_t lp = (lds_ptr_t)(const_cast<char*>(dst));
-  const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lp);
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(m0v)
-               : "memory");
-}
-
 // Diagnostic build (-DSPI_WRES_STAMPS): per-workgroup s_memtime stamps of the phases of
 // its first two bands (tools/wres_stamps.py); no output value depends on them.
 #ifdef SPI_WRES_STAMPS
@@ -105,14 +74,6 @@ __device__ unsigned long long g_wres_stamps[4096 * 10];
   do {                \
   } while (0)
 #endif
-
-template <int T, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (T < N) {
-    f(std::integral_constant<int, T>{});
-    static_for<T + 1, N>(f);
-  }
-}
 
 // LDS map: the halo buffer at 0, the resident weights from kHBuf.
 template <bool HAS_RES, bool RELU>

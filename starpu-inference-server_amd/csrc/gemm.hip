@@ -27,15 +27,20 @@
 // them with sc1 loads and runs the epilogue -- no second launch, no cache-wide
 // fences (cdna_hip_programming.md, "In-launch split-K reduction").
 //
-// This file holds the kernels, the table of their instances and the launch.  What the host does
-// before a launch is host-only code, checked without a GPU: the plan (gemm_plan.cpp), the desc
-// checks and the kernel arguments (gemm_args.cpp), and in gemm_args.hpp the argument structs and the
-// workgroup -> (tile, slice) decode, which the kernels below and the CPU tests both call.
+// This file holds the kernels, the table of their instances and the launch.  The numbers of a kernel
+// instance (modes, A-operand kinds, TileGeo: every constant of the body below and the static_asserts
+// that guard them) are gemm_tile.hpp, shared with the planner; the hand-counted LDS-DMA, its waits,
+// the swizzled fragment read and static_for are lds_dma.hpp, shared with conv_wres.hip.  What the
+// host does before a launch is host-only code, checked without a GPU: the plan (gemm_plan.cpp), the
+// desc checks and the kernel arguments (gemm_args.cpp), and in gemm_args.hpp the argument structs and
+// the workgroup -> (tile, slice) decode, which the kernels below and the CPU tests both call.
 // The diagnostic builds' macros and readers are gemm_diag.hpp.
 #include "device_math.hpp"
 #include "gemm_args.hpp"
 #include "gemm_diag.hpp"
 #include "gemm_plan.hpp"
+#include "gemm_tile.hpp"
+#include "lds_dma.hpp"
 #include "ln_fold.hpp"
 #include "spi_kernels.hpp"
 
@@ -49,42 +54,16 @@
 namespace spi {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
+template <int V>
+using IC = std::integral_constant<int, V>;
 
+// Element types of a mode's A operand and (unless the desc says otherwise) its output / residual;
+// the modes' numbers are gemm_tile.hpp.
 template <int MODE>
-struct Traits;
-// RB: bytes of each A / W image row per k-step; ESTEP: k-values per step;
-// EPC: A elements per 16-byte chunk.
-template <>
-struct Traits<(int)Prec::F16> {
-  using A = _Float16;
-  using Out = _Float16;
-  static constexpr int RB = 128, ESTEP = 64, EPC = 8;
+struct Traits {
+  using A = std::conditional_t<MODE == (int)Prec::F16, _Float16, float>;
+  using Out = A;
 };
-template <>
-struct Traits<(int)Prec::F32> {
-  using A = float;
-  using Out = float;
-  static constexpr int RB = 128, ESTEP = 32, EPC = 4;
-};
-template <>
-struct Traits<(int)Prec::F16X3> {  // A: 32 fp32; W: [32 hi | 32 lo] (RB = 256 measured slower: VGPRs, LDS)
-  using A = float;
-  using Out = float;
-  static constexpr int RB = 128, ESTEP = 32, EPC = 4;
-};
-// Kernel-internal mode kF16X3S (gemm_args.hpp): F16X3 whose A (and residual) are activations already
-// stored split, [32 hi fp16 | 32 lo fp16] per 32 channels (GemmDesc::a_split).
-// Byte-for-byte the same addressing as fp32 A (a 32-k block is 128 bytes either
-// way), so only the fragment reads differ: A is read exactly like W.
-template <>
-struct Traits<kF16X3S> : Traits<(int)Prec::F16X3> {};
-
-template <int MODE>
-constexpr bool kSplitMode = MODE == (int)Prec::F16X3 || MODE == kF16X3S;
 
 // Split layout index (in fp16 units) of logical element (m, n) of a row-major
 // [rows][ld] tensor: hi at the returned index, lo 32 further on.
@@ -115,6 +94,7 @@ __device__ __forceinline__ float load_res(const KArgs& a, int m, int n) {
                      : static_cast<float>(static_cast<const Out*>(a.p.res)[idx]);
 }
 
+// fp32 A at fragment read (F16X3): 8 values as hi = fp16(x), lo = fp16(x - hi)
 __device__ __forceinline__ void split8(const u32x4& x0, const u32x4& x1, half8& hi, half8& lo) {
   const floatx4 f0 = __builtin_bit_cast(floatx4, x0);
   const floatx4 f1 = __builtin_bit_cast(floatx4, x1);
@@ -129,107 +109,6 @@ __device__ __forceinline__ void split8(const u32x4& x0, const u32x4& x1, half8& 
   }
 }
 
-// Wait for this wave's LDS-DMA down to N outstanding, then barrier.  One asm
-// statement with a memory clobber so no LDS access moves across it.
-template <int N>
-__device__ __forceinline__ void dma_wait_barrier() {
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
-// One 1-KiB LDS-DMA piece (lane l's 16 bytes from `src` to dst + 16 l) issued from inline
-// asm, invisible to hipcc's waitcnt pass: the epilogue's residual prefetch lands in a stage
-// region addressed at run time, and with the builtin hipcc would assume it may alias the
-// last k-steps' fragment reads and drain it (vmcnt(0)) before them.  Counted by the
-// k-loop's dma_wait_barrier<N> and waited for explicitly before the epilogue reads it.
-__device__ __forceinline__ void glds16(const void* src, char* dst) {
-  const lds_ptr_t lp = (lds_ptr_t)dst;
-  const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lp);
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(m0v)
-               : "memory");
-}
-
-// The 4-byte form (a 256-byte piece: lane l's 4 bytes to dst + 4 l), same hand-counted contract.
-__device__ __forceinline__ void glds4(const void* src, char* dst) {
-  const lds_ptr_t lp = (lds_ptr_t)dst;
-  const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)lp);
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(m0v)
-               : "memory");
-}
-
-template <int RB>
-__device__ __forceinline__ u32x4 rd_chunk(const char* img, int row, int c) {
-  constexpr int CPR = RB / 16;  // 16-byte chunks per image row
-  return *reinterpret_cast<const u32x4*>(img + row * RB + ((c ^ (row & (CPR - 1))) << 4));
-}
-
-// A-operand kinds: dense rows; conv with one (kh, kw) tap per k-step (Cin >= the
-// k-step: scalar tap walk + per-row tap mask); conv in general (per-chunk taps:
-// the stem); 3x3/s1/p1 conv from an LDS-resident input band (kConvHalo, below).
-// Separate instantiations keep each kind's loop free of the others.
-enum : int { kDense = 0, kConvTap = 1, kConvGen = 2, kConvHalo = 3, kConvHaloS = 4, kConvTapW = 5 };
-
-// Split-K is compiled into the tiles split_k_compiled names (gemm_args.hpp).  Launch bounds ask
-// for the occupancy each tile reaches within its registers: 4 / 3 / 2 waves per SIMD.
-template <int BM, int BN, int KIND>
-constexpr bool kSplitK = split_k_compiled(BM, BN, KIND == kConvHalo || KIND == kConvHaloS);
-
-// kConvHalo.  An implicit-GEMM conv stages each (tap, channel block) A tile
-// separately: every input pixel crosses the CU nine times, and the vector-memory
-// ingest of a CU (~70 GB/s from L2, MI355X_MICROARCH.md "gather into LDS") is
-// what bounds these layers (no-DMA diagnostic build: +64 % end to end).  Here a
-// tile is a band of whole output rows of one image; per channel block the band's
-// input rows plus the 1-pixel border -- (th + 2) x (W + 2) pixels, 128 bytes each,
-// swizzled like the ring images -- are DMA'd once into one of two halo buffers,
-// and the nine taps read their A fragments from it at a pixel offset of
-// kh * (W + 2) + kw.  Only W goes through the per-step ring.  Halo pixels per
-// buffer: HQ DMA instructions per wave x 4 waves x 8 pixels.
-// kConvHaloS: the 64-row kind with 96-pixel buffers (14- and 7-wide layers):
-// 48 KiB of LDS instead of 56, three workgroups per CU instead of two.
-// NW = 8 (the 256-row kind, 4 x 2 waves): 6 pieces per wave = 384-pixel buffers.
-template <int BM, int KIND, int NW>
-constexpr int kHaloHQ = KIND == kConvHaloS ? 3 : NW == 8 ? 6 : BM == 64 ? 4 : 8;
-template <int KIND>
-constexpr bool kIsHalo = KIND == kConvHalo || KIND == kConvHaloS;
-// kConvTapW (round 4): 3x3/s1/p1 tap walk with the three kw taps of a (kh, channel block)
-// reading one A window.  For stride 1 and padding 1 (OH = H, OW = W) the input pixel of tap
-// (kh, kw) of output row m is the global pixel m + (kh - 1) W + kw - 1, so the 64 rows of a
-// tile read, for the three kw taps, the 66 consecutive pixels from m0 + (kh - 1) W - 1 on:
-// one DMA'd window of BM + 8 rows (BM / 32 16-byte pieces + one 4-byte piece per wave) feeds
-// 3 k-steps -- for 64-row tiles 9 KiB of A per 3 steps instead of 24 (a step's LDS ingest 16 ->
-// 11 KiB; 128-row tiles 24 -> 13.7 KiB; the tap walks run at the per-CU ingest ceiling,
-// DESIGN.md 3.1.5).
-// Taps that fall into the padding read a real neighbour pixel of the window and are zeroed
-// at fragment read by the row's tap mask.  Only W goes through the STAGES ring.
-template <int BM>
-constexpr int kWinRows = BM + 8;
-// Dense kinds keep 2 x BM {mean, rstd} pairs past the ring for the LayerNorm fold (the tile's
-// row statistics, computed once per row before the epilogue's walk).
-template <int BM, int KIND>
-constexpr int kLnBytes = KIND == kDense ? 2 * BM * 8 : 0;
-// Window kind with NW = 8 (round 5): two K groups of 4 waves in one workgroup, each walking
-// half of the slice's super-steps through its own LDS (ring + windows) and reducing through
-// LDS at the end -- the intra-workgroup split-K of DESIGN.md 3.1.6.
-template <int KIND, int NW>
-constexpr int kKGroups = KIND == kConvTapW && NW == 8 ? 2 : 1;
-// LDS bytes of one K group (the whole workgroup: kKGroups times this)
-template <int BM, int BN, int STAGES, int KIND, int NW>
-constexpr int kLdsBytes = kIsHalo<KIND> ? STAGES * BN * 128 + 2 * kHaloHQ<BM, KIND, NW> * NW * 8 * 128 + 16
-                          : KIND == kConvTapW ? STAGES * BN * 128 + 2 * kWinRows<BM> * 128 + 16
-                                              : STAGES * (BM + BN) * 128 + kLnBytes<BM, KIND> + 16;
-// Occupancy asked of the register allocator: 4 / 3 / 2 waves per SIMD by tile
-// size per wave (of a K group), capped by what the tile's LDS ring allows (NW / 4 waves
-// per SIMD per block, 160 KiB of LDS per CU; RB = 128 bytes per row per stage in every mode).
-template <int BM, int BN, int STAGES, int KIND, int NW>
-constexpr int kMinWaves = std::max(
-    1, std::min(BM * BN * 4 * kKGroups<KIND, NW> / NW <= 64 * 64 ? 4 : BM * BN * 4 * kKGroups<KIND, NW> / NW <= 128 * 64 ? 3 : 2,
-                (160 * 1024) / (kKGroups<KIND, NW> * kLdsBytes<BM, BN, STAGES, KIND, NW>) * NW / 4));
-
 // NW waves per workgroup in an (NW / 2) x 2 grid over the tile: wave (wm, wn)
 // owns rows [wm * BM / (NW / 2), ...) x columns [wn * BN / 2, ...).
 // The workgroup body: problem `a`, split-K slice `kslice`, linear tile `lin`.
@@ -237,36 +116,15 @@ constexpr int kMinWaves = std::max(
 // gemm_kernel_pair selects one of two problems at run time.
 template <int MODE, int BM, int BN, int STAGES, int KIND, int NWA>
 __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, const int lin, const int hl) {
-  constexpr bool CONV = KIND != kDense;
-  constexpr bool TAP = KIND == kConvTap;
-  constexpr bool HALO = kIsHalo<KIND>;
-  constexpr bool WIN = KIND == kConvTapW;
-  constexpr bool AR = !HALO && !WIN;  // A tiles go through the ring
-  static_assert(!WIN || ((BM == 64 || BM == 128) && BN == 64 && STAGES == 3),
-                "window kind: 64 / 128 x 64 tiles, 3 W stages");
-  static_assert(NWA == 4 || NWA == 8, "4- or 8-wave workgroups");
-  // KG K groups of NW waves: everything below is one group's (its waves, threads, LDS)
-  constexpr int KG = kKGroups<KIND, NWA>;
-  constexpr int NW = NWA / KG;
-  static_assert(NW == 4 || NW == 8, "waves per K group");
-  constexpr int NT = 64 * NW;  // threads per K group
+  // the instance's numbers (gemm_tile.hpp).  KG K groups of NW waves: everything below is one
+  // group's (its waves, threads, LDS)
+  using G = TileGeo<MODE, BM, BN, STAGES, KIND, NWA>;
+  constexpr bool CONV = G::CONV, TAP = G::TAP, HALO = G::HALO, WIN = G::WIN, AR = G::AR, RPF = G::RPF, LNF = G::LNF;
+  constexpr int KG = G::KG, NW = G::NW, NT = G::NT, ESTEP = G::ESTEP, EPC = G::EPC, RB = G::RB, CPR = G::CPR, RPI = G::RPI;
+  constexpr int IMG = G::IMG, AQ = G::AQ, BQ = G::BQ, QPS = G::QPS, HQ = G::HQ, HBUF = G::HBUF, XQ = G::XQ, LDSB = G::LDSB;
+  constexpr int WTM = G::WTM, WTN = G::WTN, TI = G::TI, TJ = G::TJ;
   using TR = Traits<MODE>;
   using AT = typename TR::A;
-  constexpr int ESTEP = TR::ESTEP, EPC = TR::EPC, RB = TR::RB;
-  constexpr int CPR = RB / 16;             // chunks per image row
-  constexpr int RPI = 64 / CPR;            // image rows per 1-KiB DMA instruction
-  constexpr int IMG = (AR ? BM + BN : BN) * RB;  // bytes per ring stage (halo, window: W only)
-  constexpr int AQ = BM / RPI / NW, BQ = BN / RPI / NW;  // DMA instructions per wave per step
-  static_assert(!AR || AQ * RPI * NW == BM, "A image rows per wave");
-  static_assert(BQ * RPI * NW == BN, "W image rows per wave");
-  constexpr int QPS = (AR ? AQ : 0) + BQ;
-  constexpr int HQ = HALO ? kHaloHQ<BM, KIND, NW> : 1;  // halo DMA instructions per wave per block
-  constexpr int HBUF = HALO ? HQ * NW * RPI * RB : WIN ? kWinRows<BM> * RB : 0;  // bytes per halo / window buffer
-  constexpr int XQ = BM / 32 + 1;  // window kind: DMA pieces per wave per window
-  constexpr int LDSB = kLdsBytes<BM, BN, STAGES, KIND, NW>;
-  static_assert(LDSB == STAGES * IMG + 2 * HBUF + kLnBytes<BM, KIND> + 16, "LDS layout");
-  static_assert(!WIN || RB == 128, "window rows are 128-byte pixel blocks");
-  static_assert(!HALO || (STAGES >= 3 && STAGES <= 6 && RPI == 8), "halo: 9 taps, the next halo at tap 10 - STAGES");
   __shared__ __attribute__((aligned(16))) char lds_wg[KG * LDSB];
   // K group (an SGPR) and its LDS: [0, LDSB) for group 0, [LDSB, 2 LDSB) for group 1
   const int grp = KG == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x / NT);
@@ -418,10 +276,9 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
   // oy0 - 1 + hy); stacked bands read virtual row u0 - 1 + hy, i.e. image
   // (u0 - 1 + hy) / period, row (u0 - 1 + hy) % period - 1 (the padding rows of the
   // stacked layout and rows past the last image read zeros).
-  constexpr int WTM_ = BM / (NW / 2);  // rows per wave
   [[maybe_unused]] const AT* h_src[HQ];
   [[maybe_unused]] bool h_ok[HQ];
-  [[maybe_unused]] int h_row[WTM_ / 16];
+  [[maybe_unused]] int h_row[WTM / 16];
   if constexpr (HALO) {
     const int imgs = a.imgs;
 #pragma unroll
@@ -444,8 +301,8 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
                  c * EPC;
     }
 #pragma unroll
-    for (int i = 0; i < WTM_ / 16; ++i) {
-      const int r = (wave >> 1) * WTM_ + i * 16 + (lane & 15);
+    for (int i = 0; i < WTM / 16; ++i) {
+      const int r = (wave >> 1) * WTM + i * 16 + (lane & 15);
       const int ty = fdiv(r, a.fd_ow), tx = r - ty * d.OW;
       h_row[i] = ty < a.h_th ? ty * a.h_hwp + tx : 0;
     }
@@ -607,8 +464,6 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
 
   const int fr = lane & 15, fq = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
-  constexpr int WTM = BM / (NW / 2), WTN = BN / 2;
-  constexpr int TI = WTM / 16, TJ = WTN / 16;
   floatx4 acc[TI][TJ];
 #pragma unroll
   for (int i = 0; i < TI; ++i)
@@ -639,9 +494,6 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
   // fp32 tile in the last step's region ((nsteps - 1) % STAGES), so the two never meet.
   // Split-K tiles prefetch in the reducing slice only, after its ticket.  res_rb: bytes of a
   // residual tile row (64 fp16 = 128, 64 fp32 or split = 256); rpw: DMA pieces per wave.
-  constexpr bool RPF = BM == 64 && BN == 64 && !HALO && NW == 4;
-  // the LayerNorm fold lives in the dense fp16 instances only (the transformer GEMMs)
-  constexpr bool LNF = KIND == kDense && MODE == (int)Prec::F16;
   // (residual planes: a row's 64 hi values, then its 64 lo values)
   [[maybe_unused]] const int res_rb =
       (MODE == kF16X3S || sizeof(typename TR::Out) == 4 || d.res_f32 || d.res_planes) ? 256 : 128;
@@ -699,7 +551,6 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
   // or nullptr (the residual, if any, is read from global memory).
   auto finish = [&](floatx4 (&v)[TI][TJ], int toff, const char* rl) {
     using Out = typename TR::Out;
-    static_assert(BM * BN * 4 <= LDSB - 16, "the C tile must fit the LDS");
     float* T = reinterpret_cast<float*>(lds + toff);
     // the bias row of this thread's column group, in flight across the park
     const int nb_ = n0 + (tid % (BN / 8)) * 8;
@@ -761,7 +612,7 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
     const int cg = tid % G, r0 = tid / G;
     const int nb = n0 + cg * 8;
     // 0 fp16, 1 fp32, 2 split layout, 3 two fp16 planes
-    const int fmt = (kSplitMode<MODE> && d.out_split) ? 2 : d.out_planes ? 3 : d.out_f16 ? 0
+    const int fmt = (split_mode(MODE) && d.out_split) ? 2 : d.out_planes ? 3 : d.out_f16 ? 0
                     : (d.out_f32 || sizeof(Out) == 4) ? 1 : 0;
     // output row of tile row `row`, -1 when it is not stored
     auto row_m = [&](int row) -> int {
@@ -1180,7 +1031,7 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
 #else
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[kk][i], bf[kk][j], acc[i][j], 0, 0, 0);
 #endif
-    } else if constexpr (kSplitMode<MODE>) {
+    } else if constexpr (split_mode(MODE)) {
       static_assert(ESTEP == 32, "one 32-k block per step");
       // fp32 A: two 16-byte chunks split into hi/lo below; split A: hi and lo
       // chunks read like W's (the same conflict-free pattern).
@@ -1273,10 +1124,10 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
     st_issue += st_c - st_b;
     st_comp += st_d - st_c;
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  using I3 = std::integral_constant<int, 3>;
+  using I0 = IC<0>;
+  using I1 = IC<1>;
+  using I2 = IC<2>;
+  using I3 = IC<3>;
   if constexpr (HALO) {
     // one channel block per iteration, its 9 taps unrolled (3 stages: stage =
     // tap % 3, a constant; deeper rings: a scalar stage counter)
@@ -1288,6 +1139,8 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
       hw_blk_next = h_b0 + j + 1;
       hw_buf_next = (j + 1) & 1;
       const int t = j * 9;
+      // (written out: driven by static_for<0, 9>, hipcc allocates the two fp32 halo kernels differently,
+      // 160 -> 140 and 154 -> 134 VGPRs, ~40 instructions fewer each -- kept byte-identical instead)
       if constexpr (STAGES == 3) {
         kstep(t + 0, I0{}, std::integral_constant<int, 0>{}, lb, Hs, std::false_type{});
         kstep(t + 1, I1{}, std::integral_constant<int, 1>{}, lb, Hs, std::false_type{});
@@ -1394,7 +1247,7 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
 #pragma unroll
         for (int j = 0; j < TJ; ++j) part[(i * TJ + j) * NT + tid] = acc[i][j];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
     if (grp == 1) return;
 #pragma unroll
     for (int i = 0; i < TI; ++i)
@@ -1433,7 +1286,7 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
       const int off = (kslice * SLAB + ((i * TJ + j) * NT + tid) * 4) * 4;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[i][j]), rs, off, 0, 16);
     }
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+  dma_wait_barrier<0>();  // the slab stores are vector memory too
   if (tid == 0) {
     const int ticket = __hip_atomic_fetch_add(words, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int last = ticket == splits - 1;
@@ -1506,18 +1359,9 @@ __global__ __launch_bounds__(64 * NW, (kMinWaves<BM, BN, STAGES, KIND, NW>)) voi
   }
 }
 
-// The planner (gemm_plan.cpp, host only) sizes k-steps and halo bands by its own copies of these
-static_assert(Traits<(int)Prec::F16>::ESTEP == estep_of(Prec::F16) && Traits<(int)Prec::F32>::ESTEP == estep_of(Prec::F32) &&
-              Traits<(int)Prec::F16X3>::ESTEP == estep_of(Prec::F16X3), "gemm_plan.hpp: k-values per step");
-static_assert(kHaloHQ<64, kConvHaloS, 4> * 4 * 8 == kHaloPixelsSmall && kHaloHQ<64, kConvHalo, 4> * 4 * 8 == kHaloPixels64 &&
-              kHaloHQ<128, kConvHalo, 4> * 4 * 8 == kHaloPixels128 && kHaloHQ<256, kConvHalo, 8> * 8 * 8 == kHaloPixels256,
-              "gemm_plan.hpp: halo buffer capacities");
-
 // The instance table of the ring kinds: the plan's (BM, BN, STAGES) as integral constants.  One
 // problem (launch_tile) and a grouped pair (dispatch_pair) pick their kernel through it, so a
 // grouped launch and its two-launch fallback cannot disagree about the tiles that exist.
-template <int V>
-using IC = std::integral_constant<int, V>;
 template <class F>
 void with_tile(const Plan& pl, F&& f) {
   if (pl.bm == 128 && pl.bn == 128) {
@@ -1570,7 +1414,7 @@ void dispatch(const Plan& pl, const KArgs& g, hipStream_t s) {
     if constexpr (MODE == (int)Prec::F16 || MODE == kF16X3S) {
       if (pl.nw == 8) {
         // K groups: both must walk the same number of super-steps (their barriers pair up)
-        const int ES = Traits<MODE>::ESTEP;
+        const int ES = estep_of(MODE);
         if (pl.bm != 64 || pl.k_per_split % (6 * ES) || g.d.Kpad % (6 * ES))
           throw std::logic_error("window kind with K groups: slices of an even number of super-steps");
         SPI_LAUNCH((gemm_kernel<MODE, 64, 64, 3, kConvTapW, 8>), grid, dim3(512), 0, s, g);

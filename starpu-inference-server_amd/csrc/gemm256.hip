@@ -27,6 +27,7 @@
 // DMA source address (rule 21), conflict-free ds_read_b128 fragment reads.
 #include "device_math.hpp"
 #include "gemm_plan.hpp"
+#include "lds_dma.hpp"
 #include "ln_fold.hpp"
 #include "spi_kernels.hpp"
 
@@ -37,10 +38,6 @@
 
 namespace spi {
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct G256Args {
   const _Float16* A;
@@ -73,7 +70,6 @@ struct G256Args {
   size_t plane;  // RES = 3: residual and output in two fp16 planes, lo `plane` elements after hi
 };
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kMaxSplits = 4;     // split-K slices (gemm256_splits, gemm_plan.cpp)
 static_assert(kMaxSplits == kG256MaxSplits, "gemm_plan.hpp: the planner's slice cap is the reduction's");
 // diagnostic build -DSPI_G256_EPI_CALLS: leave the epilogue instances to the inliner (A/B)

@@ -84,17 +84,9 @@ struct KGroup {
   int wgs0;
 };
 
-// The kernel's modes: a Prec, or F16X3 whose A (and residual) are stored split
-// (GemmDesc::a_split; kernel-internal, see Traits<> in gemm.hip).
-constexpr int kF16X3S = 3;
+// The kernel's modes (gemm_tile.hpp): a Prec, or kF16X3S for F16X3 with split activations.
 constexpr Prec prec_of_mode(int mode) { return mode == kF16X3S ? Prec::F16X3 : (Prec)mode; }
 constexpr int mode_of(Prec prec, bool a_split) { return prec == Prec::F16X3 && a_split ? kF16X3S : (int)prec; }
-
-// Split-K is compiled into the 64x64 and 128x64 tiles and the halo kinds (no plan
-// rule splits 128x128; the reducer costs 36-120 VGPRs there).
-constexpr bool split_k_compiled(int bm, int bn, bool halo) {
-  return (bm == 64 && bn == 64) || (bm == 128 && bn == 64) || halo;
-}
 
 // XCD-aware order.  The hardware deals dispatch indices round-robin to the 8 XCDs, so idx & 7
 // names the XCD: number each XCD's workgroups consecutively (bijective, chunks of q or q + 1).

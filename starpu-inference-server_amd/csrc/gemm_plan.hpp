@@ -6,15 +6,17 @@
 #include <cstddef>
 
 #include "gemm_desc.hpp"
+#include "gemm_tile.hpp"
 
 namespace spi {
 
-// Kernel constants the planner sizes by; gemm.hip static_asserts them against Traits<> / kHaloHQ<>.
+// Kernel constants the planner sizes by, from the kernel's own geometry (gemm_tile.hpp).
 // k-values per staged step:
-constexpr int estep_of(Prec prec) { return prec == Prec::F16 ? 64 : 32; }
-// halo buffer capacity in pixels (DMA instructions per wave x waves x 8 pixels) of the 64-row
-// kinds (kConvHaloS, kConvHalo), the 128-row kind and the 8-wave 256-row kind:
-constexpr int kHaloPixelsSmall = 3 * 4 * 8, kHaloPixels64 = 4 * 4 * 8, kHaloPixels128 = 8 * 4 * 8, kHaloPixels256 = 6 * 8 * 8;
+constexpr int estep_of(Prec prec) { return estep_of((int)prec); }
+// halo buffer capacity in pixels of the 64-row kinds (kConvHaloS, kConvHalo), the 128-row kind and
+// the 8-wave 256-row kind:
+constexpr int kHaloPixelsSmall = kHaloPixels<64, kConvHaloS, 4>, kHaloPixels64 = kHaloPixels<64, kConvHalo, 4>,
+              kHaloPixels128 = kHaloPixels<128, kConvHalo, 4>, kHaloPixels256 = kHaloPixels<256, kConvHalo, 8>;
 // gemm256 split-K: at most this many slices (its reduction holds one accumulator set per slice)
 constexpr int kG256MaxSplits = 4;
 // gemm256's LayerNorm consumer fold (ln_load / ln_combine) reads the chunk statistics in pairs,

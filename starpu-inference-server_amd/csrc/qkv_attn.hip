@@ -19,6 +19,7 @@
 // Replaces the QKV GEMM launch, the Q / K / V round trip through HBM (B S 3 D fp16 written and
 // read back) and the attention launch's own staging.  Same arithmetic as the unfused pair
 // (fp16 Q / K / V, fp32 scores and softmax, fp16 P), DESIGN.md 3.7.
+#include "lds_dma.hpp"
 #include "ln_fold.hpp"
 #include "spi_kernels.hpp"
 
@@ -28,12 +29,8 @@
 namespace spi {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) short4v lds_s4;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 constexpr int HD = 64;                      // head dim
 constexpr int QC = 3 * HD;                  // q | k | v columns of one head

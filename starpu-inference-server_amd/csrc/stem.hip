@@ -37,6 +37,7 @@
 // and are discarded (MFMA rows are independent).  max commutes with the monotone
 // fp16 rounding, so pooling the fp32 values and rounding once is what pooling
 // the rounded stem outputs gives.
+#include "lds_dma.hpp"
 #include "pack.hpp"
 #include "spi_kernels.hpp"
 
@@ -47,9 +48,6 @@
 namespace spi {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kCout = 64;

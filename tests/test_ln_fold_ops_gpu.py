@@ -368,6 +368,67 @@ def test_producer_gemm256_split_k(ops, ws, gemm256_everywhere, out_form, res_for
 
 
 # ---------------------------------------------------------------------------------------------
+# c': the general kernel's residual and output forms without a fold, on both store paths: the vector
+# path (tiles inside N, 16-byte aligned rows; 64 x 64 tiles prefetch the residual tile into LDS, taller
+# ones load it from global memory) and the per-element path (tiles crossing N, unaligned strides)
+
+PLAIN_FORMS = [
+    # M, N, K, output, residual, ldc, ldr, tile rows
+    (100, 72, 64, "planes", "inplace", None, None, 64),   # per element: two planes over two planes
+    (65, 72, 128, "fp16", "fp32", None, None, 64),        # per element: fp16 over an fp32 residual
+    (100, 72, 64, "fp16", "fp16", None, None, 64),        # per element: fp16 over fp16
+    (65, 128, 64, "f32", "fp16", 132, None, 64),          # per element by an unaligned ldc
+    (65, 128, 64, "planes", "fp32", None, 130, 64),       # per element by an unaligned ldr
+    (65, 128, 64, "fp16", "fp32", None, None, 64),        # vector, prefetched: fp32 rows under an fp16 output
+    (65, 128, 64, "fp16", "fp16", None, None, 64),        # vector, prefetched: fp16 rows
+    (300, 3072, 64, "planes", "inplace", None, None, 128),  # vector, two-plane residual from global memory
+]
+
+
+@pytest.mark.parametrize("M,N,K,out_form,res_form,ldc,ldr,bm", PLAIN_FORMS)
+def test_plain_forms_both_store_paths(ops, ws, M, N, K, out_form, res_form, ldc, ldr, bm):
+    Wp, W16, b, b_d = plain_linear(ops, N, K)
+    rng = np.random.default_rng(M * 23 + N + K)
+    A16 = (rng.standard_normal((M, K)) * 1.5).astype(np.float16)
+    R = make_rows(rng, M, N)
+    acc = A16.astype(np.float64) @ W16.T + b
+    ldc, ldr = ldc or N, ldr or N
+    flags = {"f32": OUT_F32_F, "planes": OUT_PLANES_F, "fp16": 0}[out_form] | \
+        {"fp32": RES_F32_F, "fp16": 0, "inplace": RES_PLANES_F}[res_form]
+    plan = (C.c_longlong * 14)()
+    assert ops.lib.spi_debug_gemm_plan(1, M, N, K, K, 1, 0, C.c_uint(flags), plan) == 0
+    what = f"plain {M}x{N}x{K} out {out_form} ldc {ldc} res {res_form} ldr {ldr}"
+    assert (int(plan[0]), int(plan[4]), int(plan[7])) == (0, bm, 1), f"{what}: routing {list(plan)}"
+    kw = dict(bias=b_d, ldc=ldc, ldr=ldr, ws=ws)
+    pv = None
+    if out_form == "planes":
+        C_d, pv, plane = planes_buf(ops, M, N, R if res_form == "inplace" else None)
+        kw.update(plane=plane)
+    else:
+        C_d = guarded(M, ldc, dtype=torch.float32 if out_form == "f32" else torch.float16)
+    if res_form == "inplace":
+        ref = acc + planes64(pv, M)
+        kw.update(residual=C_d, res_kind="planes")
+    else:
+        Rs = R.astype(np.float32 if res_form == "fp32" else np.float16)
+        ref = acc + Rs.astype(np.float64)
+        Rd = guarded(M, ldr, dtype=torch.from_numpy(Rs).dtype)  # NaN past N: a read there shows
+        Rd[:M, :N] = torch.from_numpy(Rs).cuda()
+        kw.update(residual=Rd, res_kind=res_form)
+    ops.gemm_ln(torch.from_numpy(A16).cuda(), Wp, N, C_d, {"f32": "fp32"}.get(out_form, out_form), M=M, **kw)
+    if out_form == "planes":
+        assert_guard(pv[0], M, "hi plane")
+        assert_guard(pv[1], M, "lo plane")
+        check_planes(pv, M, ref, what)
+        return
+    assert_guard(C_d, M, "C")
+    assert bool(torch.isnan(C_d[:M, N:]).all()), f"{what}: columns past N were written"
+    e = nerr(C_d[:M, :N].float().cpu().numpy(), ref)
+    print(f"{what}: {e:.3e}")
+    assert e < (TOL32 if out_form == "f32" else TOL16), f"{what}: {e:.3e}"
+
+
+# ---------------------------------------------------------------------------------------------
 # d: the post-LN residual  C = A W^T + b + LN(R) g + beta  (BERT's out-proj / FFN2)
 
 
