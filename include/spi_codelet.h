@@ -229,7 +229,14 @@ void spi_args_init(spi_codelet_args* args);
  * ------------------------------------------------------------------------- */
 enum spi_family {
   SPI_FAMILY_AUTO = 0,   /* recognise from parameter names */
-  SPI_FAMILY_RESNET = 1, /* torchvision resnet18/34/50/101/152 naming */
+  /* torchvision ResNet naming: resnet18/34/50/101/152, wide_resnet50_2/101_2 and the grouped
+   * resnext50_32x4d / resnext101_32x8d.  A grouped conv is accepted as the bottleneck conv2 only, with one
+   * group count on every block, widths that are multiples of 128 and 4, 8, 16, 32 or 64 channels per group;
+   * anything else fails with "grouped/unsupported conv".  SPI_PREC_F16 / F16M run it on the grouped kernel;
+   * SPI_PREC_F32 / F16X3 (and SPI_GCONV=0 at replica build) pack its dense block-diagonal expansion for
+   * the dense kernels: same results at their parity bar, 32x the conv's MFMA work and weight bytes
+   * (resnext101_32x8d: 170 MiB grouped in fp16, 801 MiB expanded, twice that in fp32). */
+  SPI_FAMILY_RESNET = 1,
   SPI_FAMILY_BERT = 2,   /* HF BertModel naming, returns last_hidden_state */
   SPI_FAMILY_VIT = 3,    /* torchvision vit_*_16 naming */
   SPI_FAMILY_AFFINE = 4  /* y = x * scale + shift (toy models of the reference tests) */

@@ -102,6 +102,39 @@ int spi_op_conv_pair(int32_t precision, const void* x, int32_t B, int32_t H, int
                      const spi_op_conv_spec* c0, const spi_op_conv_spec* c1, void* workspace, void* stream,
                      int64_t* plan_out);
 
+/* ---- Grouped 3x3 conv (conv_group.hip; a ResNeXt bottleneck's conv2), fp16 ----
+ * x [B][H][W][C] fp16 NHWC -> y [B][OH][OW][C] fp16 = act(conv(x) + bias), OH = (H - 1) / stride + 1 (OW
+ * alike): Cin == Cout == C in `groups` groups of cpg = C / groups channels, group g reading and writing
+ * channels [g cpg, (g + 1) cpg); 3x3, pad 1 (padding taps contribute zero), stride 1 or 2; bias fp32 [C] or
+ * null; act 0 none, 1 relu; fp32 accumulation; no residual, no workspace.
+ * Supported: C a multiple of 128, groups >= 2, cpg 4, 8, 16, 32 or 64.
+ *
+ * Packed layout (spi_op_gconv_pack_weight of the torch-order weight [C][cpg][3][3]): fp16
+ * [C / 16][steps][64][8].  A wave owns 16 output channels n0 .. n0 + 15 and contracts them in `steps`
+ * mfma_f32_16x16x32_f16 with the weights as the A operand; entry [tile][s][l][j] is the weight of output
+ * channel 16 tile + (l & 15) at k-element 8 (l >> 4) + j of step s, q = l >> 4:
+ *   cpg <= 16 (5 steps): tap 2 s + (q >> 1), input channel n0 + 8 (q & 1) + j -- two taps of the tile's own
+ *     16 channels; an input channel of another group than the row's is stored as zero, and so is tap 9;
+ *   cpg 32 (9 steps): tap s, input channel 32 (n0 / 32) + 8 q + j;
+ *   cpg 64 (18 steps): tap s >> 1, input channel 64 (n0 / 64) + 32 (s & 1) + 8 q + j;
+ * tap = kh 3 + kw.
+ *
+ * A consequence of the zero-packed off-group weights (cpg 4 and 8; cpg 16 shares nothing): groups of one
+ * 16-channel slice share MFMAs, so a non-finite activation (inf, NaN) in one group reaches the other
+ * groups of that slice as 0 inf = NaN, where PyTorch keeps it inside its group.  Finite values never leak:
+ * their products with the zeros are exact zeros, and the other groups' outputs keep their bits.
+ *
+ * Rejected before any launch, with a message in spi_last_error(): C not a multiple of 128; cpg outside the
+ * five values or groups < 2; a kernel other than 3x3 with pad 1; a stride other than 1 or 2; null x,
+ * W_packed or y; B, H or W <= 0; x, y, W_packed (or a non-null bias) off 16-byte alignment; act other
+ * than 0 / 1.  spi_op_gconv_packed_bytes returns 0 for an unsupported shape. */
+size_t spi_op_gconv_packed_bytes(int32_t C, int32_t groups, int32_t KH, int32_t KW);
+int spi_op_gconv_pack_weight(const float* w_host /* [C][C/groups][KH][KW], torch order */, int32_t C,
+                             int32_t groups, int32_t KH, int32_t KW, void* dst_host);
+int spi_op_conv2d_grouped(const void* x, int32_t B, int32_t H, int32_t W, int32_t C, const void* W_packed,
+                          int32_t groups, int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* bias,
+                          void* y, int32_t act, void* stream);
+
 /* Fused global average pool + linear layer (ResNet avgpool + fc in one launch):
  * x [B][HW][C] (fp32 / fp16 / split by precision, HW <= 64), W packed from the
  * [N][C] fc weight; y fp32 [B][N] = act(mean_hw(x) . W^T + bias). */

@@ -2,6 +2,7 @@
 // helpers; forward plans for ResNet (basic / bottleneck), BERT (post-LN) and ViT (pre-LN).
 // Reference counterparts: the per-device clones (src/core/inference_runner.cpp:251-275) and the
 // forward that LibTorch runs inside the codelet (src/core/starpu_setup.cpp:610).
+#include "gconv.hpp"
 #include "gemm_plan.hpp"
 #include "model.hpp"
 
@@ -157,8 +158,8 @@ int Model::set_input_transform(const float* scale, const float* shift) {
 
 double Model::flops(int64_t B) const {
   double f = 0;
-  auto conv_f = [&](const ConvW& c, int OH, int OW) {
-    return 2.0 * B * OH * OW * c.cout * (double)c.kh * c.kw * c.cin;
+  auto conv_f = [&](const ConvW& c, int OH, int OW) {  // a grouped conv: its own FLOPs on either route
+    return 2.0 * B * OH * OW * c.cout * (double)c.kh * c.kw * (c.cin / c.groups);
   };
   if (m_.family == SPI_FAMILY_RESNET) {
     int H = (m_.image + 2 * 3 - 7) / 2 + 1;
@@ -275,6 +276,23 @@ void Model::run_conv(const ConvW& c, const void* x, int B, int H, int W, void* y
   const ConvCall k = conv_call(c, x, B, H, W, y, OH, OW, act, res, ws, out_f32, res_f32);
   require_fit(k.d, k.prec, ws);
   prof_op(s, [&] { return conv_name(c, k.d.M); }, k.flops, k.bytes, [&] { gemm(k.d, k.p, k.prec, s); });
+}
+
+// A grouped conv packed for the grouped kernel (ConvW::gconv; conv_group.hip): no GEMM plan, no
+// split-K workspace.  flops: the conv's own (1 / groups of the dense count).
+void Model::run_gconv(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW, Act act,
+                      hipStream_t s) {
+  OH = (H + 2 * c.pad - c.kh) / c.stride + 1;
+  OW = (W + 2 * c.pad - c.kw) / c.stride + 1;
+  const int M = B * OH * OW;
+  prof_op(s,
+          [&] {
+            return "gconv3x3_c" + std::to_string(c.cout) + "_g" + std::to_string(c.groups) + "_s" +
+                   std::to_string(c.stride) + "_M" + std::to_string(M);
+          },
+          2.0 * M * c.cout * 9.0 * (c.cin / c.groups),
+          ((double)B * H * W * c.cin + (double)M * c.cout) * 2 + (double)gconv_packed_bytes(c.cout, c.groups),
+          [&] { conv_group(x, ptr<void>(c.w), ptr<float>(c.b), y, B, H, W, c.cout, c.groups, c.stride, act == Act::Relu, s); });
 }
 
 // A block's first conv and its downsample conv read the same input: one grouped
@@ -403,8 +421,12 @@ std::vector<size_t> Model::workspace_sizes_resnet(size_t& partial) const {
   size_t amax = 0;
   // a conv over an h x h input: its split-K slabs, and its output among the activation slots
   auto conv = [&](const ConvW& c, int h, bool stored = true) {
-    partial = std::max(partial, conv_partial(c, B, h, h));
-    conv_desc(c, B, h, h, OH, OW);
+    if (c.gconv) {  // the grouped kernel: no plan, no slabs
+      OH = (h + 2 * c.pad - c.kh) / c.stride + 1;
+    } else {
+      partial = std::max(partial, conv_partial(c, B, h, h));
+      conv_desc(c, B, h, h, OH, OW);
+    }
     if (stored) amax = std::max(amax, (size_t)B * OH * OH * c.cout);
     return OH;
   };
@@ -556,7 +578,10 @@ void Model::body_resnet(Workspace& w, int B, hipStream_t s) {
     H2 = H1;
     if (m_.bottleneck) {  // conv1 is 1x1 / stride 1 (H1 == H); conv2 carries the stride
       const int t2 = pick({cur, last, ident});
-      run_conv(b.c2, buf[last], B, H1, H1, buf[t2], H2, OW, Act::Relu, nullptr, w, s);
+      if (b.c2.gconv)
+        run_gconv(b.c2, buf[last], B, H1, H1, buf[t2], H2, OW, Act::Relu, s);
+      else
+        run_conv(b.c2, buf[last], B, H1, H1, buf[t2], H2, OW, Act::Relu, nullptr, w, s);
       last = t2;
     }
     const int o = pick({cur, last, ident});

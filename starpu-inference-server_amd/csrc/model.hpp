@@ -133,6 +133,8 @@ class Model {
   void run_conv(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW,
                 Act act, const void* res, Workspace& ws, hipStream_t s, bool out_f32 = false,
                 bool res_f32 = false);
+  void run_gconv(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW, Act act,
+                 hipStream_t s);
   struct ConvCall {  // the op's name (conv_name) is built only while profiling
     GemmDesc d;
     GemmPtrs p;

@@ -12,6 +12,7 @@
 #include <sstream>
 #include <stdexcept>
 
+#include "gconv.hpp"
 #include "ln_fold_pack.hpp"
 #include "pack.hpp"
 
@@ -170,25 +171,48 @@ struct Packer {
   size_t pack_vec(const float* v, int n) { return blob.add(v, (size_t)n * sizeof(float)); }
 
   // Folded conv weight [Cout][Cin][KH][KW] -> [Npad][Kpad], k = (kh*KW + kw)*cin_pad + c.
-  ConvW pack_conv(const FoldedConv& f, int stride, int cin_pad, Prec prec, bool hilo = false) {
+  // groups > 1: f.cin is the channels per group and the packed matrix the dense block-diagonal
+  // expansion over all groups * f.cin input channels, zero off the row's group.
+  ConvW pack_conv(const FoldedConv& f, int stride, int cin_pad, Prec prec, bool hilo = false, int groups = 1) {
     ConvW c;
     c.cout = f.cout;
-    c.cin = f.cin;
+    c.cin = f.cin * groups;
+    c.groups = groups;
     c.kh = f.kh;
     c.kw = f.kw;
     c.stride = stride;
     c.pad = c.kh / 2;
     c.cin_pad = std::max(cin_pad, c.cin);
     const int K = c.kh * c.kw * c.cin_pad;
-    const int cin = c.cin, kh = c.kh, kw = c.kw, cp = c.cin_pad;
+    const int cin = c.cin, kh = c.kh, kw = c.kw, cp = c.cin_pad, cpg = f.cin, npg = f.cout / groups;
     c.prec = prec;
     pack_weight(c, c.cout, K, hilo, [&](int n, int k) -> float {
       const int cell = k / cp, ci = k % cp;
-      if (ci >= cin) return 0.f;
+      if (ci >= cin || ci / cpg != n / npg) return 0.f;
       const int y = cell / kw, x = cell % kw;
-      return f.w[(((size_t)n * cin + ci) * kh + y) * kw + x];
+      return f.w[(((size_t)n * cpg + ci % cpg) * kh + y) * kw + x];
     });
     c.w_image = !hilo && packed_has_wres_image(prec, c.cout, K, c.npad, c.kpad);
+    c.b = pack_vec(f.b.data(), c.cout);
+    return c;
+  }
+
+  // A grouped 3x3 conv for the grouped kernel (gconv.hpp): fp16, no GEMM geometry.
+  ConvW pack_gconv(const FoldedConv& f, int stride, int groups) {
+    ConvW c;
+    c.cout = f.cout;
+    c.cin = c.cin_pad = f.cin * groups;
+    c.groups = groups;
+    c.gconv = true;
+    c.kh = f.kh;
+    c.kw = f.kw;
+    c.stride = stride;
+    c.pad = 1;
+    c.prec = Prec::F16;
+    c.w = blob.add(nullptr, gconv_packed_bytes(c.cout, groups));
+    const int cpg = f.cin;
+    gconv_pack_into(reinterpret_cast<_Float16*>(blob.data.data() + c.w), c.cout, groups,
+                    [&](int n, int ci, int tap) { return f.w[((size_t)n * cpg + ci) * 9 + tap]; });
     c.b = pack_vec(f.b.data(), c.cout);
     return c;
   }
@@ -267,6 +291,10 @@ void Packer::build_resnet(const PMap& p) {
   const FoldedConv stem_folded = fold_conv(p, "conv1", "bn1", m.eps);
   m.stem = pack_conv(stem_folded, 2, stem_prec == Prec::F16 ? 8 : 4, stem_prec);
   if (m.stem.kh != 7 || m.stem.cin != 3) throw std::runtime_error("resnet stem must be 7x7 over 3 channels");
+  // SPI_GCONV=0: the dense expansion of grouped convs in the fp16 modes too (A/B runs, tests)
+  const char* ge = std::getenv("SPI_GCONV");
+  const bool gconv_on = !(ge && *ge && std::atoi(ge) == 0);
+  std::vector<int> block_groups;  // conv2's groups, per block
   for (int L = 1; L <= 4; ++L) {
     int nb = 0;
     while (has(p, "layer" + std::to_string(L) + "." + std::to_string(nb) + ".conv1.weight")) ++nb;
@@ -277,7 +305,21 @@ void Packer::build_resnet(const PMap& p) {
       const int s = (L > 1 && i == 0) ? 2 : 1;
       ResBlock blk;
       blk.c1 = pack_conv(p, pre, "conv1", "bn1", m.bottleneck ? 1 : s);
-      blk.c2 = pack_conv(p, pre, "conv2", "bn2", m.bottleneck ? s : 1);
+      // A bottleneck's conv2 may be grouped (ResNeXt): weight.shape[1] = C / groups.  Inside the
+      // grouped kernel's set (gconv.hpp) the fp16 modes pack for it and the fp32-grade modes (and
+      // SPI_GCONV=0) the dense expansion; anything else is packed as it stands and fails the
+      // channel chain below.
+      const FoldedConv f2 = fold_conv(p, pre + "conv2", pre + "bn2", m.eps);
+      const int C = blk.c1.cout;
+      int groups = 1;
+      if (m.bottleneck && f2.cin > 0 && f2.cin != C && f2.cout == C && C % f2.cin == 0 && f2.kh == 3 &&
+          f2.kw == 3 && gconv_supported(C, C / f2.cin))
+        groups = C / f2.cin;
+      block_groups.push_back(groups);
+      if (groups > 1 && m.prec == Prec::F16 && gconv_on)
+        blk.c2 = pack_gconv(f2, s, groups);
+      else
+        blk.c2 = pack_conv(f2, m.bottleneck ? s : 1, 0, m.prec, false, groups);
       if (m.bottleneck) blk.c3 = pack_conv(p, pre, "conv3", "bn3", 1);
       blk.has_ds = has(p, pre + "downsample.0.weight");
       if (blk.has_ds) blk.ds = pack_conv(p, pre, "downsample.0", "downsample.1", s, m.mixed);
@@ -311,6 +353,11 @@ void Packer::build_resnet(const PMap& p) {
     ch = out;
   }
   if (m.fc.k != ch) bad(reads("fc", m.fc.k, ch, "features"));
+  m.groups = block_groups.front();
+  for (size_t i = 0; i < block_groups.size(); ++i)
+    if (block_groups[i] != m.groups)
+      bad("block " + std::to_string(i) + " conv2 has " + std::to_string(block_groups[i]) + " groups, block 0 has " +
+          std::to_string(m.groups));
   // Split activations need every activation's channel count to be a multiple
   // of 32 (the split block) and every non-stem conv to read >= 32 channels.
   m.split = m.prec == Prec::F16X3 && m.stem.cout % 32 == 0;
@@ -503,7 +550,9 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     pk.build_resnet(strip_prefix(p, "layer1.0.conv1.weight"));
     os << "resnet" << (m.bottleneck ? "-bottleneck[" : "-basic[");
     for (size_t i = 0; i < m.stage_blocks.size(); ++i) os << (i ? "," : "") << m.stage_blocks[i];
-    os << "] img" << m.image << " classes" << m.classes;
+    os << "]";
+    if (m.groups > 1) os << " g" << m.groups;
+    os << " img" << m.image << " classes" << m.classes;
   } else if (m.family == SPI_FAMILY_BERT) {
     m.eps = cfg.eps > 0 ? cfg.eps : 1e-12f;
     m.ln_fold = ln_fold_enabled(m.prec, kBertLnFold);

@@ -21,6 +21,11 @@ struct ConvW {
   Prec prec = Prec::F16;  // packing / contraction precision of this conv
   int krep = 1;           // 2: hi + lo weight steps per A step (GemmDesc::krep; SPI_PREC_F16M)
   bool w_image = false;   // the packed rows 64..127 hold conv_wres's LDS image (GemmDesc::w_image)
+  // A grouped conv (ResNeXt conv2): cin stays the full channel count, group g reads and writes channels
+  // [g cin / groups, ...).  gconv: w holds the grouped kernel's layout (gconv.hpp; kpad = npad = 0, no
+  // GEMM plan); else w is the dense [cout][kh][kw][cin] expansion with zeros off the group.
+  int groups = 1;
+  bool gconv = false;
 };
 
 struct LinearW {
@@ -62,6 +67,7 @@ struct PackedModel {
   // ResNet
   bool bottleneck = false;
   std::vector<int> stage_blocks;
+  int groups = 1;  // of every bottleneck conv2 (ResNeXt: 32)
   ConvW stem;
   bool stem_fused = false;  // stem + max pool in one launch on the NCHW input (stem.hip)
   size_t stem_pool_w = 0;   // its weights, [hi | lo][64][24][8] fp16

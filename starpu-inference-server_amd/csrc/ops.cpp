@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/spi_ops.h"
+#include "gconv.hpp"
 #include "gemm_plan.hpp"
 #include "ln_fold_pack.hpp"
 #include "pack.hpp"
@@ -251,6 +252,51 @@ int spi_op_conv_pair(int32_t precision, const void* x, int32_t B, int32_t H, int
       plan_out[21] = (int64_t)pp.counter_slots;
     }
     spi::gemm_pair(d[0], ptrs[0], d[1], ptrs[1], p, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+// ---- grouped 3x3 conv (conv_group.hip, gconv.hpp) ----
+
+namespace {
+
+// The part of the supported set that the weights alone decide; null when inside it.
+const char* gconv_shape_error(int32_t C, int32_t groups, int32_t KH, int32_t KW) {
+  if (C <= 0 || C % 128) return "grouped conv: C must be a multiple of 128";
+  if (groups < 2 || C % groups || !spi::gconv_supported(C, groups))
+    return "grouped conv: groups >= 2 with 4, 8, 16, 32 or 64 channels per group";
+  if (KH != 3 || KW != 3) return "grouped conv: the kernel is 3x3 with pad 1";
+  return nullptr;
+}
+
+}  // namespace
+
+size_t spi_op_gconv_packed_bytes(int32_t C, int32_t groups, int32_t KH, int32_t KW) {
+  return gconv_shape_error(C, groups, KH, KW) ? 0 : spi::gconv_packed_bytes(C, groups);
+}
+
+int spi_op_gconv_pack_weight(const float* w, int32_t C, int32_t groups, int32_t KH, int32_t KW, void* dst) {
+  if (!w || !dst) return fail("invalid grouped pack arguments");
+  if (const char* e = gconv_shape_error(C, groups, KH, KW)) return fail(e);
+  const int cpg = C / groups;
+  spi::gconv_pack_into(static_cast<_Float16*>(dst), C, groups,
+                       [&](int n, int c, int tap) { return w[((size_t)n * cpg + c) * 9 + tap]; });
+  return 0;
+}
+
+int spi_op_conv2d_grouped(const void* x, int32_t B, int32_t H, int32_t W, int32_t C, const void* Wp, int32_t groups,
+                          int32_t KH, int32_t KW, int32_t stride, int32_t pad, const float* bias, void* y,
+                          int32_t act, void* stream) {
+  if (!x || !Wp || !y) return fail("grouped conv: null x, W_packed or y");
+  if (B <= 0 || H <= 0 || W <= 0) return fail("grouped conv: B, H and W must be positive");
+  if (const char* e = gconv_shape_error(C, groups, KH, KW)) return fail(e);
+  if (pad != 1) return fail("grouped conv: the kernel is 3x3 with pad 1");
+  if (stride != 1 && stride != 2) return fail("grouped conv: stride 1 or 2");
+  if (act != 0 && act != 1) return fail("grouped conv: act 0 (none) or 1 (relu)");
+  for (const void* p : {x, Wp, static_cast<const void*>(y), static_cast<const void*>(bias)})
+    if (reinterpret_cast<uintptr_t>(p) & 15) return fail("grouped conv: 16-byte aligned x, W_packed, y and bias");
+  return guarded([&] {
+    spi::conv_group(x, Wp, bias, y, B, H, W, C, groups, stride, act == 1, static_cast<hipStream_t>(stream));
     return check_launch();
   });
 }

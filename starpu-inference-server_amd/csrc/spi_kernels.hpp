@@ -67,6 +67,13 @@ void conv_wres_reload_env();
 void attention_reload_env();  // SPI_ATTN_WHOLE
 void qkv_attn_reload_env();   // SPI_QKV_HP
 
+// Grouped 3x3 / pad 1 conv, stride 1 or 2, fp16 NHWC, Cin == Cout == C (conv_group.hip): x [B][H][W][C]
+// -> y [B][OH][OW][C] = act(conv + bias), fp32 accumulation.  w: gconv_packed_bytes() from
+// gconv_pack_into() (gconv.hpp, which also defines the supported C / groups); bias fp32 [C] or null.
+// x, w, y and bias 16-byte aligned.  Throws std::invalid_argument outside the supported set.
+void conv_group(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int groups,
+                int stride, bool relu, hipStream_t s);
+
 // What an image task's input buffer holds (ResNet / ViT).  The kernels that read it -- the fused
 // stem, ingest_nchw, patchify -- take the kind and, for 8-bit pixels, the per-channel input
 // transform: pixel p of channel c enters the network as fl(fl((float)p * scale[c]) + shift[c]),

@@ -176,6 +176,34 @@ def conv_pair(prec, x_nhwc, spec0, spec1, ws, stream=None):
             "counter_slots": v[21]}
 
 
+# ---- grouped 3x3 conv (a ResNeXt bottleneck's conv2; spi_ops.h: spi_op_conv2d_grouped) ----
+
+
+def pack_weight_grouped(w: np.ndarray | torch.Tensor, groups: int, device="cuda") -> torch.Tensor:
+    """torch conv weight [C][C / groups][3][3] fp32 -> the grouped kernel's packed device buffer (uint8 tensor)."""
+    w = np.ascontiguousarray(np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float32))
+    if w.ndim != 4 or groups < 1 or w.shape[0] != w.shape[1] * groups:
+        raise OpError("pack_weight_grouped: a [C][C / groups][KH][KW] weight")
+    c, _, kh, kw = w.shape
+    nbytes = lib.spi_op_gconv_packed_bytes(c, groups, kh, kw)
+    host = np.empty(max(nbytes, 16), dtype=np.uint8)
+    _check(lib.spi_op_gconv_pack_weight(w.ctypes.data, c, groups, kh, kw, host.ctypes.data))
+    return torch.from_numpy(host).to(device)
+
+
+def conv2d_grouped(x_nhwc, W_packed, groups, stride, bias=None, act=None, out=None, k=3, pad=1, stream=None):
+    """Grouped 3x3 / pad 1 conv, fp16 NHWC, Cin == Cout: x [B][H][W][C] -> out [B][OH][OW][C] (default: a
+    fresh tensor); W_packed from pack_weight_grouped, bias fp32 [C] or None, act None / "relu"; act may also
+    be the integer code itself."""
+    B, H, W_, c = x_nhwc.shape
+    if out is None:
+        out = torch.empty(B, (H + 2 * pad - k) // stride + 1, (W_ + 2 * pad - k) // stride + 1, c,
+                          device=x_nhwc.device, dtype=torch.float16)
+    _check(lib.spi_op_conv2d_grouped(_ptr(x_nhwc), B, H, W_, c, _ptr(W_packed), groups, k, k, stride, pad, _ptr(bias),
+                                     _ptr(out), ACT.get(act, act), _stream(stream)))
+    return out
+
+
 def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None, out=None):
     """ctx [B S][64 heads] of packed qkv [B S][3 D]; out: the buffer to write (default: a fresh one).  prec may
     be the integer precision code itself."""

@@ -52,12 +52,13 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: nn.Module | None = None):
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample: nn.Module | None = None,
+                 groups: int = 1, width_per_group: int = 64):
         super().__init__()
-        width = planes
+        width = int(planes * width_per_group / 64) * groups  # torchvision's formula (ResNeXt, wide ResNet)
         self.conv1 = nn.Conv2d(inplanes, width, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = nn.Conv2d(width, width, 3, stride, 1, bias=False)
+        self.conv2 = nn.Conv2d(width, width, 3, stride, 1, groups=groups, bias=False)
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
@@ -76,9 +77,11 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, block, layers: Sequence[int], num_classes: int = 1000, width: int = 64):
+    def __init__(self, block, layers: Sequence[int], num_classes: int = 1000, width: int = 64, groups: int = 1,
+                 width_per_group: int = 64):
         super().__init__()
         self.inplanes = width
+        self.groups, self.width_per_group = groups, width_per_group
         self.conv1 = nn.Conv2d(3, width, 7, 2, 3, bias=False)
         self.bn1 = nn.BatchNorm2d(width)
         self.relu = nn.ReLU(inplace=True)
@@ -99,10 +102,13 @@ class ResNet(nn.Module):
             downsample = nn.Sequential(
                 nn.Conv2d(self.inplanes, planes * block.expansion, 1, stride, bias=False),
                 nn.BatchNorm2d(planes * block.expansion))
-        layers = [block(self.inplanes, planes, stride, downsample)]
+        # bottleneck-only keywords; a BasicBlock net takes neither (torchvision raises too)
+        kw = {} if (self.groups, self.width_per_group) == (1, 64) else dict(
+            groups=self.groups, width_per_group=self.width_per_group)
+        layers = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes, **kw))
         return nn.Sequential(*layers)
 
     def forward(self, x):
@@ -141,9 +147,10 @@ def _randomize_bn_and_calibrate(model: nn.Module, image: int, seed: int, calib_b
 
 
 def resnet(layers: Sequence[int], bottleneck: bool, seed: int = 0, image: int = 224,
-           num_classes: int = 1000, calibrate: bool = True) -> ResNet:
+           num_classes: int = 1000, calibrate: bool = True, groups: int = 1, width_per_group: int = 64) -> ResNet:
     torch.manual_seed(seed)
-    model = ResNet(Bottleneck if bottleneck else BasicBlock, layers, num_classes)
+    model = ResNet(Bottleneck if bottleneck else BasicBlock, layers, num_classes, groups=groups,
+                   width_per_group=width_per_group)
     if calibrate:
         _randomize_bn_and_calibrate(model, image, seed)
     return model.eval()
@@ -155,6 +162,23 @@ def resnet18(seed: int = 0, image: int = 224, **kw) -> ResNet:
 
 def resnet152(seed: int = 0, image: int = 224, **kw) -> ResNet:
     return resnet([3, 8, 36, 3], True, seed, image, **kw)
+
+
+# The grouped and wide variants of the reference's export script (models/import_resnet.py).
+def resnext50_32x4d(seed: int = 0, image: int = 224, **kw) -> ResNet:
+    return resnet([3, 4, 6, 3], True, seed, image, groups=32, width_per_group=4, **kw)
+
+
+def resnext101_32x8d(seed: int = 0, image: int = 224, **kw) -> ResNet:
+    return resnet([3, 4, 23, 3], True, seed, image, groups=32, width_per_group=8, **kw)
+
+
+def wide_resnet50_2(seed: int = 0, image: int = 224, **kw) -> ResNet:
+    return resnet([3, 4, 6, 3], True, seed, image, width_per_group=128, **kw)
+
+
+def wide_resnet101_2(seed: int = 0, image: int = 224, **kw) -> ResNet:
+    return resnet([3, 4, 23, 3], True, seed, image, width_per_group=128, **kw)
 
 
 # ---------------------------------------------------------------------------
@@ -320,6 +344,10 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
     table = {
         "resnet18": resnet18,
         "resnet152": resnet152,
+        "resnext50_32x4d": resnext50_32x4d,
+        "resnext101_32x8d": resnext101_32x8d,
+        "wide_resnet50_2": wide_resnet50_2,
+        "wide_resnet101_2": wide_resnet101_2,
         "vit_l_16": vit_l_16,
         "bert-base-uncased": bert_base,
         "bert_base": bert_base,

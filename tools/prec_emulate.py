@@ -76,7 +76,7 @@ class Emu:
             w = r16(w)
         if cls not in self.p["a32"] and not ex:
             x = r16(x)
-        y = F.conv2d(x, w, b, conv.stride, conv.padding)
+        y = F.conv2d(x, w, b, conv.stride, conv.padding, groups=conv.groups)
         if res is not None:
             y = y + res
         if relu:
@@ -121,7 +121,7 @@ class Emu:
             w = r16(w)
         if lcls not in self.p["a32"] and not ex:
             o = r16(o)
-        y = F.relu(F.conv2d(o, w, b, last.stride, last.padding) + ident)
+        y = F.relu(F.conv2d(o, w, b, last.stride, last.padding, groups=last.groups) + ident)
         return y if self.p["s32"] or ex else r16(y)
 
 
