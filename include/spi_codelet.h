@@ -357,6 +357,37 @@ int64_t spi_model_launch_table(spi_model* model, void* stream, int64_t batch, in
  * The measurement hooks above (spi_model_profile, _profile_op, _launch_table) carry no
  * element type and always read fp32 NCHW inputs. */
 int spi_model_set_input_transform(spi_model* model, const float scale[3], const float shift[3]);
+/* Classification outputs of a ResNet / ViT replica: what it hands back beside, or instead of, its
+ * [B,classes] fp32 logits.  One more kernel launch after the classifier layer writes every selected
+ * output of the batch; with nothing selected (image_io 0, the default) the replica is unchanged.
+ *
+ * Outputs, always in this order: the logits [B,classes] fp32 (unless SPI_IMAGE_NO_LOGITS), the
+ * probabilities [B,classes] fp32 (SPI_IMAGE_OUT_PROBS), then with SPI_IMAGE_OUT_TOPK the top-k values
+ * [B,top_k] fp32 and the top-k indices [B,top_k] SPI_DTYPE_I64 (what torch.topk / torch.sort return).
+ *   probabilities  p[j] = exp(x[j] - max_j x) / sum_j exp(x[j] - max_j x) in fp32, summed in one fixed
+ *                  order without atomics: the same bits from run to run.  -inf logits give
+ *                  probability 0; +inf or NaN logits give unspecified results.
+ *   top-k          the row's top_k entries by logit, descending; equal logits by ascending class index,
+ *                  0.0 == -0.0: torch.sort(x, descending=True, stable=True).  The order is always the
+ *                  logits', so the indices do not depend on SPI_IMAGE_TOPK_PROBS.  The values are the
+ *                  logits' own bits at those indices; with SPI_IMAGE_TOPK_PROBS, the bits the
+ *                  probability output holds (or would hold) there.
+ * Refused, with a message in spi_last_error(): unknown bits; a replica of another family
+ * (SPI_ERR_UNSUPPORTED); SPI_IMAGE_NO_LOGITS with neither other output; SPI_IMAGE_TOPK_PROBS without
+ * SPI_IMAGE_OUT_TOPK; top_k outside 1 .. min(classes, 64) with SPI_IMAGE_OUT_TOPK, or non-zero without;
+ * more than 16384 classes; and any call once a stream workspace of the replica exists (after the first
+ * forward or warm-up: the logits scratch of a SPI_IMAGE_NO_LOGITS replica, max_batch x classes x 4
+ * bytes, belongs to the workspace).  (0, 0) before that point resets to the one-output contract.
+ * The measurement hooks read `outputs` in the order above; spi_model_describe appends
+ * " out[logits,probs,top5]" (the selected names) when bits are set.  FLOPs, weight bytes and the digest
+ * do not change. */
+enum spi_image_io {
+  SPI_IMAGE_OUT_PROBS = 1,  /* softmax(logits) [B,classes] fp32 */
+  SPI_IMAGE_OUT_TOPK = 2,   /* top-k values [B,k] fp32 and indices [B,k] int64 */
+  SPI_IMAGE_NO_LOGITS = 4,  /* the logits are not an output */
+  SPI_IMAGE_TOPK_PROBS = 8  /* top-k values are probabilities, not logits */
+};
+int spi_model_set_image_outputs(spi_model* model, int32_t image_io, int32_t top_k);
 /* Capture launch-bound forwards into hipGraphs (per stream, per batch). */
 void spi_model_set_graphs(spi_model* model, int32_t enable);
 /* Per-worker warm-up (inference_runner.cpp:507-560): allocate `stream`'s

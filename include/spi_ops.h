@@ -312,6 +312,19 @@ int spi_op_mask_to_bias(const int64_t* mask, float* bias, int32_t n, void* strea
 int spi_op_vit_assemble(const float* patches, const float* cls, const float* pos, float* x, int32_t B, int32_t P,
                         int32_t D, void* stream);
 
+/* ---- Classification outputs (classify.hip); fp32, deterministic (no atomics), one launch ---- */
+
+/* Softmax and / or top-k of fp32 logits rows.
+ * x fp32 [B] rows of N, ldx floats apart (ldx >= N). probs fp32 [B][N] or null; topv fp32 [B][k] and
+ * topi int64 [B][k] both or neither; topk_probs: topv holds probabilities. 1 <= N <= 16384, 1 <= k <= min(N, 64).
+ * probs[b][j] = exp(x[b][j] - max_j x[b]) / sum_j exp(x[b][j] - max_j x[b]).  Top-k: the row's k best by
+ * logit descending, equal logits (0.0 == -0.0) by index ascending, as torch.sort(descending=True,
+ * stable=True); topv carries the logits' own bits, or with topk_probs the bits probs holds (or would
+ * hold) at those indices.  Without topv / topi, k and topk_probs must be 0.  -inf logits give probability
+ * 0; +inf or NaN logits give unspecified results.  Everything is validated before any launch. */
+int spi_op_softmax_topk(const float* x, int64_t ldx, float* probs, float* topv, int64_t* topi,
+                        int32_t B, int32_t N, int32_t k, int32_t topk_probs, void* stream);
+
 /* y[i] = x[i stride_rows] for i < rows: rows of D fp32 -> fp16 when out_f16, else fp32. */
 int spi_op_gather_rows(const float* x, void* y, int32_t rows, int32_t stride_rows, int32_t D, int32_t out_f16,
                        void* stream);

@@ -60,6 +60,17 @@ int spi_torch_cpu_forward(void* model_cpu, const spi_tensor_view* inputs, int nu
  * SPI_ERR_INVALID_ARGUMENT (non-finite value, a single NULL).  Set it before serving. */
 int spi_torch_set_input_transform(spi_torch_module* module, const float scale[3], const float shift[3]);
 
+/* Classification outputs on a CPU worker (the counterpart of spi_model_set_image_outputs, same bits,
+ * same output order and element types): after the module's forward, whose single output is the
+ * [B,classes] logits, spi_torch_cpu_forward emits logits.float() (unless SPI_IMAGE_NO_LOGITS),
+ * softmax(logits.float(), -1), and the first top_k values / int64 indices of the stable descending sort
+ * of the logits (values gathered from the probabilities with SPI_IMAGE_TOPK_PROBS), through the same
+ * checked copy.  Refused (SPI_ERR_INVALID_ARGUMENT): unknown bits; SPI_IMAGE_NO_LOGITS with neither
+ * other output; SPI_IMAGE_TOPK_PROBS without SPI_IMAGE_OUT_TOPK; top_k outside 1 .. 64 with
+ * SPI_IMAGE_OUT_TOPK, or non-zero without.  The class count is known at the forward only: a task whose
+ * logits have fewer than top_k or more than 16384 classes fails there.  (0, 0) resets. */
+int spi_torch_set_image_outputs(spi_torch_module* module, int32_t image_io, int32_t top_k);
+
 /* Floating named_parameters() then named_buffers() (first occurrence of a name
  * wins), each copied to contiguous fp32 and owned by the module handle.
  * Returns the count, or -1 on error. */

@@ -8,13 +8,13 @@ from . import _native
 from ._native import lib
 from .codelet import (InferenceCodelet, InferenceExecutionException, InferenceParams, ModelReplica,
                       StarPUCodeletException, TorchCpuForward, buffer_array, buffer_byte_size,
-                      clone_model_to_gpus, load_model, make_params, make_variable_interface,
-                      make_vector_interface, named_tensors, run_hip, select_gpu_module, tensor_interface,
+                      clone_model_to_gpus, image_io_bits, load_model, make_params, make_variable_interface,
+                      make_vector_interface, named_tensors, output_specs, run_hip, select_gpu_module, tensor_interface,
                       worker_context)
 
 __all__ = [
     "_native", "lib", "InferenceCodelet", "InferenceExecutionException", "InferenceParams", "ModelReplica",
     "StarPUCodeletException", "TorchCpuForward", "buffer_array", "buffer_byte_size", "clone_model_to_gpus",
-    "load_model", "make_params", "make_variable_interface", "make_vector_interface", "named_tensors",
-    "run_hip", "select_gpu_module", "tensor_interface", "worker_context",
+    "image_io_bits", "load_model", "make_params", "make_variable_interface", "make_vector_interface", "named_tensors",
+    "output_specs", "run_hip", "select_gpu_module", "tensor_interface", "worker_context",
 ]

@@ -160,6 +160,8 @@ class ModelConfig(C.Structure):
 
 # enum spi_bert_io (spi_model_config.bert_io)
 BERT_OUT_POOLER, BERT_OUT_MEAN, BERT_NO_HIDDEN, BERT_TOKEN_TYPES = 1, 2, 4, 8
+# enum spi_image_io (spi_model_set_image_outputs)
+IMAGE_OUT_PROBS, IMAGE_OUT_TOPK, IMAGE_NO_LOGITS, IMAGE_TOPK_PROBS = 1, 2, 4, 8
 
 
 class ConvSpec(C.Structure):
@@ -205,6 +207,7 @@ _PROTOS = {
     "spi_model_describe": (C.c_char_p, [C.c_void_p]),
     "spi_model_set_graphs": (None, [C.c_void_p, C.c_int32]),
     "spi_model_set_input_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "spi_model_set_image_outputs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "spi_model_warmup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
     "spi_model_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(C.c_double),
@@ -298,6 +301,8 @@ _PROTOS = {
                                      C.c_void_p]),
     "spi_op_masked_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_void_p]),
+    "spi_op_softmax_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_void_p]),
     "spi_op_mask_to_bias": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "spi_op_vit_assemble": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                       C.c_int32, C.c_void_p]),

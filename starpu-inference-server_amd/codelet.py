@@ -147,6 +147,76 @@ def bert_io_bits(bert_io) -> int:
     return bits
 
 
+IMAGE_IO = {"probs": N.IMAGE_OUT_PROBS, "topk": N.IMAGE_OUT_TOPK, "no_logits": N.IMAGE_NO_LOGITS,
+            "topk_probs": N.IMAGE_TOPK_PROBS}
+
+
+def image_io_bits(image_io) -> int:
+    """spi_model_set_image_outputs' bits from an int, one name or several: ("probs", "topk", "no_logits", "topk_probs")."""
+    if image_io is None:
+        return 0
+    if isinstance(image_io, int):
+        return image_io
+    names = [image_io] if isinstance(image_io, str) else list(image_io)
+    bits = 0
+    for name in names:
+        if name not in IMAGE_IO:
+            raise InferenceExecutionException(f"unknown image_io name {name!r}; known: {sorted(IMAGE_IO)}")
+        bits |= IMAGE_IO[name]
+    return bits
+
+
+def output_specs(batch: int, classes: int = 0, image_io=0, top_k: int = 0, seq: int = 0, dim: int = 0,
+                 bert_io=0) -> list[tuple[tuple, torch.dtype]]:
+    """(shape, dtype) of each output buffer of a replica's task, in the replica's output order.
+    ResNet / ViT (classes): logits, probabilities, top-k values, top-k indices (int64) as image_io selects.
+    BERT (seq, dim): hidden, pooler, mean as bert_io selects."""
+    f32 = torch.float32
+    if dim:
+        io = bert_io_bits(bert_io)
+        specs = [] if io & N.BERT_NO_HIDDEN else [((batch, seq, dim), f32)]
+        return specs + [((batch, dim), f32)] * (bool(io & N.BERT_OUT_POOLER) + bool(io & N.BERT_OUT_MEAN))
+    io = image_io_bits(image_io)
+    specs = [] if io & N.IMAGE_NO_LOGITS else [((batch, classes), f32)]
+    if io & N.IMAGE_OUT_PROBS:
+        specs.append(((batch, classes), f32))
+    if io & N.IMAGE_OUT_TOPK:
+        specs += [((batch, top_k), f32), ((batch, top_k), torch.int64)]
+    return specs
+
+
+def _image_outputs(logits: torch.Tensor, io: int, top_k: int) -> list:
+    """The CPU codelets' classification outputs from [B,classes] logits (spi_model_set_image_outputs' contract)."""
+    if logits.dim() != 2:
+        raise InferenceExecutionException("image outputs: the module must return one [B,classes] tensor")
+    logits = logits.float().contiguous()
+    if logits.shape[1] > 16384:
+        raise InferenceExecutionException("image outputs: more than 16384 classes")
+    if top_k > logits.shape[1]:
+        raise InferenceExecutionException("image outputs: top_k exceeds the class count")
+    outs = [] if io & N.IMAGE_NO_LOGITS else [logits]
+    probs = torch.softmax(logits, -1) if io & (N.IMAGE_OUT_PROBS | N.IMAGE_TOPK_PROBS) else None
+    if io & N.IMAGE_OUT_PROBS:
+        outs.append(probs)
+    if io & N.IMAGE_OUT_TOPK:
+        idx = torch.sort(logits, dim=-1, descending=True, stable=True).indices[:, :top_k].contiguous()
+        outs += [(probs if io & N.IMAGE_TOPK_PROBS else logits).gather(1, idx).contiguous(), idx]
+    return outs
+
+
+def check_image_outputs(io: int, top_k: int) -> None:
+    """The refusals of spi_model_set_image_outputs that need no replica (the CPU codelets' rules)."""
+    known = N.IMAGE_OUT_PROBS | N.IMAGE_OUT_TOPK | N.IMAGE_NO_LOGITS | N.IMAGE_TOPK_PROBS
+    if io & ~known:
+        raise InferenceExecutionException(f"image outputs: unknown bits {io & ~known}")
+    if io & N.IMAGE_NO_LOGITS and not io & (N.IMAGE_OUT_PROBS | N.IMAGE_OUT_TOPK):
+        raise InferenceExecutionException("image outputs: SPI_IMAGE_NO_LOGITS leaves no output")
+    if io & N.IMAGE_TOPK_PROBS and not io & N.IMAGE_OUT_TOPK:
+        raise InferenceExecutionException("image outputs: SPI_IMAGE_TOPK_PROBS needs SPI_IMAGE_OUT_TOPK")
+    if (not 1 <= top_k <= 64) if io & N.IMAGE_OUT_TOPK else top_k != 0:
+        raise InferenceExecutionException(f"image outputs: top_k {top_k} outside 1 .. 64, or set without SPI_IMAGE_OUT_TOPK")
+
+
 def _pointer_array(tensors, at_least: int = 1) -> C.Array:
     """void*[]: device pointers, null-padded to at_least entries (a BERT replica's optional inputs)."""
     ptrs = [t.data_ptr() for t in tensors]
@@ -163,14 +233,15 @@ class ModelReplica:
     def __init__(self, module: torch.nn.Module | str | None, device_id: int = 0, precision: str = "fp16",
                  max_batch: int = 8, family: str | None = None, num_heads: int = 0, seq_len: int = 0,
                  image_size: int = 0, eps: float = 0.0, affine: tuple[float, float] = (1.0, 0.0),
-                 graphs: bool = False, bert_io=0):
+                 graphs: bool = False, bert_io=0, image_io=0, top_k: int = 0):
         if isinstance(module, str):
             # The reference's on-disk format: torch::jit::load + the C++ weight
             # extractor in libspi_torch.so (inference_runner.cpp:243-275).
             from .libtorch import TorchScriptModule
             ts = TorchScriptModule(module)
             rep = ts.replica(device_id, precision, max_batch, family=family, num_heads=num_heads, seq_len=seq_len,
-                             image_size=image_size, eps=eps, graphs=graphs, bert_io=bert_io)
+                             image_size=image_size, eps=eps, graphs=graphs, bert_io=bert_io, image_io=image_io,
+                             top_k=top_k)
             self.__dict__.update(rep.__dict__)
             rep.handle = None  # ownership moved to self
             return
@@ -206,18 +277,24 @@ class ModelReplica:
         self.precision = precision
         self.max_batch = max_batch
         self.bert_io = cfg.bert_io
+        self.image_io, self.top_k = 0, 0
+        if image_io_bits(image_io) or top_k:
+            self.set_image_outputs(image_io, top_k)
         if graphs:
             self.set_graphs(True)
 
     @classmethod
     def from_handle(cls, handle: int, device_id: int, precision: str, max_batch: int,
-                    graphs: bool = False, bert_io: int = 0) -> "ModelReplica":
+                    graphs: bool = False, bert_io: int = 0, image_io=0, top_k: int = 0) -> "ModelReplica":
         self = cls.__new__(cls)
         self.handle = C.c_void_p(handle)
         self.device_id = device_id
         self.precision = precision
         self.max_batch = max_batch
         self.bert_io = bert_io
+        self.image_io, self.top_k = 0, 0
+        if image_io_bits(image_io) or top_k:
+            self.set_image_outputs(image_io, top_k)
         if graphs:
             self.set_graphs(True)
         return self
@@ -232,6 +309,18 @@ class ModelReplica:
         st = lib.spi_model_set_input_transform(self.handle, N.float3(scale), N.float3(shift))
         if st != N.SPI_OK:
             raise InferenceExecutionException(f"set_input_transform failed: {N.last_error()}")
+
+    def set_image_outputs(self, image_io=0, top_k: int = 0) -> None:
+        """The classification outputs of a ResNet / ViT replica (spi_model_set_image_outputs): image_io as
+        image_io_bits takes it, top_k with "topk".  Output order: logits (unless "no_logits"), probabilities,
+        top-k values, top-k indices (int64).  Only before the first forward or warm-up; (0, 0) resets."""
+        bits = image_io_bits(image_io)
+        st = lib.spi_model_set_image_outputs(self.handle, bits, int(top_k))
+        if st != N.SPI_OK:
+            e = InferenceExecutionException(f"set_image_outputs failed: {N.last_error()}")
+            e.status = st
+            raise e
+        self.image_io, self.top_k = bits, int(top_k)
 
     def warmup(self, stream: int, batch: int, seq: int = 0, with_mask: bool = True) -> None:
         """Allocate `stream`'s workspace and pre-capture its (batch, seq) graph (per-worker warm-up)."""
@@ -364,11 +453,21 @@ class TorchCpuForward:
     (spi_model_set_input_transform).  When input 0 is a 4-D uint8 view, [B,3,H,W] or [B,H,W,3],
     the module is fed the contiguous fp32 NCHW tensor x.float().mul(scale[c]).add(shift[c]).
     Without it the byte tensor goes to the module unchanged.
+
+    image_outputs=(bits, k): the classification outputs of the GPU codelet (spi_model_set_image_outputs),
+    bits as image_io_bits takes them.  The module's [B,classes] logits become, in order: logits.float()
+    (unless "no_logits"), softmax(logits.float(), -1), and the first k values / int64 indices of the stable
+    descending sort (values taken from the probabilities with "topk_probs").
     """
 
-    def __init__(self, module: torch.nn.Module, input_transform=None):
+    def __init__(self, module: torch.nn.Module, input_transform=None, image_outputs=None):
         self.module = module
         self.input_transform = None
+        self.image_io, self.top_k = 0, 0
+        if image_outputs is not None:
+            io, top_k = image_io_bits(image_outputs[0]), int(image_outputs[1])
+            check_image_outputs(io, top_k)
+            self.image_io, self.top_k = io, top_k
         if input_transform is not None:
             scale, shift = (torch.tensor([float(v) for v in t], dtype=torch.float32).reshape(1, 3, 1, 1)
                             for t in input_transform)
@@ -394,6 +493,11 @@ class TorchCpuForward:
                 result = self.module(*xs)
             outs: list = []
             _append_ivalue(result, outs)
+            if self.image_io:
+                if len(outs) != 1:
+                    raise InferenceExecutionException("image outputs: the module must return one [B,classes] tensor")
+                with torch.inference_mode():
+                    outs = _image_outputs(outs[0], self.image_io, self.top_k)
             if len(outs) != n_out:
                 raise InferenceExecutionException("Mismatch between model outputs and StarPU buffers")
             for i in range(n_out):
@@ -531,7 +635,8 @@ class InferenceCodelet:
 def run_hip(replica: ModelReplica, inputs: Sequence[torch.Tensor], out, stream: int | None = None,
             device_id: int | None = None, worker_id: int = 0, sync: bool = True) -> N.CodeletArgs:
     """Convenience: one codelet call over device tensors on `stream`.  `out`: the output tensor, or
-    the list of output tensors of a BERT replica with bert_io outputs (hidden, pooler, mean order)."""
+    the list of output tensors of a BERT replica with bert_io outputs (hidden, pooler, mean order) or of an
+    image replica with image_io outputs (logits, probabilities, top-k values, int64 top-k indices; output_specs)."""
     outs = _as_list(out)
     dev = replica.device_id if device_id is None else device_id
     if stream is None:

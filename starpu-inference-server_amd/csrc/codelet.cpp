@@ -415,6 +415,14 @@ int spi_model_set_input_transform(spi_model* m, const float scale[3], const floa
   return st;
 }
 
+int spi_model_set_image_outputs(spi_model* m, int32_t image_io, int32_t top_k) {
+  if (!m) return SPI_ERR_INVALID_ARGUMENT;
+  std::string err;
+  const int st = m->impl->set_image_outputs(image_io, top_k, err);
+  if (st != SPI_OK) tl_last_error = err;
+  return st;
+}
+
 int spi_model_warmup(spi_model* m, void* stream, int64_t batch, int64_t seq, int32_t with_mask) {
   if (!m) return SPI_ERR_INVALID_ARGUMENT;
   try {

@@ -24,7 +24,8 @@ std::mutex g_capture_mu;
 // ResNet: the padded NHWC image (unfused stem only); five activation slots the blocks rotate through
 // (0: the unfused stem's output, 1: the max pool's output = the first block's input); the
 // average-pooled features (when avgpool + FC do not run as one GEMM).
-enum RnBuf { kRnIngest, kRnAct0, kRnAct1, kRnAct2, kRnAct3, kRnAct4, kRnPooled, kRnBufs };
+// The logits scratch (here and for ViT): fp32 [max_batch][classes] under SPI_IMAGE_NO_LOGITS, else empty.
+enum RnBuf { kRnIngest, kRnAct0, kRnAct1, kRnAct2, kRnAct3, kRnAct4, kRnPooled, kRnLogits, kRnBufs };
 // BERT: hidden rows fp32 (fold: the pre-LN2 rows b as two fp16 planes) and their compute-type copy;
 // qkv; ctx; the attention block's output a, fp32 (fold: the pre-LN1 rows as two planes); the FFN
 // hidden rows; the LayerNorm-fold row statistics S1 (of a) and S2 (of b); the final LayerNorm's
@@ -32,7 +33,7 @@ enum RnBuf { kRnIngest, kRnAct0, kRnAct1, kRnAct2, kRnAct3, kRnAct4, kRnPooled, 
 enum BertBuf { kBtHidden, kBtHidden16, kBtQkv, kBtCtx, kBtAttn, kBtFfn, kBtStats1, kBtStats2, kBtCls, kBtBufs };
 // ViT: patches; projected patches f32; residual stream x f32 (fold: two fp16 planes); LN output; qkv;
 // ctx; mlp hidden; the LayerNorm'd class-token rows; the LayerNorm-fold row statistics of x.
-enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, kVtStats, kVtBufs };
+enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, kVtStats, kVtLogits, kVtBufs };
 
 // ---------------------------------------------------------------------------
 // Workspace: activation buffers for one stream at max_batch.
@@ -97,7 +98,8 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
     return e;
   };
   size_t expect_out = 0;
-  size_t expect_more[2] = {0, 0};  // BERT: the outputs after the first (bert_io)
+  size_t expect_more[3] = {0, 0, 0};  // the outputs after the first (BERT: bert_io; ResNet / ViT: image_io_)
+  int i64_out = -1;                   // the output that is SPI_DTYPE_I64 (the top-k indices), if any
   if (m_.family == SPI_FAMILY_AFFINE) {
     if (a.input_types[0] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Input type mismatch");
     if (in_bytes[0] < (size_t)elems(0) * 4) throw std::runtime_error("[ERROR] Input buffer too small");
@@ -113,6 +115,19 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
                                (u8 ? " or [B," + sz + "," + sz + ",3]" : ""));
     if (in_bytes[0] < (size_t)elems(0) * (u8 ? 1 : 4)) throw std::runtime_error("[ERROR] Input buffer too small");
     expect_out = (size_t)B * m_.classes * 4;
+    if (image_io_) {  // logits (unless NO_LOGITS), probabilities, top-k values, top-k indices
+      size_t want[4];
+      int n = 0;
+      if (!(image_io_ & SPI_IMAGE_NO_LOGITS)) want[n++] = expect_out;
+      if (image_io_ & SPI_IMAGE_OUT_PROBS) want[n++] = expect_out;
+      if (image_io_ & SPI_IMAGE_OUT_TOPK) {
+        want[n++] = (size_t)B * top_k_ * 4;
+        i64_out = n;
+        want[n++] = (size_t)B * top_k_ * 8;
+      }
+      expect_out = want[0];
+      for (int i = 1; i < n; ++i) expect_more[i - 1] = want[i];
+    }
   } else {  // BERT: input_ids [B,S] int64, optional attention_mask and (bert_io) token_type_ids, [B,S] int64
     for (int i = 0; i < ni; ++i) {
       if (a.input_types[i] != SPI_DTYPE_I64) throw std::runtime_error("[ERROR] Input type mismatch");
@@ -128,7 +143,8 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
     expect_more[0] = expect_more[1] = (size_t)B * m_.D * 4;
   }
   for (int i = 0; i < no; ++i) {
-    if (a.output_types[i] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Output type mismatch");
+    if (a.output_types[i] != (i == i64_out ? SPI_DTYPE_I64 : SPI_DTYPE_F32))
+      throw std::runtime_error("[ERROR] Output type mismatch");
     if (out_bytes[i] != (i == 0 ? expect_out : expect_more[i - 1]))
       throw std::runtime_error("Output buffer size mismatch in bytes");
   }
@@ -153,6 +169,49 @@ int Model::set_input_transform(const float* scale, const float* shift) {
     }
   }
   input_xf_ = xf;
+  return SPI_OK;
+}
+
+int Model::set_image_outputs(int io, int top_k, std::string& err) {
+  constexpr int known = SPI_IMAGE_OUT_PROBS | SPI_IMAGE_OUT_TOPK | SPI_IMAGE_NO_LOGITS | SPI_IMAGE_TOPK_PROBS;
+  auto refuse = [&](int status, const std::string& msg) {
+    err = "image outputs: " + msg;
+    return status;
+  };
+  if (m_.family != SPI_FAMILY_RESNET && m_.family != SPI_FAMILY_VIT)
+    return refuse(SPI_ERR_UNSUPPORTED, "only ResNet / ViT replicas have classification outputs");
+  if (io & ~known) return refuse(SPI_ERR_INVALID_ARGUMENT, "unknown bits " + std::to_string(io & ~known));
+  if ((io & SPI_IMAGE_NO_LOGITS) && !(io & (SPI_IMAGE_OUT_PROBS | SPI_IMAGE_OUT_TOPK)))
+    return refuse(SPI_ERR_INVALID_ARGUMENT,
+                  "SPI_IMAGE_NO_LOGITS leaves no output; select SPI_IMAGE_OUT_PROBS or SPI_IMAGE_OUT_TOPK");
+  if ((io & SPI_IMAGE_TOPK_PROBS) && !(io & SPI_IMAGE_OUT_TOPK))
+    return refuse(SPI_ERR_INVALID_ARGUMENT, "SPI_IMAGE_TOPK_PROBS needs SPI_IMAGE_OUT_TOPK");
+  if (io & SPI_IMAGE_OUT_TOPK) {
+    const int kmax = std::min(m_.classes, kSoftmaxTopkMaxK);
+    if (top_k < 1 || top_k > kmax)
+      return refuse(SPI_ERR_INVALID_ARGUMENT,
+                    "top_k " + std::to_string(top_k) + " outside 1 .. min(classes, 64) = " + std::to_string(kmax));
+  } else if (top_k != 0) {
+    return refuse(SPI_ERR_INVALID_ARGUMENT, "top_k " + std::to_string(top_k) + " without SPI_IMAGE_OUT_TOPK");
+  }
+  if (io && m_.classes > kSoftmaxTopkMaxN)
+    return refuse(SPI_ERR_UNSUPPORTED, std::to_string(m_.classes) + " classes; at most " +
+                                           std::to_string(kSoftmaxTopkMaxN) + " (the row is staged in LDS as fp32)");
+  std::lock_guard<std::mutex> lk(mu_);
+  if (!ws_.empty())
+    return refuse(SPI_ERR_INVALID_ARGUMENT,
+                  "a stream workspace of the replica exists; call before the first forward or warm-up");
+  image_io_ = io;
+  top_k_ = top_k;
+  desc_io_.clear();
+  if (io) {
+    std::string outs;
+    for (const auto& o : {std::make_pair(!(io & SPI_IMAGE_NO_LOGITS), std::string("logits")),
+                          std::make_pair((io & SPI_IMAGE_OUT_PROBS) != 0, std::string("probs")),
+                          std::make_pair((io & SPI_IMAGE_OUT_TOPK) != 0, "top" + std::to_string(top_k))})
+      if (o.first) outs += (outs.empty() ? "" : ",") + o.second;
+    desc_io_ = m_.desc + " out[" + outs + "]";
+  }
   return SPI_OK;
 }
 
@@ -449,6 +508,7 @@ std::vector<size_t> Model::workspace_sizes_resnet(size_t& partial) const {
   const size_t ea = m_.mixed ? 4 : m_.f16 ? 2 : 4;
   for (int i = kRnAct0; i <= kRnAct4; ++i) sz[i] = amax * ea;
   sz[kRnPooled] = (size_t)B * m_.feat * ea;  // fp32 under F16M: the FC's A
+  sz[kRnLogits] = (image_io_ & SPI_IMAGE_NO_LOGITS) ? (size_t)B * m_.classes * 4 : 0;
   return sz;
 }
 
@@ -479,6 +539,7 @@ std::vector<size_t> Model::workspace_sizes_vit(size_t& partial) const {
   sz[kVtMlp] = T * m_.ffn * es;
   sz[kVtCls] = B * D * es;
   sz[kVtStats] = T * (D / 64) * 8;
+  sz[kVtLogits] = (image_io_ & SPI_IMAGE_NO_LOGITS) ? B * m_.classes * 4 : 0;
   partial = std::max({partial, linear_partial(m_.patch_proj, (int)B * m_.npatch), layers_partial((int)T),
                       linear_partial(m_.head, (int)B)});
   return sz;
@@ -829,16 +890,43 @@ void Model::body(Workspace& w, int B, int S, hipStream_t s) {
   }
 }
 
+// ResNet / ViT: the classifier layer writes the logits (into the task's first output, or the workspace
+// scratch under SPI_IMAGE_NO_LOGITS); with image_io_ set one more launch derives the other outputs.
 void Model::epilogue(Workspace& w, int B, int S, void* const* out, hipStream_t s) {
   switch (m_.family) {
-    case SPI_FAMILY_RESNET:
-      if (pooled_fc(w.final_hw)) return run_pooled_fc(w.bufs[w.final_buf], B, w.final_hw, out[0], w, s);
-      return run_gemm(m_.fc, w.bufs[kRnPooled], B, m_.feat, out[0], m_.classes, true, Act::None, nullptr, false, 0, w,
-                      s);
+    case SPI_FAMILY_RESNET: {
+      float* logits = logits_dst(w.bufs[kRnLogits], out);
+      if (pooled_fc(w.final_hw))
+        run_pooled_fc(w.bufs[w.final_buf], B, w.final_hw, logits, w, s);
+      else
+        run_gemm(m_.fc, w.bufs[kRnPooled], B, m_.feat, logits, m_.classes, true, Act::None, nullptr, false, 0, w, s);
+      return run_image_outputs(logits, B, out, s);
+    }
     case SPI_FAMILY_BERT: return epilogue_bert(w, B, S, out, s);
-    case SPI_FAMILY_VIT:
-      return run_gemm(m_.head, w.bufs[kVtCls], B, m_.D, out[0], m_.classes, true, Act::None, nullptr, false, 0, w, s);
+    case SPI_FAMILY_VIT: {
+      float* logits = logits_dst(w.bufs[kVtLogits], out);
+      run_gemm(m_.head, w.bufs[kVtCls], B, m_.D, logits, m_.classes, true, Act::None, nullptr, false, 0, w, s);
+      return run_image_outputs(logits, B, out, s);
+    }
   }
+}
+
+// The outputs image_io_ selects beside the logits, in the order probabilities, top-k values, top-k
+// indices: one launch (classify.hip), none with only the logits selected.
+void Model::run_image_outputs(const float* logits, int B, void* const* out, hipStream_t s) {
+  const int io = image_io_, N = m_.classes, k = top_k_;
+  if (!(io & (SPI_IMAGE_OUT_PROBS | SPI_IMAGE_OUT_TOPK))) return;
+  int o = (io & SPI_IMAGE_NO_LOGITS) ? 0 : 1;
+  float* probs = (io & SPI_IMAGE_OUT_PROBS) ? static_cast<float*>(out[o++]) : nullptr;
+  float* topv = nullptr;
+  int64_t* topi = nullptr;
+  if (io & SPI_IMAGE_OUT_TOPK) {
+    topv = static_cast<float*>(out[o++]);
+    topi = static_cast<int64_t*>(out[o++]);
+  }
+  prof_op(s, "softmax_topk", 0, (double)B * N * 4 * (probs ? 2 : 1) + (double)B * k * 12, [&] {
+    softmax_topk(logits, (size_t)N, probs, topv, topi, B, N, k, (io & SPI_IMAGE_TOPK_PROBS) != 0, s);
+  });
 }
 
 void Model::forward(hipStream_t s, int B, int S, size_t n, const void* const* in, void* const* out, int src) {

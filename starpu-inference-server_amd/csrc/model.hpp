@@ -46,7 +46,7 @@ class Model {
   int max_batch() const { return m_.max_batch; }
   size_t weight_bytes() const { return m_.blob_bytes; }
   uint64_t weight_digest() const { return m_.digest; }
-  const std::string& describe() const { return m_.desc; }
+  const std::string& describe() const { return image_io_ ? desc_io_ : m_.desc; }
   double flops(int64_t batch) const;
   void set_graphs(bool on) { graphs_ = on; }
 
@@ -60,6 +60,10 @@ class Model {
   // The input transform of 8-bit image tasks (spi_model_set_input_transform); null pointers reset
   // it to scale 1, shift 0.  Returns an spi_status.  Not synchronised with forwards in flight.
   int set_input_transform(const float* scale, const float* shift);
+  // The classification outputs of a ResNet / ViT replica (spi_model_set_image_outputs): SPI_IMAGE_* bits
+  // and the top-k count.  Returns an spi_status and, on refusal, the message in `err`.  Refused once a
+  // stream workspace exists: the logits scratch of SPI_IMAGE_NO_LOGITS is sized with the workspace.
+  int set_image_outputs(int image_io, int top_k, std::string& err);
   // Enqueue the forward on `s`; never synchronises.
   // S: BERT sequence length (ignored otherwise); n: AFFINE element count; src: input 0's SrcKind
   // (read by the prologue only -- the captured body does not depend on it).
@@ -90,8 +94,11 @@ class Model {
   int num_inputs_max() const {
     return m_.family != SPI_FAMILY_BERT ? 1 : (m_.bert_io & SPI_BERT_TOKEN_TYPES) ? 3 : 2;
   }
-  // BERT: the outputs bert_io selects, in order hidden, pooler, mean
+  // BERT: the outputs bert_io selects, in order hidden, pooler, mean.  ResNet / ViT: the outputs
+  // image_io_ selects, in order logits, probabilities, top-k values, top-k indices.
   int num_outputs() const {
+    if (image_io_)
+      return !(image_io_ & SPI_IMAGE_NO_LOGITS) + !!(image_io_ & SPI_IMAGE_OUT_PROBS) + 2 * !!(image_io_ & SPI_IMAGE_OUT_TOPK);
     if (m_.family != SPI_FAMILY_BERT) return 1;
     return !(m_.bert_io & SPI_BERT_NO_HIDDEN) + !!(m_.bert_io & SPI_BERT_OUT_POOLER) + !!(m_.bert_io & SPI_BERT_OUT_MEAN);
   }
@@ -114,6 +121,12 @@ class Model {
   void body_vit(Workspace& w, int B, hipStream_t s);
   void body_vit_folded(Workspace& w, int B, hipStream_t s);
   void epilogue_bert(Workspace& w, int B, int S, void* const* out, hipStream_t s);
+  // ResNet / ViT with image_io_: where the classifier writes its logits (the first output, or the
+  // workspace scratch under SPI_IMAGE_NO_LOGITS), and the launch that derives the other outputs from them
+  float* logits_dst(void* scratch, void* const* out) const {
+    return static_cast<float*>((image_io_ & SPI_IMAGE_NO_LOGITS) ? scratch : out[0]);
+  }
+  void run_image_outputs(const float* logits, int B, void* const* out, hipStream_t s);
   // The LayerNorm fold of one transformer GEMM (ln_fold.hpp).
   struct LnSpec {
     const float* in_stats = nullptr;  // A rows are pre-LN: their chunk statistics (L.c1 folded in)
@@ -165,6 +178,8 @@ class Model {
   void* dblob_ = nullptr;
   int stem_pr_ = SPI_STEM_PR;  // the fused stem's workgroup shape (0 = auto, stem.hip)
   InputXf input_xf_;  // ResNet / ViT: the transform of 8-bit image tasks, passed to the prologue's kernel
+  int image_io_ = 0, top_k_ = 0;  // ResNet / ViT: SPI_IMAGE_* bits and the top-k count (set_image_outputs)
+  std::string desc_io_;           // m_.desc + " out[...]" while image_io_ is set
   // SPI_QKV_ATTN: 0 the QKV GEMM + attention launches (A/B); 1 (default) the fused kernel for S <= 128;
   // 2 also for 129..256 tokens (ViT-L at 197: correct, but -4 % under the four streams)
   int qkv_fused_ = 1;

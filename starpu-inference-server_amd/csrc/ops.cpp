@@ -632,6 +632,23 @@ int spi_op_masked_mean(const float* h, const int64_t* mask, float* y, int32_t B,
   });
 }
 
+int spi_op_softmax_topk(const float* x, int64_t ldx, float* probs, float* topv, int64_t* topi, int32_t B, int32_t N,
+                        int32_t k, int32_t topk_probs, void* stream) {
+  if (!x) return fail("softmax_topk: x is null");
+  if (!probs && !topv && !topi) return fail("softmax_topk: no output selected");
+  if ((topv == nullptr) != (topi == nullptr))
+    return fail("softmax_topk: top-k values and indices come both or neither");
+  if (B < 1) return fail("softmax_topk: B >= 1");
+  if (N < 1 || N > spi::kSoftmaxTopkMaxN) return fail("softmax_topk: 1 <= N <= 16384");
+  if (ldx < N) return fail("softmax_topk: ldx >= N");
+  if (topv && (k < 1 || k > spi::kSoftmaxTopkMaxK || k > N)) return fail("softmax_topk: 1 <= k <= min(N, 64)");
+  if (!topv && (k != 0 || topk_probs != 0)) return fail("softmax_topk: k and topk_probs need the top-k outputs");
+  return guarded([&] {
+    spi::softmax_topk(x, (size_t)ldx, probs, topv, topi, B, N, k, topk_probs != 0, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
 int spi_op_mask_to_bias(const int64_t* mask, float* bias, int32_t n, void* stream) {
   if (!mask || !bias || n <= 0) return fail("invalid mask_to_bias arguments");
   return guarded([&] {

@@ -147,6 +147,16 @@ void bert_pooler(const float* h, size_t ld, const float* W, const float* bias, f
 // Masked mean: y[b] = sum_s m[b][s] h[b][s] / max(sum_s m[b][s], 1e-9), m = (mask != 0); a null mask
 // counts every token.  h [B][S][D], y [B][D].
 void masked_mean(const float* h, const int64_t* mask, float* y, int B, int S, int D, hipStream_t s);
+// Classification outputs (classify.hip): softmax and / or top-k of B fp32 logits rows of N, ldx floats
+// apart, in one launch.  probs fp32 [B][N] or null: exp(x - max) / sum, fixed summation order.  topv fp32
+// [B][k] and topi int64 [B][k], both or neither: the row's k best by logit descending, equal logits
+// (0.0 == -0.0) by index ascending; topv holds the logits' own bits, or with topk_probs the bits probs
+// holds (or would hold) there.  1 <= N <= kSoftmaxTopkMaxN, 1 <= k <= min(N, kSoftmaxTopkMaxK) (0 without
+// top-k).  -inf logits give probability 0; +inf / NaN logits give unspecified results.  Throws
+// std::invalid_argument before any launch.
+constexpr int kSoftmaxTopkMaxN = 16384, kSoftmaxTopkMaxK = 64;
+void softmax_topk(const float* x, size_t ldx, float* probs, float* topv, int64_t* topi, int B, int N, int k,
+                  bool topk_probs, hipStream_t s);
 // int64 attention mask [B,S] -> additive fp32 bias [B,S] (0 or finfo.min).
 void mask_to_bias(const int64_t* mask, float* bias, int n, hipStream_t s);
 // ViT: image (NCHW fp32, or 8-bit pixels of kind src, C = 3) -> patch rows [B*P, C*ps*ps] (compute type).

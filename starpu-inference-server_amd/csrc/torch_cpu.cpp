@@ -35,6 +35,8 @@ struct spi_torch_module {
   // spi_torch_set_input_transform: 8-bit image inputs are fed as the transformed fp32 NCHW tensor
   bool xf_set = false;
   float xf_scale[3] = {1.f, 1.f, 1.f}, xf_shift[3] = {0.f, 0.f, 0.f};
+  // spi_torch_set_image_outputs: SPI_IMAGE_* bits and the top-k count
+  int32_t image_io = 0, top_k = 0;
 };
 
 namespace {
@@ -150,6 +152,27 @@ int spi_torch_cpu_forward(void* model_cpu, const spi_tensor_view* inputs, int ni
     const c10::IValue result = m->module.forward(args);
     std::vector<at::Tensor> outs;
     append_ivalue(result, outs);
+    if (m->image_io) {
+      // spi_torch_set_image_outputs: logits, probabilities, top-k values, top-k indices, in that order
+      if (outs.size() != 1 || outs[0].dim() != 2)
+        throw std::runtime_error("image outputs: the module must return one [B,classes] tensor");
+      const at::Tensor logits = outs[0].to(at::kFloat).contiguous();
+      const int64_t classes = logits.size(1);
+      if (classes > 16384) throw std::runtime_error("image outputs: more than 16384 classes");
+      if (m->top_k > classes) throw std::runtime_error("image outputs: top_k exceeds the class count");
+      outs.clear();
+      if (!(m->image_io & SPI_IMAGE_NO_LOGITS)) outs.push_back(logits);
+      at::Tensor probs;
+      if (m->image_io & (SPI_IMAGE_OUT_PROBS | SPI_IMAGE_TOPK_PROBS)) probs = at::softmax(logits, -1);
+      if (m->image_io & SPI_IMAGE_OUT_PROBS) outs.push_back(probs);
+      if (m->image_io & SPI_IMAGE_OUT_TOPK) {
+        const auto sorted = at::sort(logits, /*stable=*/true, /*dim=*/-1, /*descending=*/true);
+        const at::Tensor idx = std::get<1>(sorted).narrow(1, 0, m->top_k).contiguous();
+        const at::Tensor& src = (m->image_io & SPI_IMAGE_TOPK_PROBS) ? probs : logits;
+        outs.push_back(src.gather(1, idx).contiguous());
+        outs.push_back(idx);
+      }
+    }
     if ((int)outs.size() != no) throw std::runtime_error("Mismatch between model outputs and StarPU buffers");
     for (int i = 0; i < no; ++i) {
       const at::Tensor& t = outs[i];
@@ -188,6 +211,17 @@ int spi_torch_set_input_transform(spi_torch_module* m, const float scale[3], con
     m->xf_shift[c] = shift[c];
   }
   m->xf_set = true;
+  return SPI_OK;
+}
+
+int spi_torch_set_image_outputs(spi_torch_module* m, int32_t io, int32_t top_k) {
+  constexpr int32_t known = SPI_IMAGE_OUT_PROBS | SPI_IMAGE_OUT_TOPK | SPI_IMAGE_NO_LOGITS | SPI_IMAGE_TOPK_PROBS;
+  if (!m || (io & ~known)) return SPI_ERR_INVALID_ARGUMENT;
+  if ((io & SPI_IMAGE_NO_LOGITS) && !(io & (SPI_IMAGE_OUT_PROBS | SPI_IMAGE_OUT_TOPK))) return SPI_ERR_INVALID_ARGUMENT;
+  if ((io & SPI_IMAGE_TOPK_PROBS) && !(io & SPI_IMAGE_OUT_TOPK)) return SPI_ERR_INVALID_ARGUMENT;
+  if ((io & SPI_IMAGE_OUT_TOPK) ? (top_k < 1 || top_k > 64) : top_k != 0) return SPI_ERR_INVALID_ARGUMENT;
+  m->image_io = io;
+  m->top_k = top_k;
   return SPI_OK;
 }
 

@@ -20,7 +20,8 @@ import os
 import numpy as np
 
 from . import _native as N
-from .codelet import InferenceExecutionException, ModelReplica, PRECISIONS, _FAMILIES, bert_io_bits, spi_dtype
+from .codelet import InferenceExecutionException, ModelReplica, PRECISIONS, _FAMILIES, bert_io_bits, image_io_bits, \
+    spi_dtype
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPI_TORCH_LIB") or os.path.join(_HERE, "libspi_torch.so")
@@ -38,6 +39,7 @@ _PROTOS = {
     "spi_torch_cpu_forward": (C.c_int, [C.c_void_p, C.POINTER(N.TensorView), C.c_int, C.POINTER(N.TensorView),
                                         C.c_int, C.c_char_p, C.c_size_t]),
     "spi_torch_set_input_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "spi_torch_set_image_outputs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "spi_torch_named_tensors": (C.c_int32, [C.c_void_p, C.POINTER(C.POINTER(N.NamedTensor))]),
     "spi_torch_create_replica": (C.c_void_p, [C.c_void_p, C.c_int32, C.POINTER(N.ModelConfig), C.c_char_p,
                                               C.c_size_t]),
@@ -94,6 +96,13 @@ class TorchScriptModule:
         if lib.spi_torch_set_input_transform(self.handle, N.float3(scale), N.float3(shift)) != N.SPI_OK:
             raise InferenceExecutionException("set_input_transform: three finite values each for scale and shift")
 
+    def set_image_outputs(self, image_io=0, top_k: int = 0) -> None:
+        """Classification outputs of the CPU codelet (spi_torch_set_image_outputs): the module's [B,classes]
+        logits become logits, probabilities, top-k values and int64 top-k indices, as image_io selects."""
+        if lib.spi_torch_set_image_outputs(self.handle, image_io_bits(image_io), int(top_k)) != N.SPI_OK:
+            raise InferenceExecutionException(
+                "set_image_outputs: unknown bits, no output left, topk_probs without topk, or top_k outside 1 .. 64")
+
     def named_tensors(self) -> list[tuple[str, tuple]]:
         arr = C.POINTER(N.NamedTensor)()
         n = lib.spi_torch_named_tensors(self.handle, C.byref(arr))
@@ -103,7 +112,7 @@ class TorchScriptModule:
 
     def replica(self, device_id: int = 0, precision: str = "fp16", max_batch: int = 8, family: str | None = None,
                 num_heads: int = 0, seq_len: int = 0, image_size: int = 0, eps: float = 0.0,
-                graphs: bool = False, bert_io=0) -> ModelReplica:
+                graphs: bool = False, bert_io=0, image_io=0, top_k: int = 0) -> ModelReplica:
         cfg = N.ModelConfig()
         cfg.family = _FAMILIES[family]
         cfg.precision = PRECISIONS[precision]
@@ -117,7 +126,7 @@ class TorchScriptModule:
         h = lib.spi_torch_create_replica(self.handle, device_id, C.byref(cfg), err, len(err))
         if not h:
             raise InferenceExecutionException(f"model replica creation failed: {err.value.decode()}")
-        return ModelReplica.from_handle(h, device_id, precision, max_batch, graphs, cfg.bert_io)
+        return ModelReplica.from_handle(h, device_id, precision, max_batch, graphs, cfg.bert_io, image_io, top_k)
 
     def bench(self, inputs: list[np.ndarray], output_bytes: list[int], workers: int = 1, threads: int = 0,
               seconds: float = 5.0, max_tasks: int = 0, output_types=None) -> dict:

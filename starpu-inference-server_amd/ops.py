@@ -475,6 +475,14 @@ def masked_mean(h, mask, out, B, S, D, stream=None):
     return out
 
 
+def softmax_topk(x, ldx, probs, topv, topi, B, N, k=0, topk_probs=False, stream=None):
+    """Softmax and / or top-k of B fp32 logits rows of N, ldx floats apart: probs fp32 [B][N] or None; topv fp32
+    [B][k] and topi int64 [B][k], both or neither (then k = 0); topk_probs: topv holds probabilities."""
+    _check(lib.spi_op_softmax_topk(_ptr(x), ldx, _ptr(probs), _ptr(topv), _ptr(topi), B, N, k, int(bool(topk_probs)),
+                                   _stream(stream)))
+    return probs, topv, topi
+
+
 def mask_to_bias(mask, bias, n, stream=None):
     _check(lib.spi_op_mask_to_bias(_ptr(mask), _ptr(bias), n, _stream(stream)))
     return bias
