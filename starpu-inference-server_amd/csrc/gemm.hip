@@ -42,6 +42,7 @@
 #include "gemm_tile.hpp"
 #include "lds_dma.hpp"
 #include "ln_fold.hpp"
+#include "pack.hpp"
 #include "spi_kernels.hpp"
 
 #include <algorithm>
@@ -1508,6 +1509,30 @@ void gemm(const GemmDesc& d, const GemmPtrs& p, Prec prec, hipStream_t s) {
     gemm256(d, p, g.g256_splits, s, g.g256_bm, g.g256_nbuf, g.g256_order);
   else
     with_mode(mode_of(prec, d.a_split), [&](auto m) { launch<decltype(m)::value>(d, p, g.pl, s); });
+}
+
+// Whether gemm() would hand this spi_op_conv2d call to conv_wres (tests: which kernel runs): 1 or 0, -1 on
+// bad arguments.  The desc is the one ops.cpp builds for a weight from spi_op_pack_weight; the pointers are
+// placeholders, 16-byte aligned (an unaligned operand keeps the general kernel, which this cannot see).
+// Launches nothing, needs no device.
+extern "C" int spi_debug_conv_route(int precision, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
+                                    int pad, int has_residual, int act) {
+  if (precision < 0 || precision > 3 || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 ||
+      stride < 1 || pad < 0 || act < 0 || act > 2)
+    return -1;
+  const Prec prec = case_prec(precision);
+  GemmDesc d = case_conv_desc(precision, B, H, W, Cin, Cout, KH, KW, stride, pad);
+  d.act = static_cast<Act>(act);
+  d.w_image = packed_has_wres_image(prec, Cout, d.K, round_up_to(Cout, 128), d.Kpad);
+  const auto at = [](uintptr_t a) { return reinterpret_cast<const void*>(a); };
+  GemmPtrs p;
+  p.A = at(0x10000000);
+  p.W = at(0x20000000);
+  p.bias = static_cast<const float*>(at(0x30000000));
+  p.res = has_residual ? at(0x40000000) : nullptr;
+  p.C = const_cast<void*>(at(0x50000000));
+  p.zeros = at(0x80000000);
+  return prec == Prec::F16 && conv_wres_eligible(d, prec, p) ? 1 : 0;
 }
 
 }  // namespace spi

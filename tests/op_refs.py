@@ -1,6 +1,7 @@
 """Plain float64 / bit-exact references of the ops behind include/spi_ops.h that the GPU op tests
 (test_qkv_attention_ops_gpu.py, test_attention_ops_gpu.py, test_elementwise_ops_gpu.py, test_conv_pair_ops_gpu.py,
-test_hilo_weight_ops_gpu.py, the hi + lo consumer of test_ln_fold_ops_gpu.py) compare the HIP kernels with,
+test_hilo_weight_ops_gpu.py, test_conv_kinds_ops_gpu.py, the hi + lo consumer of test_ln_fold_ops_gpu.py) compare the
+HIP kernels with,
 plus the inputs and case lists those tests share.  Nothing here touches a GPU; test_op_refs.py checks every reference
 against the torch op it restates, so the GPU bars rest on checked ground.
 """
@@ -333,21 +334,22 @@ def dense_acc32_hilo(A16, W):
     return (a @ torch.from_numpy(hi.astype(np.float32)).T + a @ torch.from_numpy(lo.astype(np.float32)).T).numpy()
 
 
-def conv_case(B, H, cin, convs, seed=None):
-    """Inputs of convs on one NHWC input: x fp32 [B][H][H][cin] of N(0, 1) and per conv (cout, k, stride, pad)
-    the weight [cout][k][k][cin] of He scale (its reshape to [cout][k k cin] is the matrix to pack) and a
-    bias of N(0, 1)."""
+def conv_case(B, H, cin, convs, seed=None, W=None):
+    """Inputs of convs on one NHWC input: x fp32 [B][H][W][cin] of N(0, 1) (W defaults to H) and per conv
+    (cout, k, stride, pad), k an integer or (kh, kw), the weight [cout][kh][kw][cin] of He scale (its reshape
+    to [cout][kh kw cin] is the matrix to pack) and a bias of N(0, 1)."""
     rng = np.random.default_rng(B * 1000 + H * 10 + cin if seed is None else seed)
-    x = rng.standard_normal((B, H, H, cin)).astype(np.float32)
+    x = rng.standard_normal((B, H, H if W is None else W, cin)).astype(np.float32)
     ws = []
     for cout, k, _, _ in convs:
-        w = (rng.standard_normal((cout, k, k, cin)) * np.sqrt(2.0 / (cin * k * k))).astype(np.float32)
+        kh, kw = (k, k) if isinstance(k, int) else k
+        w = (rng.standard_normal((cout, kh, kw, cin)) * np.sqrt(2.0 / (cin * kh * kw))).astype(np.float32)
         ws.append((w, rng.standard_normal(cout).astype(np.float32)))
     return x, ws
 
 
 def conv_acc(x_vals, w_vals, stride, pad, dtype=torch.float64):
-    """NHWC conv of x_vals [B][H][W][C] with w_vals [cout][k][k][C] on the values as given, in dtype
+    """NHWC conv of x_vals [B][H][W][C] with w_vals [cout][kh][kw][C] on the values as given, in dtype
     (float64: the reference; float32: an fp32-accumulated emulation) -> numpy [B][OH][OW][cout]."""
     x = torch.from_numpy(np.ascontiguousarray(x_vals)).to(dtype).permute(0, 3, 1, 2)
     w = torch.from_numpy(np.ascontiguousarray(w_vals)).to(dtype).permute(0, 3, 1, 2)
@@ -462,3 +464,273 @@ def vit_assemble_ref(patches, cls, pos):
 def gather_rows_ref(x, rows, stride_rows, f16):
     y = np.asarray(x, np.float32)[:rows * stride_rows:stride_rows]
     return y.astype(np.float16) if f16 else y.copy()
+
+
+# ---------------------------------------------------------------------------------------------
+# the conv kinds behind spi_op_conv2d (test_conv_kinds_ops_gpu.py): kConvGen, kConvTap, the three kConvTapW
+# forms, kConvHalo / kConvHaloS and the weight-resident 64 -> 64 conv, on non-square maps and filters
+#
+# A shape is always the 9-tuple (B, H, W, Cin, Cout, KH, KW, stride, pad).
+
+# 3x3 / stride 1 / pad 1, (B, H, W, Cin, Cout): the smallest at which each kind still does all it can do
+CONV3_SHAPES = {
+    "S1": (1, 5, 9, 64, 64),       # one ragged tile; eligible for the weight-resident kernel
+    "S2": (2, 13, 3, 128, 64),     # W = 3: every pixel on a side border, the image seam inside a tile
+    "S3": (3, 7, 20, 64, 128),     # three images, M = 420, two column tiles
+    "S4": (2, 14, 9, 128, 128),    # the default rule's 64-row halo (OH >= 14)
+    "S5": (1, 9, 30, 64, 64),      # short and wide
+    "S6": (3, 6, 17, 64, 64),      # kConvHaloS
+    "S7": (1, 20, 50, 64, 64),     # the default rule's 128-row halo (OW > 32); no 64-row candidate fits
+    "S8": (2, 3, 61, 64, 64),      # H = 3; no 64-row candidate fits
+    "S9": (1, 30, 9, 256, 64),     # tall and narrow; 4 (fp16) or 8 channel blocks: the deepest split-K
+    "S10": (2, 40, 52, 64, 256),   # the 128 x 64 window tile: 132 tiles, M = 4160 = 32.5 tile rows
+}
+# the weight-resident kernel (fp16, 64 -> 64), (B, H, W): the widest map whose halo fits (th = 1), one pixel
+# wider (must not take the kernel), one 16-row band per image, 2-row bands with a partial last one, 61 rows,
+# an odd band count
+WRES_SHAPES = [(1, 3, 83), (1, 3, 84), (2, 16, 8), (3, 13, 56), (2, 61, 30), (19, 28, 28)]
+WRES_REFUSED = (1, 3, 84)
+# geometry no model uses, for the tap walk and the gather
+CONV_GEO_SHAPES = [
+    (1, 9, 13, 64, 96, 5, 5, 1, 2),    # 25 taps (K = Kpad = 1600), ragged Cout, 4 to 8 slices
+    (2, 9, 14, 64, 64, 1, 7, 1, 0),    # KH != KW
+    (1, 11, 7, 32, 64, 3, 1, 2, 1),    # KH != KW at stride 2, K = 96 of Kpad = 128: the gather in fp16, the
+                                       # tap walk with a Kpad tail step elsewhere
+    (1, 10, 12, 64, 64, 7, 7, 2, 3),   # 49 taps: the gather at wide Cin; the split layout rejects it
+    (1, 9, 11, 16, 24, 3, 3, 1, 1),    # the gather with k-steps straddling filter rows
+    (1, 12, 10, 64, 64, 3, 3, 3, 0),   # stride 3, no padding, the last columns unused
+    (2, 8, 15, 128, 64, 1, 1, 1, 1),   # the output's outer ring lies wholly in the padding: act(bias)
+    (1, 6, 10, 64, 64, 3, 3, 1, 2),    # pad > k // 2
+]
+CONV_RING = (2, 8, 15, 128, 64, 1, 1, 1, 1)
+CONV_PRECS = ("fp32", "fp16", "fp16x3", "fp16x3s")
+PREC_ID = {"fp32": 0, "fp16": 1, "fp16x3": 2, "fp16x3s": 3}
+KIND_KNOBS = ("SPI_GEMM_WIN", "SPI_GEMM_HALO_CFG", "SPI_CONV_WRES", "SPI_GEMM_MAXSPLIT", "SPI_GEMM_PLAN")
+_NO_FAST = {"SPI_GEMM_HALO_CFG": "0", "SPI_CONV_WRES": "0"}
+KIND_SETTINGS = {
+    **{f"win{v}": {**_NO_FAST, "SPI_GEMM_WIN": str(v)} for v in range(4)},
+    **{f"halo{rows}{m}": {"SPI_GEMM_HALO_CFG": f"{rows},{m}", "SPI_CONV_WRES": "0"}
+       for rows in (64, 128, 256) for m in "as"},
+    "rule": {"SPI_CONV_WRES": "0"},
+    "rule-max3": {"SPI_CONV_WRES": "0", "SPI_GEMM_MAXSPLIT": "3"},
+    "wres2": {"SPI_CONV_WRES": "2"},
+    "wres0": {"SPI_CONV_WRES": "0"},
+    "default": {},
+    "plan64": {"SPI_GEMM_PLAN": "64,64,3,2"},
+    "plan128x64": {"SPI_GEMM_PLAN": "128,64,2,1"},
+    "plan128": {"SPI_GEMM_PLAN": "128,128,2,1"},
+}
+HALO_SETTINGS = [f"halo{rows}{m}" for rows in (64, 128, 256) for m in "as"] + ["rule"]
+PLAN_FIELDS = ("bm", "bn", "stages", "splits", "halo", "win", "nw", "k_per_split")
+
+
+def shape9(s):
+    """(B, H, W) of a weight-resident shape or (B, H, W, Cin, Cout) of a 3x3 one -> the 9-tuple."""
+    s = tuple(s)
+    if len(s) == 3:
+        s += (64, 64)
+    return s + (3, 3, 1, 1) if len(s) == 5 else s
+
+
+def conv_accepts(prec, shape):
+    """Whether spi_op_conv2d takes the shape at the precision (include/spi_ops.h)."""
+    _, H, W, cin, cout, kh, kw, _, pad = shape
+    if H + 2 * pad < kh or W + 2 * pad < kw or cin & (cin - 1) or cin < (8 if prec == "fp16" else 4):
+        return False
+    return prec != "fp16x3s" or (cin >= 32 and cout % 32 == 0 and kh * kw <= 31)
+
+
+def conv_kind_runs():
+    """Every (group, setting, precision, shape) the GPU tests launch, in the order they run: the smallest
+    maps first within a group.  test_exact_integer_cases runs the same list."""
+    runs = []
+    s3 = {k: shape9(v) for k, v in CONV3_SHAPES.items()}
+    for name in sorted(s3, key=lambda n: s3[n][0] * s3[n][1] * s3[n][2] * s3[n][3]):
+        for prec in ("fp16", "fp16x3s"):
+            runs += [("window", f"win{v}", prec, s3[name]) for v in (1, 0, 2, 3)]
+        if name != "S10":
+            for prec in ("fp32", "fp16", "fp16x3s"):
+                runs += [("halo", st, prec, s3[name]) for st in HALO_SETTINGS]
+                if name == "S9":
+                    runs.append(("halo", "rule-max3", prec, s3[name]))
+    for s in sorted(WRES_SHAPES, key=lambda s: s[0] * s[1] * s[2]):
+        runs += [("wres", st, "fp16", shape9(s)) for st in ("wres2", "wres0")]
+    for i, s in enumerate(CONV_GEO_SHAPES):
+        for prec in CONV_PRECS:
+            if conv_accepts(prec, s):
+                runs += [("geo", st, prec, s) for st in ("default", ("plan64", "plan128x64", "plan128")[i % 3])]
+    return runs
+
+
+def kind_key(setting, prec, shape):
+    return f"{setting}|{prec}|" + ",".join(map(str, shape))
+
+
+def query_conv_plan(lib, prec, shape):
+    """spi_debug_conv_plan under the knobs in force, as a list of the 8 PLAN_FIELDS."""
+    import ctypes as C
+    out = (C.c_int * 8)()
+    assert lib.spi_debug_conv_plan(PREC_ID[prec], *shape, out) == 0
+    return [int(v) for v in out]
+
+
+def query_conv_route(lib, prec, shape, res, act):
+    """spi_debug_conv_route: 1 when the weight-resident kernel would run (aligned operands, a whole pack)."""
+    return int(lib.spi_debug_conv_route(PREC_ID[prec], *shape, int(bool(res)), {None: 0, "relu": 1}[act]))
+
+
+class kind_knobs:
+    """with kind_knobs(lib, setting): the five knobs set to the setting's values (the others unset), re-read
+    by the library, and put back on the way out."""
+
+    def __init__(self, lib, setting):
+        self.lib, self.env = lib, KIND_SETTINGS[setting]
+
+    def __enter__(self):
+        import os
+        self.saved = {k: os.environ.pop(k, None) for k in KIND_KNOBS}
+        os.environ.update(self.env)
+        self.lib.spi_debug_gemm_reload_env()
+
+    def __exit__(self, *exc):
+        import os
+        for k, v in self.saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+        self.lib.spi_debug_gemm_reload_env()
+
+
+def conv_kind_name(prec, shape, plan, route=0):
+    """The device path a plan means, as gemm() / dispatch() / launch_tile() choose it: wres, halo<rows> /
+    haloS64, win<rows>x<waves>, gen (several taps per k-step: Cin below the k-step, or more than 31 taps) or
+    tap; "-k<slices>" appended under split-K."""
+    pl = dict(zip(PLAN_FIELDS, plan))
+    if route:
+        return "wres"
+    cin, taps = shape[3], shape[5] * shape[6]
+    if pl["halo"]:
+        name = ("haloS" if pl["halo"] == 2 else "halo") + str(pl["bm"])
+    elif pl["win"]:
+        name = f"win{pl['bm']}x{pl['nw']}"
+    elif cin < (64 if prec == "fp16" else 32) or taps > 31:
+        name = f"gen{pl['bm']}x{pl['bn']}"
+    else:
+        name = f"tap{pl['bm']}x{pl['bn']}"
+    return name + (f"-k{pl['splits']}" if pl["splits"] > 1 else "")
+
+
+def split_values(x):
+    """float64 hi + lo of the split layout: fp16(x) + fp16(x - fp16(x)) (ops.from_split(ops.to_split(x)))."""
+    x = np.asarray(x, np.float32)
+    hi = x.astype(np.float16)
+    return hi.astype(np.float64) + (x - hi.astype(np.float32)).astype(np.float16).astype(np.float64)
+
+
+def operand_values(prec, x, w=None):
+    """float64 values the kernel multiplies / adds for fp32 data at a precision: fp16-rounded for fp16 (the
+    weight too), the split layout's hi + lo for fp16x3s activations against the fp32 weight, the fp32
+    values for fp32 and fp16x3."""
+    def act(a):
+        a = np.asarray(a, np.float32)
+        return a.astype(np.float16).astype(np.float64) if prec == "fp16" else \
+            split_values(a) if prec == "fp16x3s" else a.astype(np.float64)
+    if w is None:
+        return act(x)
+    w = np.asarray(w, np.float32)
+    return act(x), (w.astype(np.float16) if prec == "fp16" else w).astype(np.float64)
+
+
+def conv_out_hw(shape):
+    _, H, W, _, _, kh, kw, stride, pad = shape
+    return (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+
+
+def conv_kind_case(shape):
+    """fp32 inputs of one shape, shared by every precision, kind and form: x [B][H][W][Cin] of N(0, 1), the
+    weight [Cout][KH][KW][Cin] of He scale, bias and residual [B][OH][OW][Cout] of N(0, 1)."""
+    B, H, W, cin, cout, kh, kw, stride, pad = shape
+    x, [(w, b)] = conv_case(B, H, cin, [(cout, (kh, kw), stride, pad)], seed=sum(v * 31 ** i for i, v in enumerate(shape)),
+                            W=W)
+    oh, ow = conv_out_hw(shape)
+    r = np.random.default_rng(H * 100 + W + cout).standard_normal((B, oh, ow, cout)).astype(np.float32)
+    return x, w, b, r
+
+
+EXACT_MAX = 2048  # every integer up to 2048 is an fp16 number
+
+
+def conv_exact_case(shape):
+    """An integer case: x in [-2, 2], w in {-1, 0, 1}, bias and residual in [-4, 4], ReLU.  Every product and
+    partial sum is an integer far below 2^24: exact in fp32 in any order, under any split-K; the reference
+    stays within EXACT_MAX, so an fp16 or split output holds it exactly as well.  Returns x, w, b, r (fp32,
+    the same for every precision) and the float64 reference [B][OH][OW][Cout]."""
+    B, H, W, cin, cout, kh, kw, stride, pad = shape
+    rng = np.random.default_rng(7 + sum(v * 29 ** i for i, v in enumerate(shape)))
+    x = rng.integers(-2, 3, (B, H, W, cin)).astype(np.float32)
+    w = rng.integers(-1, 2, (cout, kh, kw, cin)).astype(np.float32)
+    b = rng.integers(-4, 5, cout).astype(np.float32)
+    oh, ow = conv_out_hw(shape)
+    r = rng.integers(-4, 5, (B, oh, ow, cout)).astype(np.float32)
+    ref = epilogue64(conv_acc(x, w, stride, pad), b, r, "relu")
+    assert np.abs(conv_acc(x, w, stride, pad)).max() + 8 <= EXACT_MAX and np.abs(ref).max() <= EXACT_MAX, shape
+    assert np.array_equal(ref, np.rint(ref)) and ref.max() > 0
+    return x, w, b, r, ref
+
+
+# the wrong 3x3 / s1 / p1 convs a kernel with a slipped index computes (test_op_refs holds each at least
+# 10x above the bar, for every CONV3_SHAPES entry)
+def conv3_flat_unmasked(xv, wv, shape):
+    """No column, row or image mask: tap (kh, kw) of pixel m reads pixel m + (kh - 1) W + kw - 1 of the flat
+    pixel list whenever that lies in [0, M)."""
+    B, H, W, cin, cout = shape[:5]
+    M = B * H * W
+    xf = np.asarray(xv, np.float64).reshape(M, cin)
+    out = np.zeros((M, cout))
+    for kh in range(3):
+        for kw in range(3):
+            off = (kh - 1) * W + kw - 1
+            lo, hi = max(0, -off), min(M, M - off)
+            out[lo:hi] += xf[lo + off:hi + off] @ np.asarray(wv, np.float64)[:, kh, kw].T
+    return out.reshape(B, H, W, cout)
+
+
+def conv3_hw_exchanged(xv, wv, shape):
+    """The same pixel list walked as [B][W][H]."""
+    B, H, W, cin, cout = shape[:5]
+    return conv_acc(np.asarray(xv).reshape(B, W, H, cin), wv, 1, 1).reshape(B, H, W, cout)
+
+
+def conv3_images_joined(xv, wv, shape):
+    """The B images as one tall image: rows leak across the seams."""
+    B, H, W, cin, cout = shape[:5]
+    return conv_acc(np.asarray(xv).reshape(1, B * H, W, cin), wv, 1, 1).reshape(B, H, W, cout)
+
+
+def conv3_window_walk(xv, wv, shape, bm=64, col_mask=True, pitch=None):
+    """The kw-window kind's indexing (gemm.hip kConvTapW, as test_window_indexing.py restates it) on an
+    H x W map: per tile of bm output pixels from m0 and filter row kh, the bm + 2 pixels from
+    m0 + (kh - 1) pitch - 1 on (zeros outside [0, M)), tap kw of tile row r from window row r + kw, taps
+    outside the image zeroed by the per-row mask.  pitch = W and col_mask give the conv; col_mask=False
+    drops the mask's column terms, pitch = H is issue_win with d.H written for d.W."""
+    B, H, W, cin, cout = shape[:5]
+    pitch = W if pitch is None else pitch
+    M = B * H * W
+    xf, w = np.asarray(xv, np.float64).reshape(M, cin), np.asarray(wv, np.float64)
+    out = np.zeros((M, cout))
+    rows = np.arange(bm)
+    for m0 in range(0, M, bm):
+        m = m0 + rows
+        valid = m < M
+        rem = np.where(valid, m, 0) % (H * W)
+        oh, ow = rem // W, rem % W
+        left, right = ((ow > 0), (ow + 1 < W)) if col_mask else (np.ones(bm, bool), np.ones(bm, bool))
+        acc = np.zeros((bm, cout))
+        for kh in range(3):
+            row_ok = valid & (oh + kh - 1 >= 0) & (oh + kh - 1 < H)
+            pix = m0 + (kh - 1) * pitch - 1 + np.arange(bm + 2)
+            win = np.where(((pix >= 0) & (pix < M))[:, None], xf[np.clip(pix, 0, M - 1)], 0.0)
+            for kw, col_ok in enumerate((left, np.ones(bm, bool), right)):
+                acc += np.where((row_ok & col_ok)[:, None], win[rows + kw], 0.0) @ w[:, kh, kw].T
+        out[m[valid]] = acc[valid]
+    return out.reshape(B, H, W, cout)

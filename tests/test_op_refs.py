@@ -250,6 +250,198 @@ def test_hilo_values_are_what_the_pack_holds(ops):
     assert R.nerr(R.hilo_values(w), w.astype(np.float64)) < 2.0 ** -21
 
 
+# ---- the conv kinds (test_conv_kinds_ops_gpu.py) --------------------------------------------------
+
+TOL32, TOL16 = 1e-5, 2e-3  # the GPU bars: into an fp32 or split output, into an fp16 output
+
+
+@pytest.fixture(scope="module")
+def kind_table():
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_kind_plans.json")) as f:
+        return json.load(f)
+
+
+def _kind(table, setting, prec, shape, form="11"):
+    key = R.kind_key(setting, prec, R.shape9(shape))
+    route = table["routes"].get(key, {}).get(form, 0)
+    return R.conv_kind_name(prec, R.shape9(shape), table["plans"][key], route)
+
+
+def test_conv_kind_plan_table_pinned(spi, kind_table):
+    """Every (setting, precision, shape) the GPU tests launch: the planner and the weight-resident route give
+    exactly the recorded integers, so each GPU case id names the kind that case runs on."""
+    keys = {R.kind_key(st, prec, shape): (st, prec, shape) for _, st, prec, shape in R.conv_kind_runs()}
+    assert kind_table["settings"] == R.KIND_SETTINGS and set(kind_table["plans"]) == set(keys)
+    bad = []
+    for key, (st, prec, shape) in keys.items():
+        with R.kind_knobs(spi.lib, st):
+            got = R.query_conv_plan(spi.lib, prec, shape)
+            routes = {f: R.query_conv_route(spi.lib, prec, shape, f[0] == "1", "relu" if f[1] == "1" else None)
+                      for f in kind_table["routes"].get(key, {})}
+        if got != kind_table["plans"][key] or routes != kind_table["routes"].get(key, {}):
+            bad.append((key, got, routes))
+    assert not bad, f"{len(bad)} cases differ from the table, first: {bad[:3]}"
+    assert set(kind_table["routes"]) == {k for k, (_, prec, s) in keys.items() if prec == "fp16" and s[3:5] == (64, 64)}
+
+
+def test_conv_kind_table_reaches_every_kind(kind_table):
+    """What the table has to say for the GPU file to cover the seven device paths (and each form of them)."""
+    S = R.CONV3_SHAPES
+    def pl(st, prec, name):
+        return dict(zip(R.PLAN_FIELDS, kind_table["plans"][R.kind_key(st, prec, R.shape9(S[name]))]))
+
+    for prec in ("fp16", "fp16x3s"):
+        es = 64 if prec == "fp16" else 32
+        for name in S:
+            if name != "S10":  # the default rule
+                want = "halo64" if name in ("S4", "S9") else "halo128" if name == "S7" else "win64x4"
+                assert _kind(kind_table, "rule", prec, S[name]).split("-")[0] == want, (prec, name)
+            p = pl("win1", prec, name)  # halo off: the window on 4 waves, S10 at 128 x 64 in one slice
+            assert (p["win"], p["halo"], p["nw"], p["bn"]) == (1, 0, 4, 64) and p["bm"] == (128 if name == "S10" else 64)
+            assert name != "S10" or p["splits"] == 1
+            p = pl("win2", prec, name)  # 8 waves exactly where the k-steps are a multiple of 6
+            ksteps = 9 * S[name][3] // es
+            assert p["win"] == 1 and p["nw"] == (8 if ksteps % 6 == 0 and name != "S10" else 4), (prec, name, p)
+            p = pl("win0", prec, name)  # the plain tap walk: 2 stages, 3 from 12 k-steps per slice (split S10: 18)
+            assert (p["win"], p["halo"], p["stages"]) == (0, 0, 3 if p["k_per_split"] // es >= 12 else 2), (prec, name, p)
+            assert p["stages"] == 2 or (prec, name) == ("fp16x3s", "S10"), (prec, name, p)
+        assert [n for n in S if pl("win2", prec, n)["nw"] == 8] == \
+            (["S2", "S4", "S9"] if prec == "fp16" else [n for n in S if n != "S10"])
+    for prec in ("fp32", "fp16", "fp16x3s"):
+        for name in S:
+            if name == "S10":
+                continue
+            halo = pl("halo64a", prec, name)["halo"]
+            if name in ("S1", "S2", "S6"):
+                assert halo == 2, (prec, name)
+            elif name in ("S4", "S5", "S9"):
+                assert halo == 1, (prec, name)
+            elif name in ("S7", "S8"):  # no 64-row candidate fits: the window kind, for fp32 the tap walk
+                assert halo == 0 and pl("halo64a", prec, name)["win"] == (prec != "fp32"), (prec, name)
+            for rows in (128, 256):
+                for m in "as":
+                    p = pl(f"halo{rows}{m}", prec, name)
+                    assert (p["halo"], p["bm"], p["nw"]) == (1, rows, 8 if rows == 256 else 4), (prec, name, rows, m)
+    assert not any(p[5] for k, p in kind_table["plans"].items() if "|fp32|" in k), "fp32 never takes the window kind"
+    p = pl("rule-max3", "fp16x3s", "S9")
+    assert p["halo"] == 1 and p["splits"] == 3 and (S["S9"][3] // 32) % p["splits"], p  # 8 blocks in 3 slices
+    kinds = {_kind(kind_table, st, prec, shape).split("-")[0] for _, st, prec, shape in R.conv_kind_runs()}
+    assert {"wres", "halo64", "haloS64", "halo128", "halo256", "win64x4", "win64x8", "win128x4", "tap64x64",
+            "tap128x64", "tap128x128", "gen64x64", "gen128x64", "gen128x128"} <= kinds, kinds
+    geo = {s: {prec: _kind(kind_table, "default", prec, s) for prec in R.CONV_PRECS if R.conv_accepts(prec, s)}
+           for s in R.CONV_GEO_SHAPES}
+    assert geo[(1, 11, 7, 32, 64, 3, 1, 2, 1)] == {"fp32": "tap64x64", "fp16": "gen64x64", "fp16x3": "tap64x64",
+                                                   "fp16x3s": "tap64x64"}
+    assert all(k.startswith("gen") for k in geo[(1, 10, 12, 64, 64, 7, 7, 2, 3)].values())
+    assert "fp16x3s" not in geo[(1, 10, 12, 64, 64, 7, 7, 2, 3)] and "fp16x3s" not in geo[(1, 9, 11, 16, 24, 3, 3, 1, 1)]
+    assert all(k.startswith("gen") for k in geo[(1, 9, 11, 16, 24, 3, 3, 1, 1)].values())
+
+
+def test_weight_resident_route(spi):
+    """spi_debug_conv_route without a device: SPI_CONV_WRES=2 takes every weight-resident shape but the
+    84-wide one (its one-row halo, 3 x 86 pixels, no longer fits 256), =0 takes none, and nothing but an fp16
+    3x3 / s1 / p1 64 -> 64 conv without GELU is ever routed there."""
+    for shape in R.WRES_SHAPES:
+        s = R.shape9(shape)
+        for res in (False, True):
+            for act in (None, "relu"):
+                with R.kind_knobs(spi.lib, "wres2"):
+                    assert R.query_conv_route(spi.lib, "fp16", s, res, act) == int(shape != R.WRES_REFUSED), shape
+                    assert R.query_conv_route(spi.lib, "fp16x3s", s, res, act) == 0
+                with R.kind_knobs(spi.lib, "wres0"):
+                    assert R.query_conv_route(spi.lib, "fp16", s, res, act) == 0, shape
+    with R.kind_knobs(spi.lib, "wres2"):
+        assert spi.lib.spi_debug_conv_route(1, 1, 8, 8, 64, 64, 3, 3, 1, 1, 0, 2) == 0  # GELU
+        assert spi.lib.spi_debug_conv_route(1, 1, 8, 8, 64, 64, 3, 3, 2, 1, 0, 0) == 0  # stride 2
+        assert spi.lib.spi_debug_conv_route(1, 1, 8, 8, 64, 128, 3, 3, 1, 1, 0, 0) == 0
+        assert spi.lib.spi_debug_conv_route(1, 1, 8, 8, 64, 64, 3, 3, 1, 1, 0, 0) == 1
+        assert spi.lib.spi_debug_conv_route(7, 1, 8, 8, 64, 64, 3, 3, 1, 1, 0, 0) == -1
+
+
+def test_split_values_are_what_the_layout_holds(ops):
+    x = (np.random.default_rng(9).standard_normal((2, 3, 5, 64)) * 5).astype(np.float32)
+    back = ops.from_split(ops.to_split(torch.from_numpy(x))).numpy()
+    np.testing.assert_array_equal(R.split_values(x), back.astype(np.float64))
+    xv, wv = R.operand_values("fp16", x, x)
+    np.testing.assert_array_equal(xv, x.astype(np.float16).astype(np.float64))
+    np.testing.assert_array_equal(wv, xv)
+    xv, wv = R.operand_values("fp16x3s", x, x)
+    np.testing.assert_array_equal(xv, R.split_values(x))
+    np.testing.assert_array_equal(wv, x.astype(np.float64))
+
+
+def test_conv_acc_takes_rectangles():
+    """conv_case / conv_acc on an H x W map and a KH x KW filter against a direct sum, and the square callers'
+    draws unchanged."""
+    x, [(w, _)] = R.conv_case(2, 5, 4, [(3, (1, 3), 2, 1)], W=8)
+    assert x.shape == (2, 5, 8, 4) and w.shape == (3, 1, 3, 4)
+    got = R.conv_acc(x, w, 2, 1)
+    xp = np.zeros((2, 7, 10, 4))
+    xp[:, 1:6, 1:9] = x
+    want = np.zeros((2, 4, 4, 3))
+    for oh in range(4):
+        for ow in range(4):
+            want[:, oh, ow] = np.einsum("bkc,nkc->bn", xp[:, 2 * oh, 2 * ow:2 * ow + 3], w[:, 0].astype(np.float64))
+    assert got.shape == want.shape and np.abs(got - want).max() < TOL64
+    xs, [(ws_, bs)] = R.conv_case(2, 5, 4, [(3, 3, 1, 1)])
+    rng = np.random.default_rng(2 * 1000 + 5 * 10 + 4)
+    np.testing.assert_array_equal(xs, rng.standard_normal((2, 5, 5, 4)).astype(np.float32))
+    np.testing.assert_array_equal(ws_, (rng.standard_normal((3, 3, 3, 4)) * np.sqrt(2.0 / 36)).astype(np.float32))
+
+
+@pytest.mark.parametrize("name", list(R.CONV3_SHAPES))
+@pytest.mark.parametrize("prec", ["fp16", "fp16x3s"])
+def test_conv_kind_cases_discriminate(name, prec):
+    """For the GPU file's inputs: the right arithmetic (an fp32-accumulated torch conv of the same operands)
+    stays 3x below the bars, and each indexing slip a window, band or tap-walk kernel can make -- no column /
+    row / image mask, H and W exchanged, the images joined into one -- sits at least 10x above them."""
+    shape = R.shape9(R.CONV3_SHAPES[name])
+    x, w, b, r = R.conv_kind_case(shape)
+    xv, wv = R.operand_values(prec, x, w)
+    rv = R.operand_values(prec, r)
+    ref = R.epilogue64(R.conv_acc(xv, wv, 1, 1), b, rv, "relu")
+    emu = R.epilogue64(R.conv_acc(xv.astype(np.float32), wv.astype(np.float32), 1, 1, torch.float32), b, rv, "relu")
+    if prec == "fp16":
+        e32, e16 = R.nerr(emu, ref), R.nerr(emu.astype(np.float16), ref)
+    else:  # fp32 accumulation of hi + lo operands: the fp32 sum of the split values stands in for them
+        e32, e16 = R.nerr(emu, ref), None
+    wrong = {"flat": R.conv3_flat_unmasked(xv, wv, shape), "hw": R.conv3_hw_exchanged(xv, wv, shape)}
+    if shape[0] > 1:
+        wrong["joined"] = R.conv3_images_joined(xv, wv, shape)
+    # the window kind's own walk: right as it stands, wrong without the mask's column terms and with d.H
+    # written for d.W in the window's first pixel (which a square map cannot see)
+    bm = 128 if name == "S10" else 64
+    assert R.nerr(R.conv3_window_walk(xv, wv, shape, bm), R.conv_acc(xv, wv, 1, 1)) < TOL64
+    wrong["window-no-column-mask"] = R.conv3_window_walk(xv, wv, shape, bm, col_mask=False)
+    wrong["window-h-for-w"] = R.conv3_window_walk(xv, wv, shape, bm, pitch=shape[1])
+    errs ={k: R.nerr(R.epilogue64(v, b, rv, "relu"), ref) for k, v in wrong.items()}
+    print(f"{name} {prec}: fp32 accumulation {e32:.3e}" + (f", rounded to fp16 {e16:.3e}" if e16 else "") +
+          "; wrong convs " + ", ".join(f"{k} {v:.3e}" for k, v in errs.items()))
+    assert 3 * e32 < TOL32 and (e16 is None or 3 * e16 < TOL16)
+    bar = TOL16 if prec == "fp16" else TOL32
+    assert all(v > 10 * bar for v in errs.values()), errs
+
+
+def test_conv_exact_cases_are_exact(ops):
+    """Every shape the GPU file launches has an integer case whose reference stays within 2048 (asserted by
+    the builder), whose operands every layout holds exactly, and which an fp32-accumulated conv reproduces
+    to the bit."""
+    shapes = list(dict.fromkeys(s for _, _, _, s in R.conv_kind_runs()))
+    assert len(shapes) == len(R.CONV3_SHAPES) + len(R.WRES_SHAPES) + len(R.CONV_GEO_SHAPES)
+    for shape in shapes:
+        x, w, b, r, ref = R.conv_exact_case(shape)
+        assert np.abs(ref).max() <= R.EXACT_MAX and ref.shape[1:3] == R.conv_out_hw(shape)
+        for a in (x, w, b, r, ref):
+            np.testing.assert_array_equal(a.astype(np.float16).astype(np.float64), a)
+        np.testing.assert_array_equal(R.split_values(x), x)
+        emu = R.epilogue64(R.conv_acc(x, w, shape[7], shape[8], torch.float32), b, r, "relu")
+        np.testing.assert_array_equal(emu, ref)
+    t = torch.from_numpy(ref.astype(np.float32))
+    np.testing.assert_array_equal(ops.from_split(ops.to_split(t)).numpy(), ref)
+
+
 # ---- the HBM-bound kernels ----------------------------------------------------------------------
 
 
