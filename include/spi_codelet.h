@@ -357,6 +357,41 @@ int64_t spi_model_launch_table(spi_model* model, void* stream, int64_t batch, in
  * The measurement hooks above (spi_model_profile, _profile_op, _launch_table) carry no
  * element type and always read fp32 NCHW inputs. */
 int spi_model_set_input_transform(spi_model* model, const float scale[3], const float shift[3]);
+/* Resize + centre crop of 8-bit image tasks on the device (opt-in): the first two steps of torchvision's
+ * weights.transforms() preset -- resize the short side, centre-crop -- in front of the transform above.
+ * resize_short 0 (the default) leaves the replica as it is: an 8-bit task must be [B,3,S,S] or [B,S,S,3].
+ * S <= resize_short <= 8192 (S, the replica's image size, is the crop) switches it on for a ResNet / ViT
+ * replica; other values return SPI_ERR_INVALID_ARGUMENT, another family SPI_ERR_UNSUPPORTED, and any call
+ * once a stream workspace of the replica exists (after the first forward or warm-up) is refused like
+ * spi_model_set_image_outputs: the resampled image, max_batch x 3 x S x S fp32, belongs to the workspace.
+ * Every refusal leaves a message in spi_last_error().  spi_model_describe appends " resize<R>" (" resize256");
+ * FLOPs, weight bytes and the digest do not change.
+ *
+ * With the resize on, an SPI_DTYPE_U8 task may be [B,3,H,W] or [B,H,W,3] with any 1 <= H, W <= 8192:
+ * dims[1] == 3 means NCHW (also when dims[3] == 3), otherwise dims[3] == 3 means NHWC, anything else is the
+ * layout-mismatch error; the buffer is checked at one byte per element; a task whose resized long side would
+ * exceed 8192 is refused.  An S x S task takes the same path (one rule, not two).  fp32 tasks keep the strict
+ * [B,3,S,S] check and run as before.  One kernel launch in front of the forward writes the fp32 image the
+ * network reads; its value at output pixel (oy, ox), channel c:
+ *   1. resized size (torchvision Resize(int)): short = min(H,W) becomes R = resize_short, the long side
+ *      floor(R long / short); call the result RH x RW;
+ *   2. crop offset (torchvision CenterCrop): top = round_half_even((RH - S) / 2) -- with d = RH - S, k = d >> 1:
+ *      k if d or k is even, else k + 1 (d = 0..5: 0, 0, 1, 2, 2, 2) -- and left likewise;
+ *   3. antialiased bilinear resample (ATen _upsample_bilinear2d_aa, align_corners = false), separable, per
+ *      axis in integers: for output index i of n_out from n_in source pixels, m = max(n_in, n_out),
+ *      c2 = n_in (2 i + 1), taps j in [xmin, xmax) with xmin = max(0, floor((c2 - 2 m + n_out) / (2 n_out)))
+ *      and xmax = min(n_in, floor((c2 + 2 m + n_out) / (2 n_out))), weights
+ *      w_j = max(0, 1 - |n_out (2 j + 1) - c2| / (2 m)) -- the integer numerator converted to fp32 exactly, one
+ *      fp32 divide, one subtract -- normalised by their fp32 sum; rows first horizontally, then the vertical
+ *      pass, each sum in ascending j with one rounding per tap; only the crop's rows and columns are computed;
+ *   4. the transform above on the fp32 result v: fl(fl(v scale[c]) + shift[c]).
+ * Intermediate and result are fp32 and are NOT rounded back to 8 bits: torchvision's Resize on a uint8 tensor
+ * rounds to the nearest pixel level, so the two differ by at most half a level (scale[c] / 2 after the
+ * transform).  Against the same resample in float64 the value is within 255 (Kx + Ky + 4) 2^-24 pixel levels
+ * (Kx, Ky the largest tap counts).  For H = W = R = S the weights are exactly {1, 0} and the forward equals
+ * the plain 8-bit task's bit for bit.  The result for an image does not depend on the batch, its place in it,
+ * or on graphs being on. */
+int spi_model_set_input_resize(spi_model* model, int32_t resize_short);
 /* Classification outputs of a ResNet / ViT replica: what it hands back beside, or instead of, its
  * [B,classes] fp32 logits.  One more kernel launch after the classifier layer writes every selected
  * output of the batch; with nothing selected (image_io 0, the default) the replica is unchanged.

@@ -170,6 +170,19 @@ int spi_op_stem_pool_u8(int32_t precision, const uint8_t* x, int32_t nhwc, int32
 int spi_op_patchify(int32_t src_kind, const void* x, int32_t B, int32_t H, int32_t W, int32_t ps,
                     const float* scale_host, const float* shift_host, void* y, int32_t out_f16, void* stream);
 
+/* Resize + centre crop of 8-bit pixels (resample.hip; the contract and the arithmetic: spi_codelet.h,
+ * spi_model_set_input_resize): x bytes [B][3][H][W] (nhwc 0) or [B][H][W][3] (nhwc 1) at any byte address ->
+ * y fp32 NCHW [B][3][crop][crop]: the antialiased bilinear resample to short side resize_short, centre crop,
+ * then fl(fl(v scale[c]) + shift[c]).  scale / shift: host fp32 [3]; both null = scale 1, shift 0.
+ * 1 <= H, W <= 8192, 1 <= crop <= resize_short <= 8192, resized long side <= 8192, B <= 65535; rejected
+ * before any launch otherwise.  One launch, no workspace, no atomics. */
+int spi_op_resize_crop_u8(const uint8_t* x, int32_t nhwc, int32_t B, int32_t H, int32_t W, int32_t resize_short,
+                          int32_t crop, const float* scale_host, const float* shift_host, float* y, void* stream);
+/* The same arguments on host pointers (stream ignored): the same arithmetic (csrc/resample.hpp, shared with
+ * the kernel) run on the CPU, the reference the device op is compared with. */
+int spi_op_resize_crop_u8_host(const uint8_t* x, int32_t nhwc, int32_t B, int32_t H, int32_t W, int32_t resize_short,
+                               int32_t crop, const float* scale_host, const float* shift_host, float* y, void* stream);
+
 /* Multi-head attention over packed qkv [B*S][3*D] (fp16 or fp32), head_dim 64: ctx [B*S][D] =
  * softmax(q k^T scale + mask_bias) v per (batch, head); mask_bias fp32 [B][S] added to every query's
  * scores, or null.  Rejected before any launch: a precision other than 0 (fp32) or 1 (fp16), a null

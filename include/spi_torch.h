@@ -60,6 +60,18 @@ int spi_torch_cpu_forward(void* model_cpu, const spi_tensor_view* inputs, int nu
  * SPI_ERR_INVALID_ARGUMENT (non-finite value, a single NULL).  Set it before serving. */
 int spi_torch_set_input_transform(spi_torch_module* module, const float scale[3], const float shift[3]);
 
+/* Resize + centre crop of 8-bit image tasks on a CPU worker (the counterpart of spi_model_set_input_resize;
+ * here the crop is given, a module has no image size): once set, a 4-D SPI_DTYPE_U8 input 0 of any size up to
+ * 8192 -- [B,3,H,W], or [B,H,W,3] when dims[1] != 3 -- is resampled with ATen's antialiased bilinear
+ * interpolation in float64 (upsample_bilinear2d_aa, align_corners false) to the size the GPU codelet resizes
+ * to (short side resize_short, long side floor(resize_short long / short)), cropped to crop x crop at the same
+ * round-half-even offsets and cast to fp32; the input transform (scale 1, shift 0 when none is set) then
+ * applies as above.  The GPU codelet computes the same resample in fp32 (its header states the bound), so the
+ * two workers' images agree to that bound, not bit for bit.  (0, 0) clears it.  Returns SPI_OK, or
+ * SPI_ERR_INVALID_ARGUMENT unless 1 <= crop <= resize_short <= 8192; a task whose resized long side would
+ * exceed 8192 fails at the forward. */
+int spi_torch_set_input_resize(spi_torch_module* module, int32_t resize_short, int32_t crop);
+
 /* Classification outputs on a CPU worker (the counterpart of spi_model_set_image_outputs, same bits,
  * same output order and element types): after the module's forward, whose single output is the
  * [B,classes] logits, spi_torch_cpu_forward emits logits.float() (unless SPI_IMAGE_NO_LOGITS),

@@ -208,6 +208,7 @@ _PROTOS = {
     "spi_model_set_graphs": (None, [C.c_void_p, C.c_int32]),
     "spi_model_set_input_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "spi_model_set_image_outputs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "spi_model_set_input_resize": (C.c_int, [C.c_void_p, C.c_int32]),
     "spi_model_warmup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]),
     "spi_model_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_void_p), C.POINTER(C.c_float), C.POINTER(C.c_double),
@@ -257,6 +258,11 @@ _PROTOS = {
                                       C.c_void_p]),
     "spi_op_patchify": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_int32, C.c_void_p]),
+    "spi_op_resize_crop_u8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "spi_op_resize_crop_u8_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p,
+                                             C.c_void_p]),
     "spi_op_attention": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_float, C.c_void_p]),
     "spi_op_layernorm": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

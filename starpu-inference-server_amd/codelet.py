@@ -217,6 +217,45 @@ def check_image_outputs(io: int, top_k: int) -> None:
         raise InferenceExecutionException(f"image outputs: top_k {top_k} outside 1 .. 64, or set without SPI_IMAGE_OUT_TOPK")
 
 
+RESIZE_MAX = 8192  # largest source side, resize_short and resized long side (spi_model_set_input_resize)
+
+
+def resize_geometry(height: int, width: int, resize_short: int, crop: int) -> tuple[int, int, int, int]:
+    """(RH, RW, top, left) of spi_model_set_input_resize: torchvision's Resize(int) size -- the short side
+    becomes resize_short, the long side floor(resize_short * long / short) -- and CenterCrop's offsets,
+    round_half_even((RH - crop) / 2) and likewise for the columns."""
+    if height <= width:
+        rh, rw = resize_short, resize_short * width // height
+    else:
+        rh, rw = resize_short * height // width, resize_short
+
+    def offset(d):
+        k = d >> 1
+        return k if d % 2 == 0 or k % 2 == 0 else k + 1
+
+    return rh, rw, offset(rh - crop), offset(rw - crop)
+
+
+def check_input_resize(resize_short: int, crop: int) -> None:
+    if not 1 <= crop <= resize_short <= RESIZE_MAX:
+        raise InferenceExecutionException(
+            f"input resize: 1 <= crop <= resize_short <= {RESIZE_MAX}, got resize_short {resize_short}, crop {crop}")
+
+
+def _resize_crop(x_nchw: torch.Tensor, resize_short: int, crop: int) -> torch.Tensor:
+    """The CPU codelets' resize + centre crop of a uint8 NCHW tensor: ATen's antialiased bilinear resample in
+    float64, cropped, cast to float32 (spi_torch_set_input_resize's contract)."""
+    height, width = int(x_nchw.shape[2]), int(x_nchw.shape[3])
+    if not (1 <= height <= RESIZE_MAX and 1 <= width <= RESIZE_MAX):
+        raise InferenceExecutionException(f"[ERROR] Tensor layout mismatch: 1 <= H, W <= {RESIZE_MAX}")
+    rh, rw, top, left = resize_geometry(height, width, resize_short, crop)
+    if max(rh, rw) > RESIZE_MAX:
+        raise InferenceExecutionException(f"[ERROR] Input resize: resized long side {max(rh, rw)} above {RESIZE_MAX}")
+    y = torch.nn.functional.interpolate(x_nchw.contiguous().double(), size=(rh, rw), mode="bilinear", antialias=True,
+                                        align_corners=False)
+    return y[:, :, top:top + crop, left:left + crop].float().contiguous()
+
+
 def _pointer_array(tensors, at_least: int = 1) -> C.Array:
     """void*[]: device pointers, null-padded to at_least entries (a BERT replica's optional inputs)."""
     ptrs = [t.data_ptr() for t in tensors]
@@ -278,6 +317,7 @@ class ModelReplica:
         self.max_batch = max_batch
         self.bert_io = cfg.bert_io
         self.image_io, self.top_k = 0, 0
+        self.resize_short = 0
         if image_io_bits(image_io) or top_k:
             self.set_image_outputs(image_io, top_k)
         if graphs:
@@ -293,6 +333,7 @@ class ModelReplica:
         self.max_batch = max_batch
         self.bert_io = bert_io
         self.image_io, self.top_k = 0, 0
+        self.resize_short = 0
         if image_io_bits(image_io) or top_k:
             self.set_image_outputs(image_io, top_k)
         if graphs:
@@ -321,6 +362,18 @@ class ModelReplica:
             e.status = st
             raise e
         self.image_io, self.top_k = bits, int(top_k)
+
+    def set_input_resize(self, resize_short: int = 0) -> None:
+        """Resize + centre crop of 8-bit image tasks on the device (spi_model_set_input_resize): with
+        resize_short in image_size .. 8192 a uint8 task may be [B,3,H,W] or [B,H,W,3] of any size up to 8192; it
+        is resampled (antialiased bilinear) to short side resize_short and centre-cropped to the replica's image
+        before the input transform.  0 switches it off.  Only before the first forward or warm-up."""
+        st = lib.spi_model_set_input_resize(self.handle, int(resize_short))
+        if st != N.SPI_OK:
+            e = InferenceExecutionException(f"set_input_resize failed: {N.last_error()}")
+            e.status = st
+            raise e
+        self.resize_short = int(resize_short)
 
     def warmup(self, stream: int, batch: int, seq: int = 0, with_mask: bool = True) -> None:
         """Allocate `stream`'s workspace and pre-capture its (batch, seq) graph (per-worker warm-up)."""
@@ -458,11 +511,21 @@ class TorchCpuForward:
     bits as image_io_bits takes them.  The module's [B,classes] logits become, in order: logits.float()
     (unless "no_logits"), softmax(logits.float(), -1), and the first k values / int64 indices of the stable
     descending sort (values taken from the probabilities with "topk_probs").
+
+    input_resize=(resize_short, crop): the GPU codelet's resize + centre crop (spi_model_set_input_resize).
+    A 4-D uint8 input 0 of any size, in either layout, is resampled with ATen's antialiased bilinear
+    interpolation in float64 to short side resize_short, centre-cropped to crop x crop by the same offset rule,
+    cast to float32 and then transformed (input_transform, default scale 1, shift 0).
     """
 
-    def __init__(self, module: torch.nn.Module, input_transform=None, image_outputs=None):
+    def __init__(self, module: torch.nn.Module, input_transform=None, image_outputs=None, input_resize=None):
         self.module = module
         self.input_transform = None
+        self.input_resize = None
+        if input_resize is not None:
+            resize_short, crop = int(input_resize[0]), int(input_resize[1])
+            check_input_resize(resize_short, crop)
+            self.input_resize = (resize_short, crop)
         self.image_io, self.top_k = 0, 0
         if image_outputs is not None:
             io, top_k = image_io_bits(image_outputs[0]), int(image_outputs[1])
@@ -480,15 +543,19 @@ class TorchCpuForward:
     def _call(self, _model, inputs, n_in, outputs, n_out, err, errlen):
         try:
             xs = [_view(inputs[i]) for i in range(n_in)]
-            if self.input_transform is not None and n_in and xs[0].dtype == torch.uint8 and xs[0].dim() == 4:
+            if (self.input_transform is not None or self.input_resize is not None) and n_in and \
+                    xs[0].dtype == torch.uint8 and xs[0].dim() == 4:
                 x = xs[0]
                 if x.shape[1] != 3:
                     if x.shape[3] != 3:
                         raise InferenceExecutionException(
                             "[ERROR] Tensor layout mismatch: expected [B,3,H,W] or [B,H,W,3]")
                     x = x.permute(0, 3, 1, 2)
-                scale, shift = self.input_transform
-                xs[0] = x.float().contiguous().mul(scale).add(shift)
+                x = _resize_crop(x, *self.input_resize) if self.input_resize is not None else x.float().contiguous()
+                if self.input_transform is not None:
+                    scale, shift = self.input_transform
+                    x = x.mul(scale).add(shift)
+                xs[0] = x
             with torch.inference_mode():
                 result = self.module(*xs)
             outs: list = []

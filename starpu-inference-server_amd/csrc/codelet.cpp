@@ -423,6 +423,14 @@ int spi_model_set_image_outputs(spi_model* m, int32_t image_io, int32_t top_k) {
   return st;
 }
 
+int spi_model_set_input_resize(spi_model* m, int32_t resize_short) {
+  if (!m) return SPI_ERR_INVALID_ARGUMENT;
+  std::string err;
+  const int st = m->impl->set_input_resize(resize_short, err);
+  if (st != SPI_OK) tl_last_error = err;
+  return st;
+}
+
 int spi_model_warmup(spi_model* m, void* stream, int64_t batch, int64_t seq, int32_t with_mask) {
   if (!m) return SPI_ERR_INVALID_ARGUMENT;
   try {

@@ -5,6 +5,7 @@
 #include "gconv.hpp"
 #include "gemm_plan.hpp"
 #include "model.hpp"
+#include "resample.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -25,7 +26,8 @@ std::mutex g_capture_mu;
 // (0: the unfused stem's output, 1: the max pool's output = the first block's input); the
 // average-pooled features (when avgpool + FC do not run as one GEMM).
 // The logits scratch (here and for ViT): fp32 [max_batch][classes] under SPI_IMAGE_NO_LOGITS, else empty.
-enum RnBuf { kRnIngest, kRnAct0, kRnAct1, kRnAct2, kRnAct3, kRnAct4, kRnPooled, kRnLogits, kRnBufs };
+// The resampled image (here and for ViT): fp32 NCHW [max_batch][3][image][image] with the input resize on, else empty.
+enum RnBuf { kRnIngest, kRnAct0, kRnAct1, kRnAct2, kRnAct3, kRnAct4, kRnPooled, kRnLogits, kRnResized, kRnBufs };
 // BERT: hidden rows fp32 (fold: the pre-LN2 rows b as two fp16 planes) and their compute-type copy;
 // qkv; ctx; the attention block's output a, fp32 (fold: the pre-LN1 rows as two planes); the FFN
 // hidden rows; the LayerNorm-fold row statistics S1 (of a) and S2 (of b); the final LayerNorm's
@@ -33,7 +35,7 @@ enum RnBuf { kRnIngest, kRnAct0, kRnAct1, kRnAct2, kRnAct3, kRnAct4, kRnPooled, 
 enum BertBuf { kBtHidden, kBtHidden16, kBtQkv, kBtCtx, kBtAttn, kBtFfn, kBtStats1, kBtStats2, kBtCls, kBtBufs };
 // ViT: patches; projected patches f32; residual stream x f32 (fold: two fp16 planes); LN output; qkv;
 // ctx; mlp hidden; the LayerNorm'd class-token rows; the LayerNorm-fold row statistics of x.
-enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, kVtStats, kVtLogits, kVtBufs };
+enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, kVtStats, kVtLogits, kVtResized, kVtBufs };
 
 // ---------------------------------------------------------------------------
 // Workspace: activation buffers for one stream at max_batch.
@@ -108,11 +110,26 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
     const bool u8 = a.input_types[0] == SPI_DTYPE_U8;
     if (!u8 && a.input_types[0] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Input type mismatch");
     const std::string sz = std::to_string(image);
-    const bool nchw = a.num_dims[0] == 4 && a.dims[0][1] == 3 && a.dims[0][2] == image && a.dims[0][3] == image;
-    const bool nhwc = a.num_dims[0] == 4 && a.dims[0][1] == image && a.dims[0][2] == image && a.dims[0][3] == 3;
-    if (!nchw && !(u8 && nhwc))
-      throw std::runtime_error("[ERROR] Tensor layout mismatch: expected [B,3," + sz + "," + sz + "]" +
-                               (u8 ? " or [B," + sz + "," + sz + ",3]" : ""));
+    if (u8 && resize_short_) {
+      // the input resize: a source of any size in either layout; dims[1] == 3 is NCHW, also when dims[3] == 3
+      const int64_t* d = a.dims[0];
+      const bool nchw = a.num_dims[0] == 4 && d[1] == 3, nhwc = a.num_dims[0] == 4 && !nchw && d[3] == 3;
+      const int64_t H = nchw ? d[2] : d[1], W = nchw ? d[3] : d[2];
+      if ((!nchw && !nhwc) || H < 1 || W < 1 || H > kResizeMax || W > kResizeMax)
+        throw std::runtime_error("[ERROR] Tensor layout mismatch: expected [B,3,H,W] or [B,H,W,3] with 1 <= H, W <= " +
+                                 std::to_string(kResizeMax) + " (input resize " + std::to_string(resize_short_) + ")");
+      const ResizeGeom g = resize_geom((int)H, (int)W, resize_short_, image);
+      if (std::max(g.RH, g.RW) > kResizeMax)
+        throw std::runtime_error("[ERROR] Input resize: a " + std::to_string(H) + "x" + std::to_string(W) +
+                                 " source resized to short side " + std::to_string(resize_short_) + " has long side " +
+                                 std::to_string(std::max(g.RH, g.RW)) + ", above " + std::to_string(kResizeMax));
+    } else {
+      const bool nchw = a.num_dims[0] == 4 && a.dims[0][1] == 3 && a.dims[0][2] == image && a.dims[0][3] == image;
+      const bool nhwc = a.num_dims[0] == 4 && a.dims[0][1] == image && a.dims[0][2] == image && a.dims[0][3] == 3;
+      if (!nchw && !(u8 && nhwc))
+        throw std::runtime_error("[ERROR] Tensor layout mismatch: expected [B,3," + sz + "," + sz + "]" +
+                                 (u8 ? " or [B," + sz + "," + sz + ",3]" : ""));
+    }
     if (in_bytes[0] < (size_t)elems(0) * (u8 ? 1 : 4)) throw std::runtime_error("[ERROR] Input buffer too small");
     expect_out = (size_t)B * m_.classes * 4;
     if (image_io_) {  // logits (unless NO_LOGITS), probabilities, top-k values, top-k indices
@@ -150,11 +167,20 @@ void Model::check_io(const spi_codelet_args& a, const size_t* in_bytes, const si
   }
 }
 
-int Model::input_kind(const spi_codelet_args& a) const {
-  if ((m_.family != SPI_FAMILY_RESNET && m_.family != SPI_FAMILY_VIT) || a.input_types[0] != SPI_DTYPE_U8)
-    return kSrcF32Nchw;
+ImageSrc Model::input_kind(const spi_codelet_args& a) const {
+  ImageSrc src;
+  if ((m_.family != SPI_FAMILY_RESNET && m_.family != SPI_FAMILY_VIT) || a.input_types[0] != SPI_DTYPE_U8) return src;
+  const int64_t* d = a.dims[0];
+  if (resize_short_) {  // every 8-bit task is resampled, an S x S one too: [B,3,H,W] is NCHW, else [B,H,W,3]
+    const bool nchw = d[1] == 3;
+    src.kind = nchw ? kSrcU8Nchw : kSrcU8Nhwc;
+    src.H = (int)(nchw ? d[2] : d[1]);
+    src.W = (int)(nchw ? d[3] : d[2]);
+    return src;
+  }
   // [B,3,S,S] is NCHW (also when S == 3), else check_io accepted [B,S,S,3]
-  return a.dims[0][1] == 3 && a.dims[0][2] == m_.image && a.dims[0][3] == m_.image ? kSrcU8Nchw : kSrcU8Nhwc;
+  src.kind = d[1] == 3 && d[2] == m_.image && d[3] == m_.image ? kSrcU8Nchw : kSrcU8Nhwc;
+  return src;
 }
 
 int Model::set_input_transform(const float* scale, const float* shift) {
@@ -203,16 +229,41 @@ int Model::set_image_outputs(int io, int top_k, std::string& err) {
                   "a stream workspace of the replica exists; call before the first forward or warm-up");
   image_io_ = io;
   top_k_ = top_k;
-  desc_io_.clear();
-  if (io) {
+  rebuild_desc();
+  return SPI_OK;
+}
+
+int Model::set_input_resize(int resize_short, std::string& err) {
+  auto refuse = [&](int status, const std::string& msg) {
+    err = "input resize: " + msg;
+    return status;
+  };
+  if (m_.family != SPI_FAMILY_RESNET && m_.family != SPI_FAMILY_VIT)
+    return refuse(SPI_ERR_UNSUPPORTED, "only ResNet / ViT replicas take 8-bit image tasks");
+  if (resize_short != 0 && (resize_short < m_.image || resize_short > kResizeMax))
+    return refuse(SPI_ERR_INVALID_ARGUMENT, "resize_short " + std::to_string(resize_short) + " outside " +
+                                                std::to_string(m_.image) + " (the replica's image size) .. " +
+                                                std::to_string(kResizeMax) + "; 0 switches the resize off");
+  std::lock_guard<std::mutex> lk(mu_);
+  if (!ws_.empty())
+    return refuse(SPI_ERR_INVALID_ARGUMENT,
+                  "a stream workspace of the replica exists; call before the first forward or warm-up");
+  resize_short_ = resize_short;
+  rebuild_desc();
+  return SPI_OK;
+}
+
+void Model::rebuild_desc() {
+  desc_ext_ = m_.desc;
+  if (const int io = image_io_) {
     std::string outs;
     for (const auto& o : {std::make_pair(!(io & SPI_IMAGE_NO_LOGITS), std::string("logits")),
                           std::make_pair((io & SPI_IMAGE_OUT_PROBS) != 0, std::string("probs")),
-                          std::make_pair((io & SPI_IMAGE_OUT_TOPK) != 0, "top" + std::to_string(top_k))})
+                          std::make_pair((io & SPI_IMAGE_OUT_TOPK) != 0, "top" + std::to_string(top_k_))})
       if (o.first) outs += (outs.empty() ? "" : ",") + o.second;
-    desc_io_ = m_.desc + " out[" + outs + "]";
+    desc_ext_ += " out[" + outs + "]";
   }
-  return SPI_OK;
+  if (resize_short_) desc_ext_ += " resize" + std::to_string(resize_short_);
 }
 
 double Model::flops(int64_t B) const {
@@ -509,6 +560,7 @@ std::vector<size_t> Model::workspace_sizes_resnet(size_t& partial) const {
   for (int i = kRnAct0; i <= kRnAct4; ++i) sz[i] = amax * ea;
   sz[kRnPooled] = (size_t)B * m_.feat * ea;  // fp32 under F16M: the FC's A
   sz[kRnLogits] = (image_io_ & SPI_IMAGE_NO_LOGITS) ? (size_t)B * m_.classes * 4 : 0;
+  sz[kRnResized] = resize_short_ ? (size_t)B * 3 * m_.image * m_.image * 4 : 0;
   return sz;
 }
 
@@ -540,6 +592,7 @@ std::vector<size_t> Model::workspace_sizes_vit(size_t& partial) const {
   sz[kVtCls] = B * D * es;
   sz[kVtStats] = T * (D / 64) * 8;
   sz[kVtLogits] = (image_io_ & SPI_IMAGE_NO_LOGITS) ? B * m_.classes * 4 : 0;
+  sz[kVtResized] = resize_short_ ? B * 3 * m_.image * m_.image * 4 : 0;
   partial = std::max({partial, linear_partial(m_.patch_proj, (int)B * m_.npatch), layers_partial((int)T),
                       linear_partial(m_.head, (int)B)});
   return sz;
@@ -853,11 +906,24 @@ void Model::body_vit_folded(Workspace& w, int B, hipStream_t s) {
 // ---------------------------------------------------------------------------
 // Forward: prologue -> body (graph-capturable) -> epilogue, each dispatched by family (model.hpp)
 // ---------------------------------------------------------------------------
-void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStream_t s, int src) {
+void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStream_t s, ImageSrc isrc) {
   const int D = m_.D, image = m_.image;
   const bool f16 = m_.f16;
+  int src = isrc.kind;
+  const void* image_in = in[0];
+  if (isrc.H > 0) {
+    // the input resize: one launch writes the normalised fp32 NCHW image into the workspace, and the
+    // family's fp32-source prologue below reads it as it reads an fp32 task
+    if (!resize_short_) throw std::logic_error("prologue: a resized source without the input resize");
+    float* y = static_cast<float*>(w.bufs[m_.family == SPI_FAMILY_RESNET ? (int)kRnResized : (int)kVtResized]);
+    prof_op(s, "resize_crop_u8", 0, (double)B * 3 * ((double)isrc.H * isrc.W + (double)image * image * 4), [&] {
+      resize_crop_u8(in[0], src == kSrcU8Nhwc, B, isrc.H, isrc.W, resize_short_, image, input_xf_, y, s);
+    });
+    image_in = y;
+    src = kSrcF32Nchw;
+  }
   switch (m_.family) {
-    case SPI_FAMILY_RESNET: return prologue_resnet(w, B, in[0], s, src);
+    case SPI_FAMILY_RESNET: return prologue_resnet(w, B, image_in, s, src);
     case SPI_FAMILY_BERT: {
       const double T = (double)B * S;
       // the attention mask's additive bias is written by the embedding kernel (round 6: one launch
@@ -877,7 +943,7 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
     }
     case SPI_FAMILY_VIT:
       return prof_op(s, "patchify", 0, (double)B * 3 * image * image * (4 + (f16 ? 2 : 4)), [&] {
-        patchify(in[0], w.bufs[kVtPatches], B, 3, image, image, m_.patch, f16, s, src, input_xf_);
+        patchify(image_in, w.bufs[kVtPatches], B, 3, image, image, m_.patch, f16, s, src, input_xf_);
       });
   }
 }
@@ -929,7 +995,7 @@ void Model::run_image_outputs(const float* logits, int B, void* const* out, hipS
   });
 }
 
-void Model::forward(hipStream_t s, int B, int S, size_t n, const void* const* in, void* const* out, int src) {
+void Model::forward(hipStream_t s, int B, int S, size_t n, const void* const* in, void* const* out, ImageSrc src) {
   if (device_ < 0) throw std::runtime_error("host-only replica (device < 0) cannot run a forward");
   if (m_.family == SPI_FAMILY_AFFINE) {
     affine(static_cast<const float*>(in[0]), static_cast<float*>(out[0]), n, m_.aff_scale, m_.aff_shift, s);

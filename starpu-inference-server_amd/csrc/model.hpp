@@ -46,7 +46,7 @@ class Model {
   int max_batch() const { return m_.max_batch; }
   size_t weight_bytes() const { return m_.blob_bytes; }
   uint64_t weight_digest() const { return m_.digest; }
-  const std::string& describe() const { return image_io_ ? desc_io_ : m_.desc; }
+  const std::string& describe() const { return image_io_ || resize_short_ ? desc_ext_ : m_.desc; }
   double flops(int64_t batch) const;
   void set_graphs(bool on) { graphs_ = on; }
 
@@ -54,9 +54,10 @@ class Model {
   // with the reference's message wording on mismatch.
   void check_io(const spi_codelet_args& a, const size_t* in_bytes,
                 const size_t* out_bytes) const;
-  // What input 0 of a task that passed check_io holds (SrcKind): fp32 NCHW, or for a ResNet / ViT
-  // task of SPI_DTYPE_U8 the layout its dims name ([B,3,S,S] NCHW, [B,S,S,3] NHWC).
-  int input_kind(const spi_codelet_args& a) const;
+  // What input 0 of a task that passed check_io holds: fp32 NCHW, or for a ResNet / ViT task of
+  // SPI_DTYPE_U8 the layout its dims name ([B,3,S,S] NCHW, [B,S,S,3] NHWC) -- with the input resize on,
+  // [B,3,H,W] / [B,H,W,3] and the source size, which sends the task through the resample first.
+  ImageSrc input_kind(const spi_codelet_args& a) const;
   // The input transform of 8-bit image tasks (spi_model_set_input_transform); null pointers reset
   // it to scale 1, shift 0.  Returns an spi_status.  Not synchronised with forwards in flight.
   int set_input_transform(const float* scale, const float* shift);
@@ -64,11 +65,15 @@ class Model {
   // and the top-k count.  Returns an spi_status and, on refusal, the message in `err`.  Refused once a
   // stream workspace exists: the logits scratch of SPI_IMAGE_NO_LOGITS is sized with the workspace.
   int set_image_outputs(int image_io, int top_k, std::string& err);
+  // Resize + centre crop of 8-bit image tasks (spi_model_set_input_resize): 0 off, else the short side the
+  // source is resized to before the centre crop to the replica's image.  Returns an spi_status and, on
+  // refusal, the message in `err`.  Refused once a stream workspace exists: the resampled image lives there.
+  int set_input_resize(int resize_short, std::string& err);
   // Enqueue the forward on `s`; never synchronises.
-  // S: BERT sequence length (ignored otherwise); n: AFFINE element count; src: input 0's SrcKind
-  // (read by the prologue only -- the captured body does not depend on it).
+  // S: BERT sequence length (ignored otherwise); n: AFFINE element count; src: what input 0 holds
+  // (input_kind; read by the prologue only -- the captured body does not depend on it).
   void forward(hipStream_t s, int batch, int S, size_t n, const void* const* in, void* const* out,
-               int src = kSrcF32Nchw);
+               ImageSrc src = ImageSrc{});
   // Allocate the stream's workspace and capture its (batch, S, mask) graph ahead of serving.
   void warmup(hipStream_t s, int batch, int S, bool mask);
 
@@ -106,7 +111,7 @@ class Model {
   hipGraphExec_t graph(Workspace& w, int batch, int S, hipStream_t s);
   // Forward: prologue (reads the task's input buffers) -> body (workspace only, graph-capturable)
   // -> epilogue (writes the task's output buffer); each dispatches once to its family's plan.
-  void prologue(Workspace& w, int batch, int S, const void* const* in, hipStream_t s, int src = kSrcF32Nchw);
+  void prologue(Workspace& w, int batch, int S, const void* const* in, hipStream_t s, ImageSrc src = ImageSrc{});
   void body(Workspace& w, int batch, int S, hipStream_t s);
   void epilogue(Workspace& w, int batch, int S, void* const* out, hipStream_t s);
   // Bytes per workspace buffer of the family (indexed by its buffer enum, model.cpp) at max_batch;
@@ -179,7 +184,9 @@ class Model {
   int stem_pr_ = SPI_STEM_PR;  // the fused stem's workgroup shape (0 = auto, stem.hip)
   InputXf input_xf_;  // ResNet / ViT: the transform of 8-bit image tasks, passed to the prologue's kernel
   int image_io_ = 0, top_k_ = 0;  // ResNet / ViT: SPI_IMAGE_* bits and the top-k count (set_image_outputs)
-  std::string desc_io_;           // m_.desc + " out[...]" while image_io_ is set
+  int resize_short_ = 0;          // ResNet / ViT: the input resize of 8-bit tasks (set_input_resize), 0 = off
+  std::string desc_ext_;          // m_.desc + " out[...]" (image_io_) + " resize<R>" (resize_short_) while either is set
+  void rebuild_desc();
   // SPI_QKV_ATTN: 0 the QKV GEMM + attention launches (A/B); 1 (default) the fused kernel for S <= 128;
   // 2 also for 129..256 tokens (ViT-L at 197: correct, but -4 % under the four streams)
   int qkv_fused_ = 1;

@@ -5,12 +5,14 @@
 #include <cstdio>
 #include <exception>
 #include <string>
+#include <vector>
 
 #include "../../include/spi_ops.h"
 #include "gconv.hpp"
 #include "gemm_plan.hpp"
 #include "ln_fold_pack.hpp"
 #include "pack.hpp"
+#include "resample.hpp"
 #include "spi_kernels.hpp"
 
 extern "C" void spi_set_last_error(const char* msg);
@@ -379,6 +381,77 @@ int spi_op_patchify(int32_t src_kind, const void* x, int32_t B, int32_t H, int32
   return guarded([&] {
     spi::patchify(x, y, B, 3, H, W, ps, out_f16 != 0, static_cast<hipStream_t>(stream), src_kind, xf);
     return check_launch();
+  });
+}
+
+namespace {
+
+const char* resize_crop_check(const void* x, int32_t B, int32_t H, int32_t W, int32_t R, int32_t S, const void* y) {
+  if (!x || !y || B < 1 || B > 65535 || H < 1 || W < 1 || H > spi::kResizeMax || W > spi::kResizeMax || S < 1 ||
+      R < S || R > spi::kResizeMax)
+    return "invalid resize_crop_u8 arguments: 1 <= H, W <= 8192, 1 <= crop <= resize_short <= 8192, 1 <= B <= 65535";
+  const spi::ResizeGeom g = spi::resize_geom(H, W, R, S);
+  return g.RH > spi::kResizeMax || g.RW > spi::kResizeMax ? "resize_crop_u8: the resized long side exceeds 8192"
+                                                           : nullptr;
+}
+
+}  // namespace
+
+int spi_op_resize_crop_u8(const uint8_t* x, int32_t nhwc, int32_t B, int32_t H, int32_t W, int32_t resize_short,
+                          int32_t crop, const float* scale, const float* shift, float* y, void* stream) {
+  spi::InputXf xf;
+  if (const char* bad = resize_crop_check(x, B, H, W, resize_short, crop, y)) return fail(bad);
+  if (!input_xf(scale, shift, &xf)) return fail("resize_crop_u8: scale and shift come both or neither");
+  return guarded([&] {
+    spi::resize_crop_u8(x, nhwc != 0, B, H, W, resize_short, crop, xf, y, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+// The kernel's arithmetic on the CPU: per image, the horizontal samples of every source row the crop's
+// rows need (ascending taps, resample.hpp), then the vertical pass over them, then the transform.
+int spi_op_resize_crop_u8_host(const uint8_t* x, int32_t nhwc, int32_t B, int32_t H, int32_t W, int32_t resize_short,
+                               int32_t crop, const float* scale, const float* shift, float* y, void*) {
+  spi::InputXf xf;
+  if (const char* bad = resize_crop_check(x, B, H, W, resize_short, crop, y)) return fail(bad);
+  if (!input_xf(scale, shift, &xf)) return fail("resize_crop_u8: scale and shift come both or neither");
+  return guarded([&] {
+    const int S = crop;
+    const spi::ResizeGeom g = spi::resize_geom(H, W, resize_short, S);
+    const int band0 = spi::axis_taps(g.top, H, g.RH).lo, band1 = spi::axis_taps(g.top + S - 1, H, g.RH).hi;
+    std::vector<spi::AxisTaps> cx(S);
+    std::vector<float> totx(S), hrows((size_t)(band1 - band0) * 3 * S);
+    for (int ox = 0; ox < S; ++ox) {
+      cx[ox] = spi::axis_taps(g.left + ox, W, g.RW);
+      totx[ox] = spi::tap_total(cx[ox]);
+    }
+    const size_t plane = (size_t)H * W;
+    for (int b = 0; b < B; ++b) {
+      const uint8_t* img = x + (size_t)b * plane * 3;
+      auto pixel = [&](int c, int r, int j) {
+        return static_cast<float>(nhwc ? img[((size_t)r * W + j) * 3 + c] : img[(size_t)c * plane + (size_t)r * W + j]);
+      };
+      for (int r = band0; r < band1; ++r)
+        for (int c = 0; c < 3; ++c)
+          for (int ox = 0; ox < S; ++ox) {
+            float h = 0.0f;
+            for (int j = cx[ox].lo; j < cx[ox].hi; ++j)
+              h = spi::tap_acc(spi::tap_norm(spi::tap_weight(cx[ox], j), totx[ox]), pixel(c, r, j), h);
+            hrows[((size_t)(r - band0) * 3 + c) * S + ox] = h;
+          }
+      for (int oy = 0; oy < S; ++oy) {
+        const spi::AxisTaps cy = spi::axis_taps(g.top + oy, H, g.RH);
+        const float toty = spi::tap_total(cy);
+        for (int c = 0; c < 3; ++c)
+          for (int ox = 0; ox < S; ++ox) {
+            float acc = 0.0f;
+            for (int r = cy.lo; r < cy.hi; ++r)
+              acc = spi::tap_acc(spi::tap_norm(spi::tap_weight(cy, r), toty), hrows[((size_t)(r - band0) * 3 + c) * S + ox], acc);
+            y[(((size_t)b * 3 + c) * S + oy) * S + ox] = spi::resample_xf(acc, xf.scale[c], xf.shift[c]);
+          }
+      }
+    }
+    return 0;
   });
 }
 

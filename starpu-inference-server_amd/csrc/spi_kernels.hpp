@@ -99,6 +99,20 @@ __device__ __forceinline__ float input_xf_apply(unsigned char p, const InputXf& 
   return input_xf_apply(p, sc, sh);
 }
 
+// What input 0 of an image task holds: its kind and, for an 8-bit task of a replica with the input
+// resize on (H > 0), the source size the prologue resamples to the replica's image first.
+struct ImageSrc {
+  int kind = kSrcF32Nchw;
+  int H = 0, W = 0;
+};
+// Resize + centre crop of 8-bit pixels (resample.hip; arithmetic: resample.hpp): x bytes [B][3][H][W], or
+// [B][H][W][3] with nhwc, at any byte address -> y fp32 NCHW [B][3][crop][crop], the antialiased bilinear
+// resample to short side resize_short, centre-cropped, under the transform xf.  1 <= H, W <= 8192,
+// 1 <= crop <= resize_short <= 8192, resized long side <= 8192, B <= 65535; else throws
+// std::invalid_argument before any launch.  One launch, no workspace.
+void resize_crop_u8(const void* x, bool nhwc, int B, int H, int W, int resize_short, int crop, const InputXf& xf,
+                    float* y, hipStream_t s);
+
 // Image (3 channels for an 8-bit source) -> NHWC (compute type) with channels zero-padded to cpad.
 void ingest_nchw(const void* x, void* y, int B, int C, int H, int W, int cpad,
                  bool f16, hipStream_t s, int src = kSrcF32Nchw, const InputXf& xf = InputXf{});

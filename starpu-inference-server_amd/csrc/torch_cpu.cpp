@@ -37,9 +37,13 @@ struct spi_torch_module {
   float xf_scale[3] = {1.f, 1.f, 1.f}, xf_shift[3] = {0.f, 0.f, 0.f};
   // spi_torch_set_image_outputs: SPI_IMAGE_* bits and the top-k count
   int32_t image_io = 0, top_k = 0;
+  // spi_torch_set_input_resize: 8-bit image inputs of any size are resampled and centre-cropped first (0 = off)
+  int32_t resize_short = 0, crop = 0;
 };
 
 namespace {
+
+constexpr int64_t kResizeMax = 8192;  // as spi_model_set_input_resize: sources, resize_short, resized long side
 
 void put_err(char* err, size_t errlen, const std::string& msg) {
   if (err && errlen) std::snprintf(err, errlen, "%s", msg.c_str());
@@ -136,16 +140,40 @@ int spi_torch_cpu_forward(void* model_cpu, const spi_tensor_view* inputs, int ni
       // assign_tensor_view: non-owning row-major view, dims from the layout
       std::vector<int64_t> dims(inputs[i].shape, inputs[i].shape + inputs[i].ndim);
       at::Tensor t = torch::from_blob(inputs[i].data, dims, torch::TensorOptions().dtype(to_scalar(inputs[i].dtype)));
-      if (i == 0 && m->xf_set && inputs[i].dtype == SPI_DTYPE_U8 && inputs[i].ndim == 4) {
+      if (i == 0 && (m->xf_set || m->resize_short) && inputs[i].dtype == SPI_DTYPE_U8 && inputs[i].ndim == 4) {
         // the GPU codelet's 8-bit image contract (spi_model_set_input_transform): [B,3,S,S] is NCHW,
         // [B,S,S,3] NHWC; fl(fl(p * scale[c]) + shift[c]) as two ATen ops, so never an FMA
         if (dims[1] != 3) {
           if (dims[3] != 3) throw std::runtime_error("[ERROR] Tensor layout mismatch: expected [B,3,H,W] or [B,H,W,3]");
           t = t.permute({0, 3, 1, 2});
         }
-        const at::Tensor sc = torch::from_blob(m->xf_scale, {1, 3, 1, 1}, torch::kFloat);
-        const at::Tensor sh = torch::from_blob(m->xf_shift, {1, 3, 1, 1}, torch::kFloat);
-        t = t.to(at::kFloat).contiguous().mul(sc).add(sh);
+        if (m->resize_short) {
+          // spi_torch_set_input_resize: ATen's antialiased bilinear in float64 to the GPU codelet's resized
+          // size, the centre crop at its round-half-even offsets, then fp32
+          const int64_t H = t.size(2), W = t.size(3), R = m->resize_short, S = m->crop;
+          if (H < 1 || W < 1 || H > kResizeMax || W > kResizeMax)
+            throw std::runtime_error("[ERROR] Tensor layout mismatch: 1 <= H, W <= 8192");
+          const int64_t RH = H <= W ? R : R * H / W, RW = H <= W ? R * W / H : R;
+          if (std::max(RH, RW) > kResizeMax)
+            throw std::runtime_error("[ERROR] Input resize: resized long side " + std::to_string(std::max(RH, RW)) +
+                                     " above 8192");
+          auto offset = [](int64_t d) {
+            const int64_t k = d >> 1;
+            return (d & 1) == 0 || (k & 1) == 0 ? k : k + 1;
+          };
+          t = at::_upsample_bilinear2d_aa(t.contiguous().to(at::kDouble), {RH, RW}, /*align_corners=*/false)
+                  .narrow(2, offset(RH - S), S)
+                  .narrow(3, offset(RW - S), S)
+                  .to(at::kFloat)
+                  .contiguous();
+        } else {
+          t = t.to(at::kFloat).contiguous();
+        }
+        if (m->xf_set) {
+          const at::Tensor sc = torch::from_blob(m->xf_scale, {1, 3, 1, 1}, torch::kFloat);
+          const at::Tensor sh = torch::from_blob(m->xf_shift, {1, 3, 1, 1}, torch::kFloat);
+          t = t.mul(sc).add(sh);
+        }
       }
       args.emplace_back(std::move(t));
     }
@@ -211,6 +239,18 @@ int spi_torch_set_input_transform(spi_torch_module* m, const float scale[3], con
     m->xf_shift[c] = shift[c];
   }
   m->xf_set = true;
+  return SPI_OK;
+}
+
+int spi_torch_set_input_resize(spi_torch_module* m, int32_t resize_short, int32_t crop) {
+  if (!m) return SPI_ERR_INVALID_ARGUMENT;
+  if (resize_short == 0 && crop == 0) {
+    m->resize_short = m->crop = 0;
+    return SPI_OK;
+  }
+  if (crop < 1 || resize_short < crop || resize_short > kResizeMax) return SPI_ERR_INVALID_ARGUMENT;
+  m->resize_short = resize_short;
+  m->crop = crop;
   return SPI_OK;
 }
 

@@ -40,6 +40,7 @@ _PROTOS = {
                                         C.c_int, C.c_char_p, C.c_size_t]),
     "spi_torch_set_input_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "spi_torch_set_image_outputs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "spi_torch_set_input_resize": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     "spi_torch_named_tensors": (C.c_int32, [C.c_void_p, C.POINTER(C.POINTER(N.NamedTensor))]),
     "spi_torch_create_replica": (C.c_void_p, [C.c_void_p, C.c_int32, C.POINTER(N.ModelConfig), C.c_char_p,
                                               C.c_size_t]),
@@ -95,6 +96,13 @@ class TorchScriptModule:
         is fed to the module as float32(p) * scale[c] + shift[c] in NCHW.  (None, None) clears it."""
         if lib.spi_torch_set_input_transform(self.handle, N.float3(scale), N.float3(shift)) != N.SPI_OK:
             raise InferenceExecutionException("set_input_transform: three finite values each for scale and shift")
+
+    def set_input_resize(self, resize_short: int = 0, crop: int = 0) -> None:
+        """Resize + centre crop of 8-bit image inputs of the CPU codelet (spi_torch_set_input_resize): a 4-D
+        uint8 input 0 of any size is resampled (ATen antialiased bilinear, float64) to short side resize_short,
+        centre-cropped to crop x crop and cast to float32 before the input transform.  (0, 0) clears it."""
+        if lib.spi_torch_set_input_resize(self.handle, int(resize_short), int(crop)) != N.SPI_OK:
+            raise InferenceExecutionException("set_input_resize: 1 <= crop <= resize_short <= 8192, or (0, 0)")
 
     def set_image_outputs(self, image_io=0, top_k: int = 0) -> None:
         """Classification outputs of the CPU codelet (spi_torch_set_image_outputs): the module's [B,classes]

@@ -306,6 +306,33 @@ def patchify(src_kind, x, ps, scale=None, shift=None, out_f16=False, stream=None
     return out
 
 
+def resize_crop_u8(x_u8, resize_short, crop, scale=None, shift=None, nhwc=False, out=None, stream=None):
+    """Resize + centre crop of 8-bit pixels on the device (spi_op_resize_crop_u8): x_u8 uint8 [B][3][H][W], or
+    [B][H][W][3] with nhwc, contiguous, at any byte address -> float32 [B][3][crop][crop]: the antialiased
+    bilinear resample to short side resize_short, centre crop, then float32(v) * scale[c] + shift[c]."""
+    if x_u8.dtype != torch.uint8 or not x_u8.is_contiguous() or x_u8.dim() != 4 or x_u8.shape[3 if nhwc else 1] != 3:
+        raise OpError("resize_crop_u8: a contiguous uint8 tensor, [B][3][H][W] or with nhwc [B][H][W][3]")
+    B, H, W_ = (x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]) if nhwc else (x_u8.shape[0], x_u8.shape[2], x_u8.shape[3])
+    if out is None:
+        out = torch.empty(B, 3, crop, crop, device=x_u8.device, dtype=torch.float32)
+    _check(lib.spi_op_resize_crop_u8(_ptr(x_u8), int(nhwc), B, H, W_, resize_short, crop, N.float3(scale),
+                                     N.float3(shift), _ptr(out), _stream(stream)))
+    return out
+
+
+def resize_crop_u8_host(x_u8: np.ndarray, resize_short, crop, scale=None, shift=None, nhwc=False) -> np.ndarray:
+    """resize_crop_u8's arithmetic on the CPU (spi_op_resize_crop_u8_host; the header the kernel shares):
+    a uint8 numpy array in, float32 [B][3][crop][crop] out.  Needs no device."""
+    x = np.ascontiguousarray(x_u8)
+    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[3 if nhwc else 1] != 3:
+        raise OpError("resize_crop_u8_host: a uint8 array, [B][3][H][W] or with nhwc [B][H][W][3]")
+    B, H, W_ = (x.shape[0], x.shape[1], x.shape[2]) if nhwc else (x.shape[0], x.shape[2], x.shape[3])
+    out = np.empty((B, 3, crop, crop), np.float32)
+    _check(lib.spi_op_resize_crop_u8_host(x.ctypes.data, int(nhwc), B, H, W_, resize_short, crop, N.float3(scale),
+                                          N.float3(shift), out.ctypes.data, None))
+    return out
+
+
 # ---- LayerNorm folded across GEMMs (spi_ops.h: spi_op_fold_linear / spi_op_gemm_ln / ..._planes) ----
 
 KIND = {None: 0, "none": 0, "fp16": 1, "fp32": 2, "planes": 3}  # SPI_KIND_*
