@@ -265,7 +265,7 @@ int spi_op_qkv_attention(const void* A, int32_t lda, const void* W_packed, int32
                          const float* in_stats, const float* c1, float eps, const float* mask_bias, void* ctx,
                          int32_t B, int32_t S, float scale, void* stream);
 
-/* ---- The HBM-bound kernels around the contractions (elementwise.hip) ---- */
+/* ---- The HBM-bound kernels around the contractions (elementwise.hip, pool.hip, layernorm.hip) ---- */
 
 /* Image -> NHWC with the channels zero-padded to cpad: y [B][H][W][cpad] (fp16 when out_f16, else fp32).
  * src_kind, scale_host, shift_host as in spi_op_patchify; x is [B][C][H][W] fp32 (src_kind 0) or 8-bit

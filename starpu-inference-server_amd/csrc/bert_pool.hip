@@ -2,6 +2,7 @@
 // mean over the sequence.  Both are fp32 in every precision mode, small (under 10 MFLOP, 2.4 MB of
 // weights / 3 MB of rows at bert-base bs8) and deterministic: every sum has a fixed order and no
 // floating-point atomic, so two runs give the same bits.
+#include "row_util.hpp"
 #include "spi_kernels.hpp"
 
 #include <stdexcept>
@@ -15,12 +16,6 @@ template <bool VEC>
 __device__ __forceinline__ float4 load4(const float* p) {
   if constexpr (VEC) return *reinterpret_cast<const float4*>(p);
   return float4{p[0], p[1], p[2], p[3]};
-}
-
-__device__ __forceinline__ float wave_sum(float v) {  // xor butterfly: one order, every lane the total
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Pooler: one wave per output column n.  Lane l holds the float4 groups k4 = l, l + 64, ... of the
@@ -137,8 +132,6 @@ __global__ __launch_bounds__(256) void masked_mean_kernel(const float* __restric
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 void check_dims(const char* op, int B, int D) {
   if (B < 1) throw std::invalid_argument(std::string(op) + ": B >= 1");
   if (D < 64 || D % 64 != 0 || D > 1024) throw std::invalid_argument(std::string(op) + ": D a multiple of 64, <= 1024");
@@ -151,7 +144,7 @@ void bert_pooler(const float* h, size_t ld, const float* W, const float* bias, f
   check_dims("bert_pooler", B, D);
   if (ld < (size_t)D) throw std::invalid_argument("bert_pooler: ld >= D");
   const dim3 grid((D + 3) / 4);
-  const bool vec = aligned16(h) && aligned16(W) && ld % 4 == 0;
+  const bool vec = aligned(h, 16) && aligned(W, 16) && ld % 4 == 0;
   if (vec && D == 768)
     SPI_LAUNCH((bert_pooler_kernel<true, 3>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D);
   else if (vec && D == 1024)
@@ -167,7 +160,7 @@ void masked_mean(const float* h, const int64_t* mask, float* y, int B, int S, in
   if (S < 1) throw std::invalid_argument("masked_mean: S >= 1");
   if (B > 65535) throw std::invalid_argument("masked_mean: B <= 65535");
   const dim3 grid(D / 64, B);
-  if (aligned16(h))
+  if (aligned(h, 16))
     SPI_LAUNCH((masked_mean_kernel<true>), grid, dim3(256), 0, s, h, mask, y, S, D);
   else
     SPI_LAUNCH((masked_mean_kernel<false>), grid, dim3(256), 0, s, h, mask, y, S, D);

@@ -23,6 +23,7 @@
 // Per band it takes in (th + 2)(W + 2) x 128 B (29.7 KiB at W = 56) for
 // 2 x 112 x 64 x 576 FLOP: ~320 FLOP per byte, MFMA-bound per CU.
 #include "lds_dma.hpp"
+#include "row_util.hpp"
 #include "spi_kernels.hpp"
 
 #include <algorithm>
@@ -338,12 +339,12 @@ constexpr int kWresMaxTiles = 128;  // the general kernel's plan target
 bool conv_wres_eligible(const GemmDesc& d, Prec prec, const GemmPtrs& p) {
   const int on = wres_on();
   if (on == 1 && (d.M + 127) / 128 >= kWresMaxTiles) return false;  // a full 128 x 64 window grid
-  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   return on && prec == Prec::F16 && d.conv && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 &&
          d.Cin == 64 && d.N == 64 && d.K == 576 && d.Kpad == 576 && d.krep == 1 && d.OH == d.H && d.OW == d.W &&
          !d.a_split && !d.out_split && !d.out_f32 && !d.res_f32 && !d.pool_rows && d.ldc == 64 &&
-         (!p.res || d.ldr == 64) && d.act != Act::Gelu && wres_rows(d.H, d.W) >= 1 && al16(p.A) && al16(p.W) &&
-         al16(p.C) && (!p.res || al16(p.res)) && (!p.bias || al16(p.bias)) && p.zeros && d.w_image;
+         (!p.res || d.ldr == 64) && d.act != Act::Gelu && wres_rows(d.H, d.W) >= 1 && aligned(p.A, 16) &&
+         aligned(p.W, 16) && aligned(p.C, 16) && (!p.res || aligned(p.res, 16)) && (!p.bias || aligned(p.bias, 16)) &&
+         p.zeros && d.w_image;
 }
 
 void conv_wres(const GemmDesc& d, const GemmPtrs& p, hipStream_t s) {

@@ -29,6 +29,7 @@
 #include "gemm_plan.hpp"
 #include "lds_dma.hpp"
 #include "ln_fold.hpp"
+#include "row_util.hpp"
 #include "spi_kernels.hpp"
 
 #include <algorithm>
@@ -895,8 +896,8 @@ void gemm256(const GemmDesc& d, const GemmPtrs& p, int splits, hipStream_t s, in
   g.act = static_cast<int>(d.act);
   g.res_f32 = d.res_f32;
   g.out_f32 = d.out_f32;
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  g.vec_ok = d.ldc % 8 == 0 && al16(p.C) && (!p.res || (d.ldr % 8 == 0 && al16(p.res))) && (!p.bias || al16(p.bias))
+  g.vec_ok = d.ldc % 8 == 0 && aligned(p.C, 16) && (!p.res || (d.ldr % 8 == 0 && aligned(p.res, 16))) &&
+                     (!p.bias || aligned(p.bias, 16))
                  ? 1 : 0;
   g.ln_in_chunks = d.ln_in_chunks;
   g.ln_in_eps = d.ln_in_eps;

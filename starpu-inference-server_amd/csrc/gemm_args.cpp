@@ -4,6 +4,8 @@
 // map by walking every workgroup of a launch through the kernels' own decode.
 #include "gemm_args.hpp"
 
+#include "row_util.hpp"
+
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -19,8 +21,6 @@ int ilog2(int v) {
   return s;
 }
 
-bool al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
-
 }  // namespace
 
 void validate_gemm(const GemmDesc& d, const GemmPtrs& p, Prec prec) {
@@ -35,12 +35,14 @@ void validate_gemm(const GemmDesc& d, const GemmPtrs& p, Prec prec) {
     // the fold lives in the dense fp16 kernels' vector epilogue: whole 128-column tiles,
     // 16-byte aligned rows everywhere it reads or writes
     const bool ok = prec == Prec::F16 && !d.conv && !d.pool_rows && d.N % 128 == 0 &&
-                    d.ldc % 8 == 0 && al16(p.C) && (!p.bias || al16(p.bias)) &&
-                    (!p.res || (d.ldr % 8 == 0 && al16(p.res))) &&
-                    (d.ln_in_chunks == 0 || (p.ln.in_stats && p.ln.c1 && al16(p.ln.c1))) &&
+                    d.ldc % 8 == 0 && aligned(p.C, 16) && (!p.bias || aligned(p.bias, 16)) &&
+                    (!p.res || (d.ldr % 8 == 0 && aligned(p.res, 16))) &&
+                    (d.ln_in_chunks == 0 || (p.ln.in_stats && p.ln.c1 && aligned(p.ln.c1, 16))) &&
                     (d.res_ln_chunks == 0 ||
-                     (p.res && (d.res_f32 || d.res_planes) && p.ln.res_stats && al16(p.ln.res_g) && al16(p.ln.res_b))) &&
-                    (!d.ln_out || (p.ln.out_stats && (p.ln.c16 ? al16(p.ln.c16) && d.ld16 % 8 == 0 : d.out_planes)));
+                     (p.res && (d.res_f32 || d.res_planes) && p.ln.res_stats && aligned(p.ln.res_g, 16) &&
+                      aligned(p.ln.res_b, 16))) &&
+                    (!d.ln_out ||
+                     (p.ln.out_stats && (p.ln.c16 ? aligned(p.ln.c16, 16) && d.ld16 % 8 == 0 : d.out_planes)));
     if (!ok) throw std::invalid_argument("LayerNorm fold: dense fp16 GEMM, N % 128 == 0, aligned vectors");
   }
   if (d.res_planes || d.out_planes) {
@@ -86,7 +88,8 @@ KArgs make_args(int mode, const GemmDesc& d, const GemmPtrs& p, const Plan& pl) 
   a.cin_shift = d.conv ? ilog2(d.Cin) : 0;
   a.kw_mul = (65536 + d.KW - 1) / d.KW;
   a.cell_uniform = cell_uniform(d, prec);
-  a.vec_ok = d.ldc % 8 == 0 && al16(p.C) && (!p.res || (d.ldr % 8 == 0 && al16(p.res))) && (!p.bias || al16(p.bias));
+  a.vec_ok = d.ldc % 8 == 0 && aligned(p.C, 16) && (!p.res || (d.ldr % 8 == 0 && aligned(p.res, 16))) &&
+             (!p.bias || aligned(p.bias, 16));
   if (pl.halo) {
     a.h_th = pl.th;
     a.h_period = pl.period;

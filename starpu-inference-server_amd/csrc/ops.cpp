@@ -13,6 +13,7 @@
 #include "ln_fold_pack.hpp"
 #include "pack.hpp"
 #include "resample.hpp"
+#include "row_util.hpp"
 #include "spi_kernels.hpp"
 
 extern "C" void spi_set_last_error(const char* msg);
@@ -613,7 +614,6 @@ int spi_op_ingest(int32_t src_kind, const void* x, int32_t B, int32_t Cc, int32_
 namespace {
 
 // 16-byte channel vectors of the pooling kernels: 4 fp32, 8 fp16, a 32-channel block of the split layout
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 int pool_vec(int32_t precision) { return precision == 0 ? 4 : precision == 1 ? 8 : precision == kSplitPrecision ? 32 : 0; }
 
 }  // namespace
@@ -624,7 +624,7 @@ int spi_op_maxpool(int32_t precision, const void* x, int32_t B, int32_t H, int32
   if (!vec || !x || !y || B <= 0 || H <= 0 || W <= 0 || Cc <= 0 || k <= 0 || stride <= 0 || pad < 0 || pad >= k)
     return fail("invalid maxpool arguments");
   if (Cc % vec) return fail("maxpool: C must be a multiple of 4 (fp32), 8 (fp16) or 32 (split)");
-  if (!aligned16(x) || !aligned16(y)) return fail("maxpool: 16-byte aligned x and y");
+  if (!spi::aligned(x, 16) || !spi::aligned(y, 16)) return fail("maxpool: 16-byte aligned x and y");
   if (H + 2 * pad < k || W + 2 * pad < k) return fail("empty maxpool output");
   const int OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
   return guarded([&] {
@@ -641,7 +641,7 @@ int spi_op_avgpool(int32_t precision, const void* x, int32_t B, int32_t HW, int3
   const int vec = pool_vec(precision);
   if (!vec || !x || !y || B <= 0 || HW <= 0 || Cc <= 0) return fail("invalid avgpool arguments");
   if (Cc % vec) return fail("avgpool: C must be a multiple of 4 (fp32), 8 (fp16) or 32 (split)");
-  if (!aligned16(x) || !aligned16(y)) return fail("avgpool: 16-byte aligned x and y");
+  if (!spi::aligned(x, 16) || !spi::aligned(y, 16)) return fail("avgpool: 16-byte aligned x and y");
   return guarded([&] {
     if (precision == kSplitPrecision)
       spi::avgpool_nhwc_split(x, static_cast<float*>(y), B, HW, Cc, static_cast<hipStream_t>(stream));

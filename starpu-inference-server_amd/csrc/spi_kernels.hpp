@@ -113,7 +113,8 @@ struct ImageSrc {
 void resize_crop_u8(const void* x, bool nhwc, int B, int H, int W, int resize_short, int crop, const InputXf& xf,
                     float* y, hipStream_t s);
 
-// Image (3 channels for an 8-bit source) -> NHWC (compute type) with channels zero-padded to cpad.
+// Image (3 channels for an 8-bit source) -> NHWC (compute type) with channels zero-padded to cpad
+// (elementwise.hip).
 void ingest_nchw(const void* x, void* y, int B, int C, int H, int W, int cpad,
                  bool f16, hipStream_t s, int src = kSrcF32Nchw, const InputXf& xf = InputXf{});
 // Fused ResNet stem (stem.hip): NCHW fp32 image [B][3][H][W] -> 7x7/s2/p3 conv
@@ -127,8 +128,8 @@ void ingest_nchw(const void* x, void* y, int B, int C, int H, int W, int cpad,
 // is [B][3][H][W] or [B][H][W][3] bytes at any byte address.
 void stem_pool(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int lo,
                bool split, int pr, hipStream_t s, int src = kSrcF32Nchw, const InputXf& xf = InputXf{});
-// 3x3/s2/p1 max pool on NHWC.  The pools work on whole 16-byte channel vectors: C % 8 == 0 (fp16),
-// C % 4 == 0 (fp32), else they throw.
+// 3x3/s2/p1 max pool on NHWC (the pools: pool.hip).  They work on whole 16-byte channel vectors:
+// C % 8 == 0 (fp16), C % 4 == 0 (fp32), else they throw.
 void maxpool_nhwc(const void* x, void* y, int B, int H, int W, int C, int OH,
                   int OW, int k, int stride, int pad, bool f16, hipStream_t s);
 // Global average pool NHWC [B,HW,C] -> [B,C] (compute type).
@@ -139,7 +140,8 @@ void avgpool_nhwc(const void* x, void* y, int B, int HW, int C, bool f16,
 void maxpool_nhwc_split(const void* x, void* y, int B, int H, int W, int C, int OH,
                         int OW, int k, int stride, int pad, hipStream_t s);
 void avgpool_nhwc_split(const void* x, float* y, int B, int HW, int C, hipStream_t s);
-// Row LayerNorm over D: y = LN(x) * g + b.  x fp32 [rows, ldx]; writes fp32
+// Row LayerNorm over D (the LayerNorm family, the BERT embedding and mask_to_bias: layernorm.hip):
+// y = LN(x) * g + b.  x fp32 [rows, ldx]; writes fp32
 // (yf, may alias x) and/or compute-type (yt) outputs.
 void layernorm(const float* x, int ldx, const float* g, const float* b,
                float* yf, void* yt, int ldy, int rows, int D, float eps, bool f16,
@@ -173,7 +175,8 @@ void softmax_topk(const float* x, size_t ldx, float* probs, float* topv, int64_t
                   bool topk_probs, hipStream_t s);
 // int64 attention mask [B,S] -> additive fp32 bias [B,S] (0 or finfo.min).
 void mask_to_bias(const int64_t* mask, float* bias, int n, hipStream_t s);
-// ViT: image (NCHW fp32, or 8-bit pixels of kind src, C = 3) -> patch rows [B*P, C*ps*ps] (compute type).
+// ViT (patchify, the two assemblies, gather_rows and affine: elementwise.hip): image (NCHW fp32, or
+// 8-bit pixels of kind src, C = 3) -> patch rows [B*P, C*ps*ps] (compute type).
 void patchify(const void* x, void* y, int B, int C, int H, int W, int ps,
               bool f16, hipStream_t s, int src = kSrcF32Nchw, const InputXf& xf = InputXf{});
 // ViT: x[b, 0] = cls + pos[0]; x[b, 1+p] = patch[b, p] + pos[1+p]  (fp32).
@@ -184,7 +187,7 @@ void vit_assemble(const float* patches, const float* cls, const float* pos,
 // (ln_fold.hpp).
 void vit_assemble_planes(const float* patches, const float* cls, const float* pos, _Float16* xh, size_t plane,
                          float* stats, int B, int P, int D, hipStream_t s);
-// layernorm() over rows held in two fp16 planes (x = hi + lo), D <= 1024.
+// layernorm() over rows held in two fp16 planes (x = hi + lo), D <= 1024 (layernorm.hip).
 void layernorm_planes(const _Float16* xh, size_t plane, int ldx, const float* g, const float* b, float* yf, void* yt,
                       int ldy, int rows, int D, float eps, bool f16, hipStream_t s);
 // Gather rows: y[i] = x[i * stride_rows] (fp32 -> compute type) for CLS pooling.

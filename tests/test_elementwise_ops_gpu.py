@@ -1,4 +1,5 @@
-"""Op-level tests of the HBM-bound kernels of elementwise.hip through include/spi_ops.h: layout ingest,
+"""Op-level tests of the HBM-bound kernels of elementwise.hip, pool.hip and layernorm.hip through
+include/spi_ops.h: layout ingest,
 the max and average pools (fp32, fp16 and the split layout), the BERT embedding (scalar and vector
 kernels, with the fused mask bias), mask_to_bias, vit_assemble and gather_rows -- each against the
 reference of op_refs.py, which test_op_refs.py holds to the torch op it restates.

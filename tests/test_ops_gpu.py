@@ -142,7 +142,11 @@ def test_attention_fully_masked_row(ops, prec):
 
 
 @pytest.mark.parametrize("prec", ["fp32", "fp16"])
-@pytest.mark.parametrize("rows,D,eps", [(1024, 768, 1e-12), (394, 1024, 1e-6), (3, 64, 1e-5)])
+# (5, 200), (7, 1000), (1, 256): the scalar kernel with masked lanes and a ragged last block, with 15.6
+# values per lane, and at a multiple of 256 that is no vector width; (5, 768): the vector kernel with a
+# ragged last block of 4 rows.
+@pytest.mark.parametrize("rows,D,eps", [(1024, 768, 1e-12), (394, 1024, 1e-6), (3, 64, 1e-5), (5, 200, 1e-5),
+                                        (7, 1000, 1e-6), (1, 256, 1e-5), (5, 768, 1e-12)])
 def test_layernorm(ops, prec, rows, D, eps):
     g = torch.Generator().manual_seed(rows + D)
     x = torch.randn(rows, D, generator=g) * 3 + 1
