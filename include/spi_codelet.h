@@ -336,6 +336,18 @@ int spi_model_profile_op(spi_model* model, void* stream, int64_t batch, int64_t 
  * Writes at most buflen - 1 bytes plus a NUL; returns the full length, or -1 on error. */
 int64_t spi_model_launch_table(spi_model* model, void* stream, int64_t batch, int64_t seq,
                                const void* const* inputs, void* const* outputs, char* buf, size_t buflen);
+/* Debug hooks of the replica's host-only forward plan (csrc/model_plan.hpp); neither needs a device, so
+ * both work on a host-only replica (device_id -1).
+ * spi_model_workspace_plan: the bytes of each per-stream workspace buffer at max_batch under the options
+ * in force, in allocation order (bytes_out[0 .. min(*n, cap))), the buffer count in *n, the split-K slab
+ * floats a workspace gets and what the launches at max_batch plan before the allocation's floor.
+ * spi_model_plan_check: walks one forward at `batch` (BERT: `seq` tokens) launching nothing and holds every
+ * GEMM, conv and conv pair against the planned workspace exactly as the launch does; *steps = the number of
+ * launches held.  Both return an spi_status; a step that does not fit is SPI_ERR_INVALID_ARGUMENT with the
+ * step named in spi_last_error(). */
+int spi_model_workspace_plan(const spi_model* model, size_t* bytes_out, int32_t cap, int32_t* n,
+                             size_t* partial_floats, size_t* partial_before_floor);
+int spi_model_plan_check(const spi_model* model, int64_t batch, int64_t seq, int32_t* steps);
 /* 8-bit image tasks.  A ResNet / ViT replica also takes tasks whose input_types[0] is
  * SPI_DTYPE_U8: decoded pixels, one byte per element, laid out as the task's dims say --
  * [B,3,S,S] (NCHW) or [B,S,S,3] (NHWC, what image decoders produce), S the replica's

@@ -401,6 +401,33 @@ int64_t spi_model_launch_table(spi_model* m, void* stream, int64_t batch, int64_
   }
 }
 
+int spi_model_workspace_plan(const spi_model* m, size_t* bytes_out, int32_t cap, int32_t* n, size_t* partial_floats,
+                             size_t* partial_before_floor) {
+  if (!m || !n || (cap > 0 && !bytes_out)) return SPI_ERR_INVALID_ARGUMENT;
+  try {
+    const spi::WorkspacePlan p = m->impl->planned_workspace();
+    for (int i = 0; i < (int)p.bytes.size() && i < cap; ++i) bytes_out[i] = p.bytes[i];
+    *n = (int32_t)p.bytes.size();
+    if (partial_floats) *partial_floats = p.partial_floats;
+    if (partial_before_floor) *partial_before_floor = p.partial_planned;
+    return SPI_OK;
+  } catch (const std::exception& e) {
+    tl_last_error = e.what();
+    return SPI_ERR_INVALID_ARGUMENT;
+  }
+}
+
+int spi_model_plan_check(const spi_model* m, int64_t batch, int64_t seq, int32_t* steps) {
+  if (!m || !steps) return SPI_ERR_INVALID_ARGUMENT;
+  try {
+    *steps = m->impl->check_plan((int)batch, (int)seq);
+    return SPI_OK;
+  } catch (const std::exception& e) {
+    tl_last_error = e.what();
+    return SPI_ERR_INVALID_ARGUMENT;
+  }
+}
+
 void spi_model_set_graphs(spi_model* m, int32_t on) {
   if (m) m->impl->set_graphs(on != 0);
 }

@@ -3,8 +3,10 @@
 // packed on the host (model_pack.hpp) and the whole replica lives in one HBM blob.
 // Activations live in per-stream workspaces (one per StarPU worker stream: replicas are
 // shared read-only by the workers of a device, starpu_setup.cpp:725-778 /
-// docs/server_guide.md:116).  Layers: packer (model_pack.cpp) -> replica, workspaces and
-// launch helpers -> per-family forward plans (model.cpp) -> profiling hooks (model_profile.cpp).
+// docs/server_guide.md:116).  Layers: packer (model_pack.cpp) -> host-only forward plans: I/O
+// contract, layer descs, the ResNet walk, FLOPs, workspace sizes (model_plan.cpp) -> replica,
+// workspaces, launch helpers and the per-family launches (model.cpp) -> profiling hooks
+// (model_profile.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,7 +18,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "model_pack.hpp"
+#include "model_plan.hpp"
 #include "spi_kernels.hpp"
 
 #define SPI_HIP(x)                                                                  \
@@ -46,18 +48,19 @@ class Model {
   int max_batch() const { return m_.max_batch; }
   size_t weight_bytes() const { return m_.blob_bytes; }
   uint64_t weight_digest() const { return m_.digest; }
-  const std::string& describe() const { return image_io_ || resize_short_ ? desc_ext_ : m_.desc; }
-  double flops(int64_t batch) const;
+  const std::string& describe() const { return desc_; }
+  double flops(int64_t batch) const { return model_flops(m_, batch); }
+  // Debug exports (spi_model_workspace_plan, spi_model_plan_check): what workspace() allocates, and the
+  // forward walked without a launch against it; both work on a host-only replica.
+  WorkspacePlan planned_workspace() const { return workspace_plan(m_, opt_); }
+  int check_plan(int batch, int S) const { return plan_check(m_, opt_, batch, S); }
   void set_graphs(bool on) { graphs_ = on; }
 
-  // Validates the task's I/O against the replica; throws std::runtime_error
-  // with the reference's message wording on mismatch.
-  void check_io(const spi_codelet_args& a, const size_t* in_bytes,
-                const size_t* out_bytes) const;
-  // What input 0 of a task that passed check_io holds: fp32 NCHW, or for a ResNet / ViT task of
-  // SPI_DTYPE_U8 the layout its dims name ([B,3,S,S] NCHW, [B,S,S,3] NHWC) -- with the input resize on,
-  // [B,3,H,W] / [B,H,W,3] and the source size, which sends the task through the resample first.
-  ImageSrc input_kind(const spi_codelet_args& a) const;
+  // The task's I/O against the replica and what its input 0 holds (model_plan.hpp).
+  void check_io(const spi_codelet_args& a, const size_t* in_bytes, const size_t* out_bytes) const {
+    spi::check_io(m_, opt_, a, in_bytes, out_bytes);
+  }
+  ImageSrc input_kind(const spi_codelet_args& a) const { return spi::input_kind(m_, opt_, a); }
   // The input transform of 8-bit image tasks (spi_model_set_input_transform); null pointers reset
   // it to scale 1, shift 0.  Returns an spi_status.  Not synchronised with forwards in flight.
   int set_input_transform(const float* scale, const float* shift);
@@ -96,17 +99,6 @@ class Model {
                  int reps, float* ms, double* flops, double* bytes);
 
  private:
-  int num_inputs_max() const {
-    return m_.family != SPI_FAMILY_BERT ? 1 : (m_.bert_io & SPI_BERT_TOKEN_TYPES) ? 3 : 2;
-  }
-  // BERT: the outputs bert_io selects, in order hidden, pooler, mean.  ResNet / ViT: the outputs
-  // image_io_ selects, in order logits, probabilities, top-k values, top-k indices.
-  int num_outputs() const {
-    if (image_io_)
-      return !(image_io_ & SPI_IMAGE_NO_LOGITS) + !!(image_io_ & SPI_IMAGE_OUT_PROBS) + 2 * !!(image_io_ & SPI_IMAGE_OUT_TOPK);
-    if (m_.family != SPI_FAMILY_BERT) return 1;
-    return !(m_.bert_io & SPI_BERT_NO_HIDDEN) + !!(m_.bert_io & SPI_BERT_OUT_POOLER) + !!(m_.bert_io & SPI_BERT_OUT_MEAN);
-  }
   Workspace* workspace(hipStream_t s);
   hipGraphExec_t graph(Workspace& w, int batch, int S, hipStream_t s);
   // Forward: prologue (reads the task's input buffers) -> body (workspace only, graph-capturable)
@@ -114,11 +106,6 @@ class Model {
   void prologue(Workspace& w, int batch, int S, const void* const* in, hipStream_t s, ImageSrc src = ImageSrc{});
   void body(Workspace& w, int batch, int S, hipStream_t s);
   void epilogue(Workspace& w, int batch, int S, void* const* out, hipStream_t s);
-  // Bytes per workspace buffer of the family (indexed by its buffer enum, model.cpp) at max_batch;
-  // raises `partial` to the split-K slab floats its GEMMs need.
-  std::vector<size_t> workspace_sizes_resnet(size_t& partial) const;
-  std::vector<size_t> workspace_sizes_bert(size_t& partial) const;
-  std::vector<size_t> workspace_sizes_vit(size_t& partial) const;
   void prologue_resnet(Workspace& w, int B, const void* x, hipStream_t s, int src);
   void body_resnet(Workspace& w, int B, hipStream_t s);
   void body_bert(Workspace& w, int B, int S, hipStream_t s);
@@ -126,49 +113,36 @@ class Model {
   void body_vit(Workspace& w, int B, hipStream_t s);
   void body_vit_folded(Workspace& w, int B, hipStream_t s);
   void epilogue_bert(Workspace& w, int B, int S, void* const* out, hipStream_t s);
-  // ResNet / ViT with image_io_: where the classifier writes its logits (the first output, or the
+  // ResNet / ViT with image outputs: where the classifier writes its logits (the first output, or the
   // workspace scratch under SPI_IMAGE_NO_LOGITS), and the launch that derives the other outputs from them
   float* logits_dst(void* scratch, void* const* out) const {
-    return static_cast<float*>((image_io_ & SPI_IMAGE_NO_LOGITS) ? scratch : out[0]);
+    return static_cast<float*>((opt_.image_io & SPI_IMAGE_NO_LOGITS) ? scratch : out[0]);
   }
   void run_image_outputs(const float* logits, int B, void* const* out, hipStream_t s);
-  // The LayerNorm fold of one transformer GEMM (ln_fold.hpp).
-  struct LnSpec {
-    const float* in_stats = nullptr;  // A rows are pre-LN: their chunk statistics (L.c1 folded in)
-    const float* res_stats = nullptr;  // residual is LN(R): R's statistics, gain, bias
-    const float* res_g = nullptr;
-    const float* res_b = nullptr;
-    float* out_stats = nullptr;  // write the output's statistics ...
-    void* c16 = nullptr;         // ... and an fp16 copy
-  };
-  void run_gemm(const LinearW& L, const void* A, int M, int lda, void* C, int ldc,
-                bool out_f32, Act act, const void* res, bool res_f32, int ldr, Workspace& ws,
-                hipStream_t s, const LnSpec* ln = nullptr, size_t planes = 0);
-  // QKV projection + attention of one transformer layer: the fused kernel (qkv_attn.hip) when
+  // One GEMM from its finished desc (linear_layer_desc / tf_gemm_desc) plus pointers; ln: the LayerNorm
+  // fold's statistics / gain / bias pointers the desc asks for (ln_fold.hpp), else empty.
+  void run_gemm(const LinearW& L, const GemmDesc& d, const void* A, void* C, const void* res, const LnPtrs& ln,
+                Workspace& ws, hipStream_t s);
+  // GEMM g of encoder layer `layer` over T token rows: the desc is tf_gemm_desc's
+  void run_tf_gemm(int layer, TfGemm g, int T, const void* A, void* C, const void* res, Workspace& ws,
+                   hipStream_t s, const LnPtrs& ln = LnPtrs{});
+  // QKV projection + attention of encoder layer `layer`: the fused kernel (qkv_attn.hip) when
   // the shape allows it, else the QKV GEMM into qkv and the attention launch
-  void run_qkv_attention(const LinearW& L, const void* x, const float* in_stats, void* qkv, void* ctx, int B,
-                         int S, Workspace& ws, hipStream_t s);
-  void run_conv(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW,
-                Act act, const void* res, Workspace& ws, hipStream_t s, bool out_f32 = false,
-                bool res_f32 = false);
-  void run_gconv(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW, Act act,
-                 hipStream_t s);
+  void run_qkv_attention(int layer, const void* x, const float* in_stats, void* qkv, void* ctx, int B, int S,
+                         Workspace& ws, hipStream_t s);
+  // Convs from their finished descs (conv_layer_desc): the launchers add pointers, FLOPs and bytes.
   struct ConvCall {  // the op's name (conv_name) is built only while profiling
-    GemmDesc d;
     GemmPtrs p;
-    Prec prec = Prec::F16;
     double flops = 0, bytes = 0;
   };
-  ConvCall conv_call(const ConvW& c, const void* x, int B, int H, int W, void* y, int& OH, int& OW, Act act,
-                     const void* res, Workspace& ws, bool out_f32, bool res_f32) const;
-  void run_conv_pair(const ConvW& c0, const void* x, int B, int H, int W, void* y0, int& OH0, int& OW0, Act act0,
-                     const ConvW& c1, void* y1, bool out1_f32, Workspace& ws, hipStream_t s);
-  bool pooled_fc(int hw) const;
+  ConvCall conv_call(const ConvW& c, const GemmDesc& d, const void* x, void* y, const void* res,
+                     const Workspace& ws) const;
+  void run_conv(const ConvW& c, const GemmDesc& d, const void* x, void* y, const void* res, Workspace& ws,
+                hipStream_t s);
+  void run_gconv(const ConvW& c, const void* x, int B, int H, void* y, Act act, hipStream_t s);
+  void run_conv_pair(const void* x, const ConvW& c0, const GemmDesc& d0, void* y0, const ConvW& c1, const GemmDesc& d1,
+                     void* y1, Workspace& ws, hipStream_t s);
   void run_pooled_fc(const void* act, int B, int hw, void* out, Workspace& ws, hipStream_t s);
-  size_t conv_partial(const ConvW& c, int B, int H, int W) const;
-  size_t linear_partial(const LinearW& L, int M) const;
-  size_t layers_partial(int T) const;  // the encoder layers' four GEMMs over T rows
-  GemmDesc pooled_fc_desc(int B, int hw) const;  // avgpool + FC as one GEMM (pool_rows = hw)
   template <typename P>
   const P* ptr(size_t off) const {
     return reinterpret_cast<const P*>(static_cast<const char*>(dblob_) + off);
@@ -183,10 +157,11 @@ class Model {
   void* dblob_ = nullptr;
   int stem_pr_ = SPI_STEM_PR;  // the fused stem's workgroup shape (0 = auto, stem.hip)
   InputXf input_xf_;  // ResNet / ViT: the transform of 8-bit image tasks, passed to the prologue's kernel
-  int image_io_ = 0, top_k_ = 0;  // ResNet / ViT: SPI_IMAGE_* bits and the top-k count (set_image_outputs)
-  int resize_short_ = 0;          // ResNet / ViT: the input resize of 8-bit tasks (set_input_resize), 0 = off
-  std::string desc_ext_;          // m_.desc + " out[...]" (image_io_) + " resize<R>" (resize_short_) while either is set
-  void rebuild_desc();
+  ReplicaOptions opt_;  // set_image_outputs, set_input_resize
+  std::string desc_;    // replica_desc(m_, opt_)
+  // The setters' common end: under mu_, refuse once a stream workspace exists, else assign and re-describe.
+  template <typename F>
+  int set_options(const char* what, std::string& err, F&& assign);
   // SPI_QKV_ATTN: 0 the QKV GEMM + attention launches (A/B); 1 (default) the fused kernel for S <= 128;
   // 2 also for 129..256 tokens (ViT-L at 197: correct, but -4 % under the four streams)
   int qkv_fused_ = 1;

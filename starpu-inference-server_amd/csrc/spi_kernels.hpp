@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "gemm_desc.hpp"
+#include "image_src.hpp"
 
 namespace spi {
 
@@ -74,16 +75,7 @@ void qkv_attn_reload_env();   // SPI_QKV_HP
 void conv_group(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int groups,
                 int stride, bool relu, hipStream_t s);
 
-// What an image task's input buffer holds (ResNet / ViT).  The kernels that read it -- the fused
-// stem, ingest_nchw, patchify -- take the kind and, for 8-bit pixels, the per-channel input
-// transform: pixel p of channel c enters the network as fl(fl((float)p * scale[c]) + shift[c]),
-// one fp32 multiply and one fp32 add, each rounded to nearest and never contracted into an FMA.
-// The transform travels as a kernel argument; an fp32 image ignores it.
-enum SrcKind : int { kSrcF32Nchw = 0, kSrcU8Nchw = 1, kSrcU8Nhwc = 2 };
-struct InputXf {
-  float scale[3] = {1.f, 1.f, 1.f};
-  float shift[3] = {0.f, 0.f, 0.f};
-};
+// The kind of an image task's input buffer (SrcKind) and its 8-bit input transform (InputXf): image_src.hpp.
 // The transform of one pixel of channel c.  Contraction is switched off for the two operations:
 // HIP compiles with -ffp-contract=fast, under which __fmul_rn / __fadd_rn are a plain * and + that
 // the backend may still fuse; without the contract flag it cannot.  The channel is picked by
@@ -99,12 +91,6 @@ __device__ __forceinline__ float input_xf_apply(unsigned char p, const InputXf& 
   return input_xf_apply(p, sc, sh);
 }
 
-// What input 0 of an image task holds: its kind and, for an 8-bit task of a replica with the input
-// resize on (H > 0), the source size the prologue resamples to the replica's image first.
-struct ImageSrc {
-  int kind = kSrcF32Nchw;
-  int H = 0, W = 0;
-};
 // Resize + centre crop of 8-bit pixels (resample.hip; arithmetic: resample.hpp): x bytes [B][3][H][W], or
 // [B][H][W][3] with nhwc, at any byte address -> y fp32 NCHW [B][3][crop][crop], the antialiased bilinear
 // resample to short side resize_short, centre-cropped, under the transform xf.  1 <= H, W <= 8192,
@@ -170,7 +156,6 @@ void masked_mean(const float* h, const int64_t* mask, float* y, int B, int S, in
 // holds (or would hold) there.  1 <= N <= kSoftmaxTopkMaxN, 1 <= k <= min(N, kSoftmaxTopkMaxK) (0 without
 // top-k).  -inf logits give probability 0; +inf / NaN logits give unspecified results.  Throws
 // std::invalid_argument before any launch.
-constexpr int kSoftmaxTopkMaxN = 16384, kSoftmaxTopkMaxK = 64;
 void softmax_topk(const float* x, size_t ldx, float* probs, float* topv, int64_t* topi, int B, int N, int k,
                   bool topk_probs, hipStream_t s);
 // int64 attention mask [B,S] -> additive fp32 bias [B,S] (0 or finfo.min).
