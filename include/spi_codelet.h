@@ -293,12 +293,40 @@ typedef struct spi_model_config {
  * SPI_BERT_NO_HIDDEN with neither pooled output; SPI_BERT_OUT_POOLER on a model without
  * pooler.dense.weight / .bias (add_pooling_layer=False).
  * The measurement hooks (spi_model_profile, _profile_op, _launch_table) read `inputs` up to
- * the replica's input count (absent inputs null) and `outputs` in the order above. */
+ * the replica's input count (absent inputs null) and `outputs` in the order above.
+ *
+ * Task heads (SPI_BERT_HEAD_*): the one dense layer of a fine-tuned BERT, written on the device.  At
+ * most one head per replica (two of them share the parameter name `classifier`); its output(s), fp32,
+ * follow hidden, pooler and mean, so a replica has at most five outputs.  L, the label count, is the
+ * head weight's first dimension (spi_model_bert_num_labels), not a config field.
+ *   SPI_BERT_HEAD_SEQUENCE  logits [B,L] = W_c . pooler_output + b_c: HF BertForSequenceClassification
+ *                           in eval.  classifier.weight [L,D], classifier.bias [L], 1 <= L <= 1024, and
+ *                           pooler.dense.*; the pooler runs whether or not SPI_BERT_OUT_POOLER also
+ *                           makes it an output.
+ *   SPI_BERT_HEAD_TOKEN     logits [B,S,L] = W_c . last_hidden_state + b_c on every token, padded ones
+ *                           included: HF BertForTokenClassification.  classifier.weight [L,D],
+ *                           classifier.bias [L], 1 <= L <= 64.
+ *   SPI_BERT_HEAD_QA        two outputs, start_logits [B,S] then end_logits [B,S]: rows 0 and 1 of
+ *                           qa_outputs.weight [2,D] / .bias [2], HF BertForQuestionAnswering.
+ * The head's parameters sit outside the `bert.` prefix the other names share: they are the one tensor
+ * named `classifier.weight` or ending in `.classifier.weight` (likewise .bias, qa_outputs.*).
+ * SPI_BERT_NO_HIDDEN is also satisfied by a head bit: logits alone are a valid replica, and for a
+ * token-level head the hidden state is then never written to memory.
+ * Independence: a row's logits depend on that row's inputs alone -- not on B, not on the row's
+ * position in the batch, not on graphs being on -- so dynamic batching changes nobody's answer.  Every
+ * sum has a fixed order and there are no floating-point atomics: two runs give the same bits.
+ * spi_model_create also refuses: two head bits; a head bit on another family; a missing or ambiguous
+ * head parameter (named); a weight that is not [L,D] or a bias that is not [L]; L outside the head's
+ * range (QA: L != 2); SPI_BERT_HEAD_SEQUENCE without pooler.dense.weight / .bias.
+ * Bits 16, 32 and 64 stay unknown. */
 enum spi_bert_io {
   SPI_BERT_OUT_POOLER = 1,
   SPI_BERT_OUT_MEAN = 2,
   SPI_BERT_NO_HIDDEN = 4,
-  SPI_BERT_TOKEN_TYPES = 8
+  SPI_BERT_TOKEN_TYPES = 8,
+  SPI_BERT_HEAD_SEQUENCE = 128,
+  SPI_BERT_HEAD_TOKEN = 256,
+  SPI_BERT_HEAD_QA = 512
 };
 
 spi_model* spi_model_create(int32_t device_id, const spi_model_config* config,
@@ -314,6 +342,9 @@ uint64_t spi_model_weight_digest(const spi_model* model);
 double spi_model_flops(const spi_model* model, int64_t batch);
 /* Short description ("resnet[2,2,2,2] basic f16 ..."). */
 const char* spi_model_describe(const spi_model* model);
+/* The label count L of a BERT replica's task head (SPI_BERT_HEAD_*), 0 without one.  Works on a
+ * host-only replica. */
+int32_t spi_model_bert_num_labels(const spi_model* model);
 /* Measurement hook (not on the task path): runs one forward on `stream` with
  * every kernel launch bracketed by hipEvents, synchronises, and returns the
  * number of ops; per op: device milliseconds, algorithmic FLOPs, algorithmic

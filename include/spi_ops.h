@@ -318,6 +318,30 @@ int spi_op_bert_pooler(const float* h, int64_t ld, const float* W, const float* 
 int spi_op_masked_mean(const float* h, const int64_t* mask, float* y, int32_t B, int32_t S, int32_t D,
                        void* stream);
 
+/* ---- BERT task heads (bert_head.hip, bert_pool.hip); fp32 throughout, deterministic (no atomics) ---- */
+
+/* Token-level head: y[t][l] = bias[l] + sum_c h[t][c] W[l][c], t < T, l < L.  h[t] by `src`:
+ *   0  x: fp32 rows [T][D], already normalised;
+ *   1  x: fp32 pre-LayerNorm rows [T][D]; the kernel normalises each row in registers with gamma / beta
+ *      [D] and eps and never stores it;
+ *   2  x: pre-LayerNorm rows as two fp16 planes, hi [T][D] at x and lo `plane` elements (>= T D) after
+ *      it, the row being hi + lo; normalised as under 1.
+ * gamma, beta, eps and plane are ignored where the source does not use them (may be null / 0).
+ * W fp32 [L][D] row-major, bias fp32 [L].  y1 null: y0 is fp32 [T][L]; else L must be 2 and label 0 goes
+ * to y0 [T], label 1 to y1 [T] (QA start / end logits).  T >= 1, D a multiple of 64 and <= 1024,
+ * 1 <= L <= 64.  A row's result does not depend on T or on the row's place.  A pointer that is not
+ * 16-byte aligned (8 for the fp16 planes) takes scalar loads. */
+int spi_op_bert_token_head(int32_t src, const void* x, int64_t plane, const float* gamma, const float* beta, float eps,
+                           const float* W, const float* bias, float* y0, float* y1, int32_t T, int32_t D, int32_t L,
+                           void* stream);
+
+/* The pooler's kernel as a dense layer: y[b][n] = act(bias[n] + sum_k h[b ld + k] W[n][k]), b < B, n < N;
+ * h as for spi_op_bert_pooler, W fp32 [N][D], bias fp32 [N], y fp32 [B][N]; activation 0 = none, 1 = tanh.
+ * B >= 1, D a multiple of 64 and <= 1024, 1 <= N <= 1024.  N = D with tanh gives spi_op_bert_pooler's bits;
+ * without an activation it is the sequence-classification head on pooler_output. */
+int spi_op_bert_dense_rows(const float* h, int64_t ld, const float* W, const float* bias, float* y, int32_t B,
+                           int32_t D, int32_t N, int32_t activation, void* stream);
+
 /* bias[i] = mask[i] != 0 ? 0 : the lowest finite fp32, i < n. */
 int spi_op_mask_to_bias(const int64_t* mask, float* bias, int32_t n, void* stream);
 

@@ -160,6 +160,7 @@ class ModelConfig(C.Structure):
 
 # enum spi_bert_io (spi_model_config.bert_io)
 BERT_OUT_POOLER, BERT_OUT_MEAN, BERT_NO_HIDDEN, BERT_TOKEN_TYPES = 1, 2, 4, 8
+BERT_HEAD_SEQUENCE, BERT_HEAD_TOKEN, BERT_HEAD_QA = 128, 256, 512  # 16, 32 and 64 stay unknown bits
 # enum spi_image_io (spi_model_set_image_outputs)
 IMAGE_OUT_PROBS, IMAGE_OUT_TOPK, IMAGE_NO_LOGITS, IMAGE_TOPK_PROBS = 1, 2, 4, 8
 
@@ -205,6 +206,7 @@ _PROTOS = {
     "spi_model_weight_digest": (C.c_uint64, [C.c_void_p]),
     "spi_model_flops": (C.c_double, [C.c_void_p, C.c_int64]),
     "spi_model_describe": (C.c_char_p, [C.c_void_p]),
+    "spi_model_bert_num_labels": (C.c_int32, [C.c_void_p]),
     "spi_model_set_graphs": (None, [C.c_void_p, C.c_int32]),
     "spi_model_set_input_transform": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "spi_model_set_image_outputs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
@@ -308,6 +310,11 @@ _PROTOS = {
                                           C.c_void_p, C.c_void_p]),
     "spi_op_bert_pooler": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p]),
+    "spi_op_bert_token_head": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_void_p]),
+    "spi_op_bert_dense_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "spi_op_masked_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_void_p]),
     "spi_op_softmax_topk": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,

@@ -129,11 +129,13 @@ PRECISIONS = {"fp16": N.PREC_F16, "f16": N.PREC_F16, "fp32": N.PREC_F32, "f32": 
 _FAMILIES = {None: N.FAMILY_AUTO, "auto": N.FAMILY_AUTO, "resnet": N.FAMILY_RESNET, "bert": N.FAMILY_BERT,
              "vit": N.FAMILY_VIT, "affine": N.FAMILY_AFFINE}
 BERT_IO = {"pooler": N.BERT_OUT_POOLER, "mean": N.BERT_OUT_MEAN, "no_hidden": N.BERT_NO_HIDDEN,
-           "token_types": N.BERT_TOKEN_TYPES}
+           "token_types": N.BERT_TOKEN_TYPES, "seq_head": N.BERT_HEAD_SEQUENCE, "token_head": N.BERT_HEAD_TOKEN,
+           "qa_head": N.BERT_HEAD_QA}
 
 
 def bert_io_bits(bert_io) -> int:
-    """spi_model_config.bert_io from an int, one name or several: ("pooler", "mean", "no_hidden", "token_types")."""
+    """spi_model_config.bert_io from an int, one name or several: ("pooler", "mean", "no_hidden", "token_types",
+    and at most one task head of "seq_head", "token_head", "qa_head")."""
     if bert_io is None:
         return 0
     if isinstance(bert_io, int):
@@ -167,15 +169,25 @@ def image_io_bits(image_io) -> int:
 
 
 def output_specs(batch: int, classes: int = 0, image_io=0, top_k: int = 0, seq: int = 0, dim: int = 0,
-                 bert_io=0) -> list[tuple[tuple, torch.dtype]]:
+                 bert_io=0, num_labels: int = 0) -> list[tuple[tuple, torch.dtype]]:
     """(shape, dtype) of each output buffer of a replica's task, in the replica's output order.
     ResNet / ViT (classes): logits, probabilities, top-k values, top-k indices (int64) as image_io selects.
-    BERT (seq, dim): hidden, pooler, mean as bert_io selects."""
+    BERT (seq, dim): hidden, pooler, mean as bert_io selects, then the task head's: [B,L] ("seq_head"),
+    [B,S,L] ("token_head") with L = num_labels (ModelReplica.num_labels), or [B,S] twice ("qa_head")."""
     f32 = torch.float32
     if dim:
         io = bert_io_bits(bert_io)
         specs = [] if io & N.BERT_NO_HIDDEN else [((batch, seq, dim), f32)]
-        return specs + [((batch, dim), f32)] * (bool(io & N.BERT_OUT_POOLER) + bool(io & N.BERT_OUT_MEAN))
+        specs += [((batch, dim), f32)] * (bool(io & N.BERT_OUT_POOLER) + bool(io & N.BERT_OUT_MEAN))
+        if io & (N.BERT_HEAD_SEQUENCE | N.BERT_HEAD_TOKEN) and num_labels < 1:
+            raise InferenceExecutionException("output_specs: a sequence or token head needs num_labels")
+        if io & N.BERT_HEAD_SEQUENCE:
+            specs.append(((batch, num_labels), f32))
+        if io & N.BERT_HEAD_TOKEN:
+            specs.append(((batch, seq, num_labels), f32))
+        if io & N.BERT_HEAD_QA:
+            specs += [((batch, seq), f32)] * 2
+        return specs
     io = image_io_bits(image_io)
     specs = [] if io & N.IMAGE_NO_LOGITS else [((batch, classes), f32)]
     if io & N.IMAGE_OUT_PROBS:
@@ -394,6 +406,11 @@ class ModelReplica:
 
     def flops(self, batch: int) -> float:
         return lib.spi_model_flops(self.handle, batch)
+
+    @property
+    def num_labels(self) -> int:
+        """The label count L of a BERT replica's task head (the head weight's first dimension), 0 without one."""
+        return lib.spi_model_bert_num_labels(self.handle)
 
     def profile(self, inputs: Sequence[torch.Tensor], out, stream: int, max_ops: int = 4096) -> list[dict]:
         """One forward with every launch bracketed by hipEvents on `stream` (measurement only).

@@ -24,20 +24,22 @@ __device__ __forceinline__ float4 load4(const float* p) {
 // NK > 0: D = NK * 256 (BERT-base 768, BERT-large 1024), every lane holds NK groups and all of a pass's
 // loads are issued before the first FMA -- the kernel is one memory round trip per wave, so the trips
 // are what it costs.  NK = 0: any D, a loop over the groups.  The sums and their order are the same.
+// The kernel is the dense layer y = act(h W^T + bias) over N output columns (bert_dense_rows): the pooler
+// is N = D with TANH, the sequence-classification head N = labels without.
 constexpr int kPoolRows = 8;
 
 __device__ __forceinline__ float dot4(float4 x, float4 w, float acc) {
   return fmaf(x.w, w.w, fmaf(x.z, w.z, fmaf(x.y, w.y, fmaf(x.x, w.x, acc))));
 }
 
-template <bool VEC, int NK>
+template <bool VEC, int NK, bool TANH>
 __global__ __launch_bounds__(256) void bert_pooler_kernel(const float* __restrict__ h, size_t ld,
                                                           const float* __restrict__ W,
                                                           const float* __restrict__ bias, float* __restrict__ y,
-                                                          int B, int D) {
+                                                          int B, int D, int N) {
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (n >= D) return;  // the whole wave
+  if (n >= N) return;  // the whole wave
   const float* wr = W + (size_t)n * D;
   const int D4 = D >> 2;
   const float bn = bias[n];
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(256) void bert_pooler_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < kPoolRows; ++i) {
       const float t = wave_sum(acc[i]);
-      if (lane == 0 && b0 + i < B) y[(size_t)(b0 + i) * D + n] = tanhf(t + bn);
+      if (lane == 0 && b0 + i < B) y[(size_t)(b0 + i) * N + n] = TANH ? tanhf(t + bn) : t + bn;
     }
   }
 }
@@ -137,22 +139,39 @@ void check_dims(const char* op, int B, int D) {
   if (D < 64 || D % 64 != 0 || D > 1024) throw std::invalid_argument(std::string(op) + ": D a multiple of 64, <= 1024");
 }
 
+template <bool TANH>
+void launch_dense_rows(const float* h, size_t ld, const float* W, const float* bias, float* y, int B, int D, int N,
+                       hipStream_t s) {
+  const dim3 grid((N + 3) / 4);
+  const bool vec = aligned(h, 16) && aligned(W, 16) && ld % 4 == 0;
+  if (vec && D == 768)
+    SPI_LAUNCH((bert_pooler_kernel<true, 3, TANH>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D, N);
+  else if (vec && D == 1024)
+    SPI_LAUNCH((bert_pooler_kernel<true, 4, TANH>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D, N);
+  else if (vec)
+    SPI_LAUNCH((bert_pooler_kernel<true, 0, TANH>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D, N);
+  else
+    SPI_LAUNCH((bert_pooler_kernel<false, 0, TANH>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D, N);
+}
+
 }  // namespace
+
+void bert_dense_rows(const float* h, size_t ld, const float* W, const float* bias, float* y, int B, int D, int N,
+                     bool tanh_act, hipStream_t s) {
+  check_dims("bert_dense_rows", B, D);
+  if (ld < (size_t)D) throw std::invalid_argument("bert_dense_rows: ld >= D");
+  if (N < 1 || N > 1024) throw std::invalid_argument("bert_dense_rows: 1 <= N <= 1024");
+  if (tanh_act)
+    launch_dense_rows<true>(h, ld, W, bias, y, B, D, N, s);
+  else
+    launch_dense_rows<false>(h, ld, W, bias, y, B, D, N, s);
+}
 
 void bert_pooler(const float* h, size_t ld, const float* W, const float* bias, float* y, int B, int D,
                  hipStream_t s) {
   check_dims("bert_pooler", B, D);
   if (ld < (size_t)D) throw std::invalid_argument("bert_pooler: ld >= D");
-  const dim3 grid((D + 3) / 4);
-  const bool vec = aligned(h, 16) && aligned(W, 16) && ld % 4 == 0;
-  if (vec && D == 768)
-    SPI_LAUNCH((bert_pooler_kernel<true, 3>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D);
-  else if (vec && D == 1024)
-    SPI_LAUNCH((bert_pooler_kernel<true, 4>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D);
-  else if (vec)
-    SPI_LAUNCH((bert_pooler_kernel<true, 0>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D);
-  else
-    SPI_LAUNCH((bert_pooler_kernel<false, 0>), grid, dim3(256), 0, s, h, ld, W, bias, y, B, D);
+  launch_dense_rows<true>(h, ld, W, bias, y, B, D, D, s);
 }
 
 void masked_mean(const float* h, const int64_t* mask, float* y, int B, int S, int D, hipStream_t s) {

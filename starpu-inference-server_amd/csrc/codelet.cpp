@@ -361,6 +361,7 @@ size_t spi_model_weight_bytes(const spi_model* m) { return m ? m->impl->weight_b
 uint64_t spi_model_weight_digest(const spi_model* m) { return m ? m->impl->weight_digest() : 0; }
 double spi_model_flops(const spi_model* m, int64_t b) { return m ? m->impl->flops(b) : 0.0; }
 const char* spi_model_describe(const spi_model* m) { return m ? m->impl->describe().c_str() : ""; }
+int32_t spi_model_bert_num_labels(const spi_model* m) { return m ? m->impl->bert_num_labels() : 0; }
 int spi_model_profile(spi_model* m, void* stream, int64_t batch, int64_t seq, const void* const* inputs,
                       void* const* outputs, float* op_ms, double* op_flops, double* op_bytes, char* op_names,
                       int32_t name_len, int32_t max_ops) {

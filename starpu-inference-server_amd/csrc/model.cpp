@@ -244,6 +244,12 @@ Workspace* Model::workspace(hipStream_t s) {
     SPI_HIP(hipMalloc(&b, std::max<size_t>(bytes, 256)));
     w->bufs.push_back(b);
   }
+  // ViT patch rows that are no whole number of 16-byte chunks (vit_patches_tail_bytes): the patch
+  // projection's last A chunk of a row runs into the row behind it, against zero weights -- so what lies
+  // behind a task's last row, another task's rows or the buffer's tail, must be finite from the start.
+  // Stream-ordered, like the tickets below; patchify writes whole rows only, so the tail stays zero.
+  if (vit_patches_tail_bytes(m_))
+    SPI_HIP(hipMemsetAsync(w->bufs[kVtPatches], 0, plan.bytes[kVtPatches], s));
   w->partial_floats = plan.partial_floats;
   SPI_HIP(hipMalloc(&w->partial, plan.partial_floats * sizeof(float)));
   SPI_HIP(hipMalloc(&w->counters, kCounterSlots * sizeof(int)));
@@ -406,25 +412,35 @@ void Model::epilogue_bert(Workspace& w, int B, int S, void* const* out, hipStrea
   const int D = m_.D, T = B * S, io = m_.bert_io;
   const bool hidden = !(io & SPI_BERT_NO_HIDDEN), pooler = (io & SPI_BERT_OUT_POOLER) != 0,
              mean = (io & SPI_BERT_OUT_MEAN) != 0;
-  const bool cls_only = !hidden && !mean;
+  // The task head (SPI_BERT_HEAD_*) writes last.  The sequence head reads the pooled vector, so it runs
+  // the pooler whether or not that is an output.  A token-level head (token, QA) reads every normalised
+  // row: the hidden output's or the mean's where one of them is written anyway, else the pre-LN2 rows
+  // themselves, normalised in the head kernel's registers -- then no LayerNorm launch covers all rows.
+  const bool seq_head = (io & SPI_BERT_HEAD_SEQUENCE) != 0, tok_head = (io & (SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA)) != 0;
+  const bool pooled = pooler || seq_head;
+  const bool cls_only = !hidden && !mean;  // no launch needs all rows normalised in memory
+  const int L = m_.num_labels;
   int o = 0;
   float* rows = hidden     ? static_cast<float*>(out[o++])
                 : cls_only ? static_cast<float*>(w.bufs[kBtCls])
                            : static_cast<float*>(w.bufs[m_.ln_fold ? kBtAttn : kBtHidden]);
   const int nrows = cls_only ? B : T, ldx = cls_only ? S * D : D;
-  prof_op(s, cls_only ? "layernorm_cls" : "layernorm_out", 0, (double)nrows * D * 8, [&] {
-    // the last layer's pre-LN2 rows: the two-plane b under the LayerNorm fold, else a
-    if (m_.ln_fold)
-      layernorm_planes(static_cast<const _Float16*>(w.bufs[kBtHidden]), (size_t)T * D, ldx, ptr<float>(l.g),
-                       ptr<float>(l.b), rows, nullptr, D, nrows, D, m_.eps, m_.f16, s);
-    else
-      layernorm(static_cast<float*>(w.bufs[kBtAttn]), ldx, ptr<float>(l.g), ptr<float>(l.b), rows, nullptr, D, nrows,
-                D, m_.eps, m_.f16, s);
-  });
-  if (pooler) {
-    float* y = static_cast<float*>(out[o++]);
+  if (!cls_only || pooled)
+    prof_op(s, cls_only ? "layernorm_cls" : "layernorm_out", 0, (double)nrows * D * 8, [&] {
+      // the last layer's pre-LN2 rows: the two-plane b under the LayerNorm fold, else a
+      if (m_.ln_fold)
+        layernorm_planes(static_cast<const _Float16*>(w.bufs[kBtHidden]), (size_t)T * D, ldx, ptr<float>(l.g),
+                         ptr<float>(l.b), rows, nullptr, D, nrows, D, m_.eps, m_.f16, s);
+      else
+        layernorm(static_cast<float*>(w.bufs[kBtAttn]), ldx, ptr<float>(l.g), ptr<float>(l.b), rows, nullptr, D, nrows,
+                  D, m_.eps, m_.f16, s);
+    });
+  float* pool_y = nullptr;
+  if (pooled) {
+    // an output, or the workspace place behind the class-token rows (model_plan.hpp: kBtCls' two parts)
+    pool_y = pooler ? static_cast<float*>(out[o++]) : static_cast<float*>(w.bufs[kBtCls]) + bert_cls_rows_floats(m_);
     prof_op(s, "bert_pooler", 2.0 * B * D * (double)D, (double)D * D * 4 + (double)B * D * 8, [&] {
-      bert_pooler(rows, cls_only ? (size_t)D : (size_t)S * D, ptr<float>(m_.pool_w), ptr<float>(m_.pool_b), y, B, D, s);
+      bert_pooler(rows, cls_only ? (size_t)D : (size_t)S * D, ptr<float>(m_.pool_w), ptr<float>(m_.pool_b), pool_y, B, D, s);
     });
   }
   if (mean) {
@@ -432,6 +448,28 @@ void Model::epilogue_bert(Workspace& w, int B, int S, void* const* out, hipStrea
     prof_op(s, "bert_mean_pool", 2.0 * T * D, (double)T * D * 4 + (double)B * D * 4, [&] {
       masked_mean(rows, w.has_mask ? w.mask_ids : nullptr, y, B, S, D, s);
     });
+  }
+  if (seq_head) {
+    float* y = static_cast<float*>(out[o++]);
+    prof_op(s, "bert_seq_head", 2.0 * B * D * (double)L, (double)L * D * 4 + (double)B * (D + L) * 4, [&] {
+      bert_dense_rows(pool_y, (size_t)D, ptr<float>(m_.head_w), ptr<float>(m_.head_b), y, B, D, L, false, s);
+    });
+  }
+  if (tok_head) {
+    float* y0 = static_cast<float*>(out[o++]);
+    float* y1 = (io & SPI_BERT_HEAD_QA) ? static_cast<float*>(out[o++]) : nullptr;
+    const double flops = 2.0 * T * D * (double)L, wy = (double)L * D * 4 + (double)T * L * 4;
+    if (!cls_only)
+      prof_op(s, "bert_token_head", flops, (double)T * D * 4 + wy, [&] {
+        bert_token_head(kHeadSrcRows, rows, 0, nullptr, nullptr, 0.f, ptr<float>(m_.head_w), ptr<float>(m_.head_b), y0,
+                        y1, T, D, L, s);
+      });
+    else  // fused with the last LayerNorm: the fold's two-plane b, else the fp32 rows a
+      prof_op(s, "bert_ln_token_head", flops, (double)T * D * 4 + wy, [&] {
+        bert_token_head(m_.ln_fold ? kHeadSrcPlanes : kHeadSrcPreLn, w.bufs[m_.ln_fold ? kBtHidden : kBtAttn],
+                        (size_t)T * D, ptr<float>(l.g), ptr<float>(l.b), m_.eps, ptr<float>(m_.head_w),
+                        ptr<float>(m_.head_b), y0, y1, T, D, L, s);
+      });
   }
 }
 

@@ -49,6 +49,7 @@ class Model {
   size_t weight_bytes() const { return m_.blob_bytes; }
   uint64_t weight_digest() const { return m_.digest; }
   const std::string& describe() const { return desc_; }
+  int bert_num_labels() const { return m_.num_labels; }  // the task head's label count, 0 without a head
   double flops(int64_t batch) const { return model_flops(m_, batch); }
   // Debug exports (spi_model_workspace_plan, spi_model_plan_check): what workspace() allocates, and the
   // forward walked without a launch against it; both work on a host-only replica.

@@ -274,7 +274,8 @@ struct Packer {
     if (m.D % 64 != 0 || m.D > 1024) throw std::runtime_error("hidden size must be a multiple of 64, <= 1024");
   }
   void build_resnet(const PMap& p);
-  void build_bert(const PMap& p);
+  void build_bert(const PMap& p, const PMap& all);
+  void pack_bert_head(const PMap& all);
   void build_vit(const PMap& p);
 };
 
@@ -382,7 +383,44 @@ void Packer::build_resnet(const PMap& p) {
   }
 }
 
-void Packer::build_bert(const PMap& p) {
+// The one tensor of the unstripped parameter list named `name` or ending in ".name": the task heads'
+// parameters sit beside the `bert.` prefix strip_prefix removes, not under it.
+const spi_named_tensor* find_head_param(const PMap& all, const std::string& name, const char* bit) {
+  const spi_named_tensor* found = nullptr;
+  int n = 0;
+  for (const auto& kv : all)
+    if (kv.first == name || ends_with(kv.first, "." + name)) found = kv.second, ++n;
+  if (n == 0) throw std::runtime_error(std::string("bert_io: ") + bit + " needs parameter '" + name + "'");
+  if (n > 1)
+    throw std::runtime_error(std::string("bert_io: ") + bit + ": parameter '" + name + "' is ambiguous (" +
+                             std::to_string(n) + " tensors end in it)");
+  return found;
+}
+
+// The task head's dense layer, appended as plain fp32 [L][D] and [L], each on its own 256-byte line.
+void Packer::pack_bert_head(const PMap& all) {
+  const int io = m.bert_io, D = m.D;
+  const bool qa = (io & SPI_BERT_HEAD_QA) != 0, seq = (io & SPI_BERT_HEAD_SEQUENCE) != 0;
+  const char* bit = qa ? "SPI_BERT_HEAD_QA" : seq ? "SPI_BERT_HEAD_SEQUENCE" : "SPI_BERT_HEAD_TOKEN";
+  const std::string name = qa ? "qa_outputs" : "classifier";
+  const spi_named_tensor* w = find_head_param(all, name + ".weight", bit);
+  const spi_named_tensor* b = find_head_param(all, name + ".bias", bit);
+  if (w->ndim != 2 || w->shape[1] != D || w->shape[0] < 1 || b->ndim != 1 || b->shape[0] != w->shape[0])
+    throw std::runtime_error("bert: " + name + ".weight must be [L][D] with D = " + std::to_string(D) + " and " + name +
+                             ".bias [L]");
+  const int64_t L = w->shape[0];
+  if (qa && L != 2)
+    throw std::runtime_error("bert_io: SPI_BERT_HEAD_QA needs qa_outputs.weight [2][D], got " + std::to_string(L) + " rows");
+  const int64_t lmax = seq ? 1024 : 64;
+  if (L > lmax)
+    throw std::runtime_error(std::string("bert_io: ") + bit + " takes 1 .. " + std::to_string(lmax) + " labels, " + name +
+                             ".weight has " + std::to_string(L));
+  m.num_labels = (int)L;
+  m.head_w = pack_vec(fdata(w), (int)numel(w));
+  m.head_b = pack_vec(fdata(b), (int)L);
+}
+
+void Packer::build_bert(const PMap& p, const PMap& all) {
   const spi_named_tensor* we = need(p, "embeddings.word_embeddings.weight");
   m.vocab = (int)we->shape[0];
   const int D = m.D = (int)we->shape[1];
@@ -439,7 +477,7 @@ void Packer::build_bert(const PMap& p) {
     if (te->ndim != 2 || te->shape[1] != D) throw std::runtime_error("bert: token_type_embeddings.weight must be [types][D]");
     m.type_table = pack_vec(fdata(te), (int)numel(te));
   }
-  if (m.bert_io & SPI_BERT_OUT_POOLER) {
+  if (m.bert_io & (SPI_BERT_OUT_POOLER | SPI_BERT_HEAD_SEQUENCE)) {  // the sequence head reads the pooled vector
     for (const char* nm : {"pooler.dense.weight", "pooler.dense.bias"})
       if (!has(p, nm))
         throw std::runtime_error(std::string("bert_io: SPI_BERT_OUT_POOLER needs parameter '") + nm +
@@ -451,6 +489,7 @@ void Packer::build_bert(const PMap& p) {
     m.pool_w = pack_vec(fdata(pw), (int)numel(pw));
     m.pool_b = pack_vec(fdata(pb), D);
   }
+  if (m.bert_io & (SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA)) pack_bert_head(all);
 }
 
 void Packer::build_vit(const PMap& p) {
@@ -532,10 +571,13 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT parameter names");
   }
   if (const int io = cfg.bert_io) {  // spi_codelet.h: enum spi_bert_io
-    constexpr int known = SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | SPI_BERT_NO_HIDDEN | SPI_BERT_TOKEN_TYPES;
+    constexpr int heads = SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA;
+    constexpr int known = SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | SPI_BERT_NO_HIDDEN | SPI_BERT_TOKEN_TYPES | heads;
     if (io & ~known) throw std::runtime_error("bert_io: unknown bits " + std::to_string(io & ~known));
     if (m.family != SPI_FAMILY_BERT) throw std::runtime_error("bert_io is set, but the model is not a BERT");
-    if ((io & SPI_BERT_NO_HIDDEN) && !(io & (SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN)))
+    if ((io & heads) & ((io & heads) - 1))
+      throw std::runtime_error("bert_io: at most one of SPI_BERT_HEAD_SEQUENCE, SPI_BERT_HEAD_TOKEN, SPI_BERT_HEAD_QA");
+    if ((io & SPI_BERT_NO_HIDDEN) && !(io & (SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | heads)))
       throw std::runtime_error("bert_io: SPI_BERT_NO_HIDDEN leaves no output; select SPI_BERT_OUT_POOLER or SPI_BERT_OUT_MEAN");
     m.bert_io = io;
   }
@@ -557,7 +599,7 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     m.eps = cfg.eps > 0 ? cfg.eps : 1e-12f;
     m.ln_fold = ln_fold_enabled(m.prec, kBertLnFold);
     m.seq = cfg.seq_len;
-    pk.build_bert(strip_prefix(p, "embeddings.word_embeddings.weight"));
+    pk.build_bert(strip_prefix(p, "embeddings.word_embeddings.weight"), p);
     os << "bert L" << m.layers << " D" << m.D << " H" << m.heads << " FF" << m.ffn << " S<=" << m.seq;
   } else if (m.family == SPI_FAMILY_VIT) {
     m.eps = cfg.eps > 0 ? cfg.eps : 1e-6f;
@@ -576,6 +618,12 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
                           std::make_pair((m.bert_io & SPI_BERT_OUT_POOLER) != 0, "pooler"),
                           std::make_pair((m.bert_io & SPI_BERT_OUT_MEAN) != 0, "mean")})
       if (o.first) outs += (outs.empty() ? "" : ",") + std::string(o.second);
+    const std::string L = std::to_string(m.num_labels);
+    const std::string head = (m.bert_io & SPI_BERT_HEAD_SEQUENCE) ? "seq_logits" + L
+                             : (m.bert_io & SPI_BERT_HEAD_TOKEN)  ? "token_logits" + L
+                             : (m.bert_io & SPI_BERT_HEAD_QA)     ? "qa_start,qa_end"
+                                                                  : "";
+    if (!head.empty()) outs += (outs.empty() ? "" : ",") + head;
     os << " out[" << outs << "] in[ids,mask" << ((m.bert_io & SPI_BERT_TOKEN_TYPES) ? ",types]" : "]");
   }
   m.desc = os.str();

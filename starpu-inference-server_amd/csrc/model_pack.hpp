@@ -86,6 +86,10 @@ struct PackedModel {
   // pooler.dense as plain fp32 [D][D] plus its bias.
   int bert_io = 0, type_vocab = 1;
   size_t type_table = 0, pool_w = 0, pool_b = 0;
+  // The task head (SPI_BERT_HEAD_*): classifier / qa_outputs as plain fp32 [num_labels][D] plus its bias,
+  // appended after the above; SPI_BERT_HEAD_SEQUENCE also packs the pooler (once).  0 labels: no head.
+  int num_labels = 0;
+  size_t head_w = 0, head_b = 0;
   LnW emb_ln, final_ln;
   std::vector<TfLayer> tf;
   // ViT

@@ -24,7 +24,8 @@ int num_outputs(const PackedModel& m, const ReplicaOptions& o) {
   if (o.image_io)
     return !(o.image_io & SPI_IMAGE_NO_LOGITS) + !!(o.image_io & SPI_IMAGE_OUT_PROBS) + 2 * !!(o.image_io & SPI_IMAGE_OUT_TOPK);
   if (m.family != SPI_FAMILY_BERT) return 1;
-  return !(m.bert_io & SPI_BERT_NO_HIDDEN) + !!(m.bert_io & SPI_BERT_OUT_POOLER) + !!(m.bert_io & SPI_BERT_OUT_MEAN);
+  return !(m.bert_io & SPI_BERT_NO_HIDDEN) + !!(m.bert_io & SPI_BERT_OUT_POOLER) + !!(m.bert_io & SPI_BERT_OUT_MEAN) +
+         !!(m.bert_io & (SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN)) + 2 * !!(m.bert_io & SPI_BERT_HEAD_QA);
 }
 
 void check_io(const PackedModel& m, const ReplicaOptions& o, const spi_codelet_args& a, const size_t* in_bytes,
@@ -44,7 +45,7 @@ void check_io(const PackedModel& m, const ReplicaOptions& o, const spi_codelet_a
     return e;
   };
   size_t expect_out = 0;
-  size_t expect_more[3] = {0, 0, 0};  // the outputs after the first (BERT: bert_io; ResNet / ViT: image_io)
+  size_t expect_more[4] = {0, 0, 0, 0};  // the outputs after the first (BERT: bert_io; ResNet / ViT: image_io)
   int i64_out = -1;                   // the output that is SPI_DTYPE_I64 (the top-k indices), if any
   if (m.family == SPI_FAMILY_AFFINE) {
     if (a.input_types[0] != SPI_DTYPE_F32) throw std::runtime_error("[ERROR] Input type mismatch");
@@ -99,9 +100,19 @@ void check_io(const PackedModel& m, const ReplicaOptions& o, const spi_codelet_a
     const int64_t S = a.dims[0][1];
     if (S < 1 || S > m.seq || S > m.maxpos)
       throw std::runtime_error("sequence length " + std::to_string(S) + " exceeds " + std::to_string(m.seq));
-    // hidden [B,S,D] unless SPI_BERT_NO_HIDDEN, then the selected [B,D] sentence outputs
-    expect_out = (m.bert_io & SPI_BERT_NO_HIDDEN) ? (size_t)B * m.D * 4 : (size_t)B * S * m.D * 4;
-    expect_more[0] = expect_more[1] = (size_t)B * m.D * 4;
+    // hidden [B,S,D] unless SPI_BERT_NO_HIDDEN, then the selected [B,D] sentence outputs, then the head's:
+    // [B,L] (sequence), [B,S,L] (token) or [B,S] twice (QA)
+    const int io = m.bert_io;
+    size_t want[5];
+    int n = 0;
+    if (!(io & SPI_BERT_NO_HIDDEN)) want[n++] = (size_t)B * S * m.D * 4;
+    if (io & SPI_BERT_OUT_POOLER) want[n++] = (size_t)B * m.D * 4;
+    if (io & SPI_BERT_OUT_MEAN) want[n++] = (size_t)B * m.D * 4;
+    if (io & SPI_BERT_HEAD_SEQUENCE) want[n++] = (size_t)B * m.num_labels * 4;
+    if (io & SPI_BERT_HEAD_TOKEN) want[n++] = (size_t)B * S * m.num_labels * 4;
+    if (io & SPI_BERT_HEAD_QA) want[n++] = (size_t)B * S * 4, want[n++] = (size_t)B * S * 4;
+    expect_out = want[0];
+    for (int i = 1; i < n; ++i) expect_more[i - 1] = want[i];
   }
   for (int i = 0; i < no; ++i) {
     if (a.output_types[i] != (i == i64_out ? SPI_DTYPE_I64 : SPI_DTYPE_F32))
@@ -313,7 +324,10 @@ double model_flops(const PackedModel& m, int64_t B) {
            4.0 * B * S * S * m.D;
     if (m.family == SPI_FAMILY_VIT)
       f += 2.0 * B * m.npatch * (double)m.D * m.patch_proj.k + 2.0 * B * m.head.n * m.head.k;
-    if (m.bert_io & SPI_BERT_OUT_POOLER) f += 2.0 * B * (double)m.D * m.D;
+    // the pooler once, as an output or under the sequence head; then the head's dense layer
+    if (m.bert_io & (SPI_BERT_OUT_POOLER | SPI_BERT_HEAD_SEQUENCE)) f += 2.0 * B * (double)m.D * m.D;
+    if (m.bert_io & SPI_BERT_HEAD_SEQUENCE) f += 2.0 * B * (double)m.D * m.num_labels;
+    if (m.bert_io & (SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA)) f += 2.0 * T * (double)m.D * m.num_labels;
   }
   return f;
 }
@@ -398,11 +412,11 @@ WorkspacePlan workspace_plan(const PackedModel& m, const ReplicaOptions& o) {
     sz[kBtAttn] = T * D * 4;
     sz[kBtFfn] = T * m.ffn * es;
     sz[kBtStats1] = sz[kBtStats2] = T * (D / 64) * 8;
-    sz[kBtCls] = (m.bert_io & SPI_BERT_NO_HIDDEN) ? B * D * 4 : 0;
+    sz[kBtCls] = (bert_cls_rows_floats(m) + bert_pooled_ws_floats(m)) * 4;
   } else if (m.family == SPI_FAMILY_VIT) {
     const size_t T = B * (m.npatch + 1);
     sz.assign(kVtBufs, 0);
-    sz[kVtPatches] = B * m.npatch * m.patch_proj.k * es;
+    sz[kVtPatches] = B * m.npatch * m.patch_proj.k * es + vit_patches_tail_bytes(m);
     sz[kVtProj] = B * m.npatch * D * 4;
     sz[kVtX] = T * D * 4;
     sz[kVtLn] = T * D * es;

@@ -35,9 +35,10 @@ enum RnBuf { kRnIngest, kRnAct0, kRnAct1, kRnAct2, kRnAct3, kRnAct4, kRnPooled, 
 // BERT: hidden rows fp32 (fold: the pre-LN2 rows b as two fp16 planes) and their compute-type copy;
 // qkv; ctx; the attention block's output a, fp32 (fold: the pre-LN1 rows as two planes); the FFN
 // hidden rows; the LayerNorm-fold row statistics S1 (of a) and S2 (of b); the final LayerNorm's
-// class-token rows, fp32 (SPI_BERT_NO_HIDDEN with the pooler alone).
+// class-token rows, fp32 (SPI_BERT_NO_HIDDEN with the pooler alone), followed max_batch x D floats on by
+// the sequence head's pooled vector when the pooler is not an output.
 enum BertBuf { kBtHidden, kBtHidden16, kBtQkv, kBtCtx, kBtAttn, kBtFfn, kBtStats1, kBtStats2, kBtCls, kBtBufs };
-// ViT: patches; projected patches f32; residual stream x f32 (fold: two fp16 planes); LN output; qkv;
+// ViT: patches (plus vit_patches_tail_bytes, zeroed, where the rows are ragged); projected patches f32; residual stream x f32 (fold: two fp16 planes); LN output; qkv;
 // ctx; mlp hidden; the LayerNorm'd class-token rows; the LayerNorm-fold row statistics of x.
 enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, kVtStats, kVtLogits, kVtResized, kVtBufs };
 
@@ -45,7 +46,7 @@ enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, 
 // I/O contract
 // ---------------------------------------------------------------------------
 int num_inputs_max(const PackedModel& m);
-// BERT: the outputs bert_io selects, in order hidden, pooler, mean.  ResNet / ViT: the outputs
+// BERT: the outputs bert_io selects, in order hidden, pooler, mean, the head's.  ResNet / ViT: the outputs
 // image_io selects, in order logits, probabilities, top-k values, top-k indices.
 int num_outputs(const PackedModel& m, const ReplicaOptions& o);
 // Validates the task's I/O against the replica; throws std::runtime_error with the reference's
@@ -163,6 +164,23 @@ void walk_resnet(const PackedModel& m, int B, V&& v) {
 // FLOPs and workspace
 // ---------------------------------------------------------------------------
 double model_flops(const PackedModel& m, int64_t B);
+
+// BERT's kBtCls buffer: the class-token rows [max_batch][D] fp32 under SPI_BERT_NO_HIDDEN, then the sequence
+// head's pooled vector [max_batch][D] fp32 when the pooler is not an output.  workspace_plan sizes the buffer
+// and the epilogue addresses the pooled vector from these two.
+inline size_t bert_cls_rows_floats(const PackedModel& m) {
+  return (m.bert_io & SPI_BERT_NO_HIDDEN) ? (size_t)m.max_batch * m.D : 0;
+}
+inline size_t bert_pooled_ws_floats(const PackedModel& m) {
+  return (m.bert_io & SPI_BERT_HEAD_SEQUENCE) && !(m.bert_io & SPI_BERT_OUT_POOLER) ? (size_t)m.max_batch * m.D : 0;
+}
+// ViT's kVtPatches rows are patch_proj.k elements long and the dense GEMM stages A in 16-byte chunks, taking a
+// chunk whenever its first element lies inside K.  With a row that is no whole number of chunks (patch 14:
+// K = 588 fp16) the last chunk runs into the next row -- finite values against zero weights -- and on the
+// last row past the rows: the buffer ends with this many zeroed bytes for it to read.
+inline size_t vit_patches_tail_bytes(const PackedModel& m) {
+  return m.family == SPI_FAMILY_VIT && ((size_t)m.patch_proj.k * (m.f16 ? 2 : 4)) % 16 != 0 ? 16 : 0;
+}
 
 struct WorkspacePlan {
   std::vector<size_t> bytes;   // per buffer of the family's enum, at max_batch

@@ -705,6 +705,27 @@ int spi_op_masked_mean(const float* h, const int64_t* mask, float* y, int32_t B,
   });
 }
 
+int spi_op_bert_token_head(int32_t src, const void* x, int64_t plane, const float* g, const float* b, float eps,
+                           const float* W, const float* bias, float* y0, float* y1, int32_t T, int32_t D, int32_t L,
+                           void* stream) {
+  if (!x || !W || !bias || !y0 || T <= 0 || D <= 0 || L <= 0 || plane < 0)
+    return fail("invalid bert_token_head arguments");
+  return guarded([&] {
+    spi::bert_token_head(src, x, (size_t)plane, g, b, eps, W, bias, y0, y1, T, D, L, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_bert_dense_rows(const float* h, int64_t ld, const float* W, const float* bias, float* y, int32_t B,
+                           int32_t D, int32_t N, int32_t activation, void* stream) {
+  if (!h || !W || !bias || !y || B <= 0 || D <= 0 || N <= 0 || ld < D || (activation != 0 && activation != 1))
+    return fail("invalid bert_dense_rows arguments");
+  return guarded([&] {
+    spi::bert_dense_rows(h, (size_t)ld, W, bias, y, B, D, N, activation == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
 int spi_op_softmax_topk(const float* x, int64_t ldx, float* probs, float* topv, int64_t* topi, int32_t B, int32_t N,
                         int32_t k, int32_t topk_probs, void* stream) {
   if (!x) return fail("softmax_topk: x is null");

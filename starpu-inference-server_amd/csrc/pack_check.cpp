@@ -1,7 +1,8 @@
 // Stand-alone check of the host-only packer (make pack_check): packs three small models whose
 // tensors are synthesised here with the closed-form fill of tests/golden/make_replica_digests.py
 // and prints the digests, which equal that table's resnet_basic / bert_d128 / vit_d128 entries; then the
-// BERT once more with every spi_model_config.bert_io bit set, checking what the bits append to the blob.
+// BERT once more with every spi_model_config.bert_io bit set, and once per task head (SPI_BERT_HEAD_*),
+// checking what the bits append to the blob.
 // Built with the address and undefined-behaviour sanitizers, no HIP.
 #include <cstdio>
 #include <deque>
@@ -95,6 +96,27 @@ int main() {
       io.pool_b + 128 * sizeof(float) != io.blob_bytes) {
     std::fprintf(stderr, "bert_io packing: unexpected blob growth %zu -> %zu\n", plain.blob_bytes, io.blob_bytes);
     return 1;
+  }
+  // Task heads: the head's parameters sit beside the `bert.` prefix, not under it.  One case per head; each
+  // appends its fp32 [L][128] weight and [L] bias on 256-byte lines (the sequence head the pooler too).
+  bt.linear("classifier", 5, 128), bt.linear("qa_outputs", 2, 128);
+  const struct { const char* name; int bit, labels; size_t pooler; const char* out; } heads[] = {
+      {"seq_head", SPI_BERT_HEAD_SEQUENCE, 5, 128 * 128 + 128, "out[hidden,seq_logits5] in[ids,mask]"},
+      {"token_head", SPI_BERT_HEAD_TOKEN, 5, 0, "out[hidden,token_logits5] in[ids,mask]"},
+      {"qa_head", SPI_BERT_HEAD_QA, 2, 0, "out[hidden,qa_start,qa_end] in[ids,mask]"}};
+  for (const auto& h : heads) {
+    cfg.bert_io = h.bit;
+    const spi::PackedModel m = spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+    std::printf("bert_d128|fp16|%s %016llx %zu %s\n", h.name, (unsigned long long)m.digest, m.blob_bytes, m.desc.c_str());
+    const size_t grow = (h.pooler + (size_t)h.labels * 128 + h.labels) * sizeof(float);
+    const std::string want = h.out;
+    if (m.num_labels != h.labels || m.blob_bytes < plain.blob_bytes + grow || m.blob_bytes > plain.blob_bytes + grow + 3 * 256 ||
+        m.head_w < plain.blob_bytes || m.head_b + h.labels * sizeof(float) != m.blob_bytes || m.digest == plain.digest ||
+        m.desc.size() < want.size() || m.desc.compare(m.desc.size() - want.size(), want.size(), want) != 0) {
+      std::fprintf(stderr, "%s packing: unexpected blob %zu -> %zu, %d labels, %s\n", h.name, plain.blob_bytes,
+                   m.blob_bytes, m.num_labels, m.desc.c_str());
+      return 1;
+    }
   }
   return 0;
 }

@@ -2,7 +2,9 @@
 // models (same closed-form tensors) in every precision and, for each, counts the FLOPs, plans the
 // workspace, walks the forward at every batch 1 .. max_batch against it (plan_check: the checks of each
 // launch, with no launch) and holds one accepted and one refused task against the I/O contract; prints
-// one line per model.  Built with the address and undefined-behaviour sanitizers, no HIP.
+// one line per model; then the BERT with task heads (SPI_BERT_HEAD_*): output counts up to five, their byte
+// sizes, the pooled vector's place in the workspace.  Built with the address and undefined-behaviour
+// sanitizers, no HIP.
 #include <cstdio>
 #include <deque>
 #include <initializer_list>
@@ -148,5 +150,56 @@ int main() {
                   c.name, pr.name, spi::model_flops(m, 1), spi::model_flops(m, 3), bytes, plan.bytes.size(),
                   plan.partial_floats, plan.partial_planned, steps, spi::replica_desc(m, o).c_str());
     }
+  // BERT task heads: the output count and byte sizes check_io holds a task to -- up to five outputs (hidden,
+  // pooler, mean, start, end) -- the pooled vector's place in the workspace, and the walk at max_batch.
+  bt.linear("bert.pooler.dense", 128, 128), bt.linear("classifier", 5, 128), bt.linear("qa_outputs", 2, 128);
+  const int64_t B = 2, S = 16, D = 128, Lh = 5;
+  const struct { const char* name; int io; std::vector<size_t> out; size_t cls; } heads[] = {
+      {"seq_head", SPI_BERT_HEAD_SEQUENCE, {(size_t)(B * S * D), (size_t)(B * Lh)}, 8 * 128 * 4},
+      {"no_hidden|seq_head", SPI_BERT_NO_HIDDEN | SPI_BERT_HEAD_SEQUENCE, {(size_t)(B * Lh)}, 2 * 8 * 128 * 4},
+      {"no_hidden|token_head", SPI_BERT_NO_HIDDEN | SPI_BERT_HEAD_TOKEN, {(size_t)(B * S * Lh)}, 8 * 128 * 4},
+      {"pooler|mean|qa_head", SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | SPI_BERT_HEAD_QA,
+       {(size_t)(B * S * D), (size_t)(B * D), (size_t)(B * D), (size_t)(B * S), (size_t)(B * S)}, 0}};
+  for (const auto& h : heads) {
+    spi_model_config cfg{};
+    cfg.family = SPI_FAMILY_AUTO, cfg.precision = SPI_PREC_F16, cfg.max_batch = 8, cfg.num_heads = 2, cfg.seq_len = 16;
+    cfg.bert_io = h.io;
+    const spi::PackedModel m = spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+    const spi::ReplicaOptions o;
+    spi_codelet_args a{};
+    a.num_inputs = 2, a.num_outputs = (uint32_t)h.out.size();
+    size_t in_bytes[2] = {(size_t)(B * S * 8), (size_t)(B * S * 8)}, out_bytes[SPI_MAX_OUTPUTS] = {};
+    for (int i = 0; i < 2; ++i) a.input_types[i] = SPI_DTYPE_I64, a.num_dims[i] = 2, a.dims[i][0] = B, a.dims[i][1] = S;
+    for (size_t i = 0; i < h.out.size(); ++i) a.output_types[i] = SPI_DTYPE_F32, out_bytes[i] = h.out[i] * 4;
+    auto takes = [&] {
+      try {
+        spi::check_io(m, o, a, in_bytes, out_bytes);
+        return true;
+      } catch (const std::runtime_error&) {
+        return false;
+      }
+    };
+    bool ok = spi::num_outputs(m, o) == (int)h.out.size() && takes();
+    out_bytes[h.out.size() - 1] += 4;  // the last output one element too long
+    ok = ok && !takes();
+    out_bytes[h.out.size() - 1] -= 4;
+    a.num_outputs -= 1;  // one output too few
+    ok = ok && !takes();
+    const spi::WorkspacePlan plan = spi::workspace_plan(m, o);
+    int steps = 0;
+    try {
+      steps = spi::plan_check(m, o, m.max_batch, m.seq);
+    } catch (const std::runtime_error& e) {
+      std::fprintf(stderr, "bert_d128|fp16|%s: %s\n", h.name, e.what());
+      ok = false;
+    }
+    if (!ok || plan.bytes.size() != (size_t)spi::kBtBufs || plan.bytes[spi::kBtCls] != h.cls) {
+      std::fprintf(stderr, "bert_d128|fp16|%s: outputs, check_io or the workspace plan are not the expected ones\n", h.name);
+      rc = 1;
+    }
+    std::printf("bert_d128|fp16|%s| %d outputs, %d labels, flops(3) %.0f, class-token buffer %zu bytes, %d steps fit, %s\n",
+                h.name, spi::num_outputs(m, o), m.num_labels, spi::model_flops(m, 3), plan.bytes[spi::kBtCls], steps,
+                spi::replica_desc(m, o).c_str());
+  }
   return rc;
 }

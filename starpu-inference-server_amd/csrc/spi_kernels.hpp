@@ -146,6 +146,18 @@ void bert_embed(const int64_t* ids, const float* word, const float* pos,
 // Pooler: y[b][n] = tanh(bias[n] + sum_k h[b ld + k] W[n][k]); W fp32 [D][D], y [B][D].
 void bert_pooler(const float* h, size_t ld, const float* W, const float* bias, float* y, int B, int D,
                  hipStream_t s);
+// The pooler's kernel as a dense layer over N columns: y[b][n] = act(bias[n] + sum_k h[b ld + k] W[n][k]),
+// W fp32 [N][D], y [B][N], act = tanh or none; 1 <= N <= 1024.  N = D with tanh is bert_pooler, bit for bit.
+void bert_dense_rows(const float* h, size_t ld, const float* W, const float* bias, float* y, int B, int D, int N,
+                     bool tanh_act, hipStream_t s);
+// Token-level task head (bert_head.hip): y[t][l] = bias[l] + sum_c h[t][c] W[l][c], t < T, l < L <= 64, fp32,
+// fixed summation order, a row's result independent of T and of the row's place.  h[t] by source kind:
+// normalised fp32 rows; pre-LayerNorm fp32 rows, normalised in registers with g / b / eps and never stored;
+// or pre-LayerNorm rows in two fp16 planes (hi at x, lo `plane` elements on), likewise.  Rows are D apart;
+// D % 64 == 0, D <= 1024.  y1 null: y0 is [T][L]; else L == 2 and label 0 goes to y0 [T], label 1 to y1 [T].
+enum HeadSrc { kHeadSrcRows = 0, kHeadSrcPreLn = 1, kHeadSrcPlanes = 2 };
+void bert_token_head(int src, const void* x, size_t plane, const float* g, const float* b, float eps, const float* W,
+                     const float* bias, float* y0, float* y1, int T, int D, int L, hipStream_t s);
 // Masked mean: y[b] = sum_s m[b][s] h[b][s] / max(sum_s m[b][s], 1e-9), m = (mask != 0); a null mask
 // counts every token.  h [B][S][D], y [B][D].
 void masked_mean(const float* h, const int64_t* mask, float* y, int B, int S, int D, hipStream_t s);

@@ -496,6 +496,25 @@ def bert_pooler(h, ld, W, bias, out, B, D, stream=None):
     return out
 
 
+HEAD_SRC = {"rows": 0, "pre_ln": 1, "planes": 2}
+
+
+def bert_token_head(src, x, W, bias, y0, T, D, L, y1=None, plane=0, gamma=None, beta=None, eps=0.0, stream=None):
+    """Token-level head: y0 fp32 [T][L] = bias + h W^T, or with y1 (L == 2) label 0 into y0 [T] and label 1 into
+    y1 [T].  src "rows": x fp32 [T][D], normalised; "pre_ln": x fp32 pre-LayerNorm rows, normalised in the kernel
+    with gamma / beta / eps; "planes": the same rows as fp16 hi at x and lo `plane` elements after it."""
+    _check(lib.spi_op_bert_token_head(HEAD_SRC[src], _ptr(x), plane, _ptr(gamma), _ptr(beta), eps, _ptr(W), _ptr(bias),
+                                      _ptr(y0), _ptr(y1), T, D, L, _stream(stream)))
+    return y0, y1
+
+
+def bert_dense_rows(h, ld, W, bias, out, B, D, N, activation=None, stream=None):
+    """out fp32 [B][N] = act(bias + h_rows W^T), W fp32 [N][D]; activation None or "tanh" (N = D: bert_pooler)."""
+    act = {None: 0, "none": 0, "tanh": 1}[activation]
+    _check(lib.spi_op_bert_dense_rows(_ptr(h), ld, _ptr(W), _ptr(bias), _ptr(out), B, D, N, act, _stream(stream)))
+    return out
+
+
 def masked_mean(h, mask, out, B, S, D, stream=None):
     """out fp32 [B][D] = masked mean over S of h fp32 [B][S][D]; mask int64 [B][S] or None (every token)."""
     _check(lib.spi_op_masked_mean(_ptr(h), _ptr(mask), _ptr(out), B, S, D, _stream(stream)))

@@ -172,6 +172,15 @@ def batching_config(kind: str = "fixed", min_batch: int = 1, batch_limit: int = 
     return b
 
 
+def bert_output_specs(replica: ModelReplica, seq: int, dim: int) -> list[tuple[int, type]]:
+    """Runtime's output_specs for a BERT replica: the per-sample element count of each output bert_io selects,
+    in the replica's order -- S D (hidden), D (pooler, mean), then the task head's L ("seq_head"), S L
+    ("token_head") or S and S ("qa_head") -- all float32, so per-job slicing follows the batch dimension."""
+    from .codelet import output_specs
+    return [(int(np.prod(shape[1:])), np.float32)
+            for shape, _ in output_specs(1, seq=seq, dim=dim, bert_io=replica.bert_io, num_labels=replica.num_labels)]
+
+
 class Runtime:
     """Eager priority queue over `workers_per_device` HIP workers per replica."""
 

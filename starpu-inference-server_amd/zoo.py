@@ -302,11 +302,54 @@ class BertSegmentsWrapper(nn.Module):
                          return_dict=False)[0]
 
 
+class BertHeadWrapper(nn.Module):
+    """A fine-tuned HF head model (BertForSequenceClassification, BertForTokenClassification or
+    BertForQuestionAnswering, eval) returning HF's tuple as a replica with a task head serves it:
+    last_hidden_state and pooler_output first, where `outputs` names them ("hidden", "pooler"), then the
+    logits -- [B,L] ("sequence"), [B,S,L] ("token"), or start and end logits [B,S] each ("qa").  The
+    parameters are model.bert.* beside model.classifier.* / model.qa_outputs.*, as HF names them."""
+
+    def __init__(self, model: nn.Module, head: str, outputs=("hidden",)):
+        super().__init__()
+        if head not in ("sequence", "token", "qa"):
+            raise ValueError(f"unknown BERT head {head!r}; known: 'sequence', 'token', 'qa'")
+        if "pooler" in outputs and head != "sequence":
+            raise ValueError("HF's token and QA head models have no pooler (add_pooling_layer=False)")
+        self.model = model
+        self.head = head
+        self.outputs = tuple(outputs)
+
+    @property
+    def bert(self) -> nn.Module:
+        return self.model.bert
+
+    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor):
+        out = self.model.bert(input_ids=input_ids, attention_mask=attention_mask, return_dict=False)
+        hidden = out[0]
+        res = []
+        if "hidden" in self.outputs:
+            res.append(hidden)
+        if "pooler" in self.outputs:
+            res.append(out[1])
+        if self.head == "sequence":
+            res.append(self.model.classifier(self.model.dropout(out[1])))
+        elif self.head == "token":
+            res.append(self.model.classifier(self.model.dropout(hidden)))
+        else:
+            start, end = self.model.qa_outputs(hidden).split(1, dim=-1)
+            res += [start.squeeze(-1).contiguous(), end.squeeze(-1).contiguous()]
+        return tuple(res)
+
+
 def bert(layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072,
-         vocab: int = 30522, max_position: int = 512, seed: int = 0, init_std: float = 0.02) -> BertWrapper:
+         vocab: int = 30522, max_position: int = 512, seed: int = 0, init_std: float = 0.02,
+         head: str | None = None, num_labels: int = 2, outputs=("hidden",)) -> nn.Module:
+    """BertModel in BertWrapper; with head = "sequence" | "token" | "qa" the HF head model of num_labels
+    labels (QA: 2) in BertHeadWrapper, which returns the `outputs` it names, then the logits."""
     import logging
 
-    from transformers import BertConfig, BertModel
+    from transformers import (BertConfig, BertForQuestionAnswering, BertForSequenceClassification,
+                              BertForTokenClassification, BertModel)
     from transformers.utils import logging as hf_logging
 
     hf_logging.set_verbosity_error()
@@ -315,12 +358,26 @@ def bert(layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int
     cfg = BertConfig(num_hidden_layers=layers, hidden_size=hidden, num_attention_heads=heads,
                      intermediate_size=intermediate, vocab_size=vocab, max_position_embeddings=max_position,
                      initializer_range=init_std, torchscript=True)
-    model = BertWrapper(BertModel(cfg))
+    if head is None:
+        model = BertWrapper(BertModel(cfg))
+    else:
+        cfg.num_labels = 2 if head == "qa" else num_labels
+        hf = {"sequence": BertForSequenceClassification, "token": BertForTokenClassification,
+              "qa": BertForQuestionAnswering}
+        if head not in hf:
+            raise ValueError(f"unknown BERT head {head!r}; known: {sorted(hf)}")
+        model = BertHeadWrapper(hf[head](cfg), head, outputs)
     with torch.no_grad():
         for m in model.modules():
             if isinstance(m, nn.LayerNorm):
                 m.weight.copy_(1.0 + 0.1 * torch.randn_like(m.weight))
                 m.bias.copy_(0.05 * torch.randn_like(m.bias))
+        if head is not None:
+            # HF's 0.02 init gives logits too small for a normalised comparison to mean anything (the
+            # reason vit() re-draws its head): weights from N(0, 1/D), bias from N(0, 0.1^2)
+            dense = model.model.qa_outputs if head == "qa" else model.model.classifier
+            dense.weight.copy_(torch.randn_like(dense.weight) / hidden ** 0.5)
+            dense.bias.copy_(0.1 * torch.randn_like(dense.bias))
     return model.eval()
 
 
@@ -361,5 +418,5 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
 # name is not an identifier, so give the zoo's modules a loadable qualified name
 # (a traced/scripted model must round-trip through .pt like the reference's).
 for _cls in (BasicBlock, Bottleneck, ResNet, MLPBlock, EncoderBlock, Encoder, VisionTransformer, BertWrapper,
-             BertTupleWrapper, BertSegmentsWrapper, AddConstant):
+             BertTupleWrapper, BertSegmentsWrapper, BertHeadWrapper, AddConstant):
     _cls.__module__ = "spi_zoo"
