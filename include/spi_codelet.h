@@ -267,7 +267,10 @@ typedef struct spi_model_config {
   int32_t family;     /* enum spi_family */
   int32_t precision;  /* enum spi_precision: MFMA operand type */
   int32_t max_batch;  /* largest dims[0] the replica will see */
-  int32_t num_heads;  /* transformers: attention heads (0 = default for family) */
+  int32_t num_heads;  /* transformers: attention heads; hidden / num_heads must be 32 or 64 (hidden a
+                         multiple of 64, <= 1024, so 32-wide models have an even count).  0 = hidden / 64:
+                         a 32-wide model (MiniLM: 384 over 12) must state its count.  Any other width is
+                         refused at creation with a message naming hidden, heads and the two widths. */
   int32_t seq_len;    /* BERT: max sequence length (0 = from position table) */
   int32_t image_size; /* ResNet/ViT: input H = W (0 = 224) */
   float eps;          /* norm epsilon (0 = family default) */

@@ -183,13 +183,17 @@ int spi_op_resize_crop_u8(const uint8_t* x, int32_t nhwc, int32_t B, int32_t H, 
 int spi_op_resize_crop_u8_host(const uint8_t* x, int32_t nhwc, int32_t B, int32_t H, int32_t W, int32_t resize_short,
                                int32_t crop, const float* scale_host, const float* shift_host, float* y, void* stream);
 
-/* Multi-head attention over packed qkv [B*S][3*D] (fp16 or fp32), head_dim 64: ctx [B*S][D] =
+/* Multi-head attention over packed qkv [B*S][3*D] (fp16 or fp32), D = heads * 64: ctx [B*S][D] =
  * softmax(q k^T scale + mask_bias) v per (batch, head); mask_bias fp32 [B][S] added to every query's
  * scores, or null.  Rejected before any launch: a precision other than 0 (fp32) or 1 (fp16), a null
  * qkv or ctx, B, S or heads <= 0, B * heads > 65535 (the grid's y extent), qkv off 16-byte alignment
  * (q / k / v rows are read in 16-byte chunks), ctx off 8-byte alignment (the fp16 kernels' stores). */
 int spi_op_attention(int32_t precision, const void* qkv, const float* mask_bias, void* ctx,
                      int32_t B, int32_t S, int32_t heads, float scale, void* stream);
+/* The same with the head width stated: D = heads * head_dim, head_dim 32 or 64 (any other value is
+ * rejected before any launch, like the above).  spi_op_attention is this with head_dim 64. */
+int spi_op_attention_hd(int32_t precision, const void* qkv, const float* mask_bias, void* ctx, int32_t B,
+                        int32_t S, int32_t heads, int32_t head_dim, float scale, void* stream);
 
 /* Row LayerNorm: x fp32 [rows][D] -> yf fp32 and/or yt (fp16 when precision fp16). */
 int spi_op_layernorm(int32_t precision, const float* x, const float* gamma, const float* beta,
@@ -253,7 +257,8 @@ int spi_op_vit_assemble_planes(const float* patches, const float* cls, const flo
                                float* stats, int32_t B, int32_t P, int32_t D, void* stream);
 
 /* ---- Fused QKV projection + attention (qkv_attn.hip) ----
- * ctx [B S][D] fp16 = attention over q | k | v = A . W^T + bias, D = 64 heads.  A: fp16 [B S][lda];
+ * ctx [B S][D] fp16 = attention over q | k | v = A . W^T + bias, D = 64 heads: 64-wide heads only (32-wide
+ * heads run the QKV GEMM + spi_op_attention_hd, which measured faster).  A: fp16 [B S][lda];
  * W_packed: spi_op_pack_weight(fp16, [3 D][D]) (rows q, k, v; row stride the packed Kpad = D); bias fp32
  * [3 D], required.  in_stats / c1 (both or neither): the LayerNorm fold's consumer -- A holds the rows
  * before the LayerNorm, in_stats their chunk statistics [B S][D / 64][2], W / bias / c1 come from

@@ -278,8 +278,26 @@ def _as_list(out) -> list:
     return [out] if isinstance(out, torch.Tensor) else list(out)
 
 
+def module_num_heads(module: torch.nn.Module) -> int:
+    """The attention head count a module states: HF's config.num_attention_heads on the module or on a
+    model it wraps, else nn.MultiheadAttention.num_heads; 0 where nothing states one.  Two submodules
+    that disagree are an error (one count serves the whole replica)."""
+    found = set()
+    for m in module.modules():
+        n = getattr(getattr(m, "config", None), "num_attention_heads", None)
+        if isinstance(m, torch.nn.MultiheadAttention):
+            n = m.num_heads
+        if isinstance(n, int) and n > 0:
+            found.add(n)
+    if len(found) > 1:
+        raise InferenceExecutionException(f"the module states several attention head counts: {sorted(found)}")
+    return found.pop() if found else 0
+
+
 class ModelReplica:
-    """One device-resident weight replica (BN-folded, MFMA-packed) -- a `spi_model*`."""
+    """One device-resident weight replica (BN-folded, MFMA-packed) -- a `spi_model*`.  num_heads 0 takes
+    the head count the module states (module_num_heads), else hidden / 64; a TorchScript file states
+    none, so a model with 32-wide heads loaded from a .pt needs num_heads."""
 
     def __init__(self, module: torch.nn.Module | str | None, device_id: int = 0, precision: str = "fp16",
                  max_batch: int = 8, family: str | None = None, num_heads: int = 0, seq_len: int = 0,
@@ -313,7 +331,7 @@ class ModelReplica:
         cfg.family = _FAMILIES[family]
         cfg.precision = PRECISIONS[precision]
         cfg.max_batch = max_batch
-        cfg.num_heads = num_heads
+        cfg.num_heads = num_heads or (module_num_heads(module) if module is not None else 0)
         cfg.seq_len = seq_len
         cfg.image_size = image_size
         cfg.eps = eps

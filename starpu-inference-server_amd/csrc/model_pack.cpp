@@ -268,10 +268,13 @@ struct Packer {
     return l;
   }
 
-  void check_heads() {  // transformers: 64-wide heads, num_heads 0 = as many as fit
+  void check_heads() {  // transformers: 32- or 64-wide heads, num_heads 0 = as many 64-wide ones as fit
+    if (m.D <= 0 || m.D % 64 != 0 || m.D > 1024)
+      throw std::runtime_error("hidden size must be a multiple of 64, <= 1024");
     if (m.heads <= 0) m.heads = m.D / 64;
-    if (m.D % m.heads != 0 || m.D / m.heads != 64) throw std::runtime_error("attention head_dim must be 64");
-    if (m.D % 64 != 0 || m.D > 1024) throw std::runtime_error("hidden size must be a multiple of 64, <= 1024");
+    if (m.D % m.heads != 0 || (m.D / m.heads != 32 && m.D / m.heads != 64))
+      throw std::runtime_error("hidden size " + std::to_string(m.D) + " over " + std::to_string(m.heads) +
+                               " attention heads: head_dim must be 32 or 64");
   }
   void build_resnet(const PMap& p);
   void build_bert(const PMap& p, const PMap& all);

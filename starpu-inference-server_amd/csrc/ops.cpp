@@ -458,14 +458,20 @@ int spi_op_resize_crop_u8_host(const uint8_t* x, int32_t nhwc, int32_t B, int32_
 
 int spi_op_attention(int32_t precision, const void* qkv, const float* mask_bias, void* ctx, int32_t B, int32_t S,
                      int32_t heads, float scale, void* stream) {
+  return spi_op_attention_hd(precision, qkv, mask_bias, ctx, B, S, heads, 64, scale, stream);
+}
+
+int spi_op_attention_hd(int32_t precision, const void* qkv, const float* mask_bias, void* ctx, int32_t B, int32_t S,
+                        int32_t heads, int32_t head_dim, float scale, void* stream) {
   if ((precision != 0 && precision != 1) || !qkv || !ctx || B <= 0 || S <= 0 || heads <= 0)
     return fail("invalid attention arguments");
+  if (head_dim != 32 && head_dim != 64) return fail("attention: head_dim must be 32 or 64");
   if ((int64_t)B * heads > 65535) return fail("attention: B * heads is the grid's y extent, at most 65535");
   // the kernels read q / k / v rows in 16-byte chunks and the fp16 ones store ctx 8 bytes at a time
   if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(ctx) & 7))
     return fail("attention: 16-byte aligned qkv and 8-byte aligned ctx");
   return guarded([&] {
-    spi::attention(qkv, mask_bias, ctx, B, S, heads, 64, scale, precision == 1, static_cast<hipStream_t>(stream));
+    spi::attention(qkv, mask_bias, ctx, B, S, heads, head_dim, scale, precision == 1, static_cast<hipStream_t>(stream));
     return check_launch();
   });
 }

@@ -71,7 +71,8 @@ int main() {
     vt.linear(v + "self_attention.out_proj", 128, 128), vt.linear(v + "mlp.0", 256, 128), vt.linear(v + "mlp.3", 128, 256);
   }
   struct Case { const char* name; Tensors* t; int heads, seq, image; } cases[] = {
-      {"resnet_basic", &rn, 0, 0, 64}, {"bert_d128", &bt, 2, 16, 0}, {"vit_d128", &vt, 2, 0, 32}};
+      {"resnet_basic", &rn, 0, 0, 64}, {"bert_d128", &bt, 2, 16, 0}, {"vit_d128", &vt, 2, 0, 32},
+      {"bert_d128_h4", &bt, 4, 16, 0}, {"vit_d128_h4", &vt, 4, 0, 32}};  // the last two: 32-wide heads
   const struct { const char* name; int prec; } precs[] = {{"fp16", SPI_PREC_F16}, {"fp16x3", SPI_PREC_F16X3}, {"fp16m", SPI_PREC_F16M}};
   for (const Case& c : cases)
     for (const auto& pr : precs) {

@@ -16,6 +16,9 @@
 //      O^T = V^T P^T, V^T fragments by ds_read_b64_tr_b16), 16 queries per wave per pass (QR / 128
 //      passes); every key of the sequence is already in LDS, so no K / V staging or barrier
 //      between key tiles.
+// Head dim 64 only.  A 32-wide form (two adjacent heads per 64-column slot, the attention phase run once per
+// sub-head) was built and measured slower than the QKV GEMM + attention.hip's 32-wide kernels, so 32-wide
+// heads take that pair and qkv_attention_eligible refuses them.
 // Replaces the QKV GEMM launch, the Q / K / V round trip through HBM (B S 3 D fp16 written and
 // read back) and the attention launch's own staging.  Same arithmetic as the unfused pair
 // (fp16 Q / K / V, fp32 scores and softmax, fp16 P), DESIGN.md 3.7.

@@ -53,7 +53,8 @@ void gemm256(const GemmDesc& d, const GemmPtrs& p, int splits, hipStream_t s, in
 // Fused QKV projection + attention for S <= 128 (qkv_attn.hip): one workgroup per (sequence,
 // head) runs the head's q | k | v GEMM (A rows lda apart, packed W rows ldw apart; with
 // ln_stats: the LayerNorm consumer fold, ln_fold.hpp) and the attention on the LDS-resident
-// result, writing ctx [B S][heads 64] fp16.
+// result, writing ctx [B S][heads 64] fp16.  64-wide heads only: qkv_attention_eligible refuses any
+// other hd and the caller runs the QKV GEMM + attention().
 bool qkv_attention_eligible(int S, int heads, int hd, int K, int kpad, int krep, int lda, int ldw);
 void qkv_attention(const void* A, int lda, const void* W, int ldw, const float* bias, const float* ln_stats,
                    const float* c1, int ln_chunks, float ln_eps, const float* mask_bias, void* ctx, int B, int S,
@@ -195,7 +196,8 @@ void affine(const float* x, float* y, size_t n, float scale, float shift,
             hipStream_t s);
 
 // Multi-head attention over a packed qkv buffer [B*S, 3*D] (compute type):
-// ctx[b*S+i, h*hd:(h+1)*hd] = softmax(q k^T * scale + mask_bias[b]) v.
+// ctx[b*S+i, h*hd:(h+1)*hd] = softmax(q k^T * scale + mask_bias[b]) v.  hd 32 or 64; any other
+// width throws std::invalid_argument.
 // mask_bias: fp32 [B, S] additive bias or nullptr.
 void attention(const void* qkv, const float* mask_bias, void* ctx, int B, int S,
                int heads, int hd, float scale, bool f16, hipStream_t s);

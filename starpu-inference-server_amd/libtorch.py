@@ -121,6 +121,9 @@ class TorchScriptModule:
     def replica(self, device_id: int = 0, precision: str = "fp16", max_batch: int = 8, family: str | None = None,
                 num_heads: int = 0, seq_len: int = 0, image_size: int = 0, eps: float = 0.0,
                 graphs: bool = False, bert_io=0, image_io=0, top_k: int = 0) -> ModelReplica:
+        """A replica of the loaded module.  A TorchScript file states no attention head count and the QKV
+        weights do not tell it, so num_heads 0 means hidden / 64: a model with 32-wide heads (MiniLM: 384 over
+        12) needs its num_heads here."""
         cfg = N.ModelConfig()
         cfg.family = _FAMILIES[family]
         cfg.precision = PRECISIONS[precision]

@@ -204,14 +204,14 @@ def conv2d_grouped(x_nhwc, W_packed, groups, stride, bias=None, act=None, out=No
     return out
 
 
-def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None, out=None):
-    """ctx [B S][64 heads] of packed qkv [B S][3 D]; out: the buffer to write (default: a fresh one).  prec may
-    be the integer precision code itself."""
-    D = heads * 64
+def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None, out=None, head_dim=64):
+    """ctx [B S][D] of packed qkv [B S][3 D], D = heads * head_dim (32 or 64); out: the buffer to write
+    (default: a fresh one).  prec may be the integer precision code itself."""
+    D = heads * head_dim
     ctx = torch.empty(B * S, D, device=qkv.device, dtype=qkv.dtype) if out is None else out
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
-    _check(lib.spi_op_attention(PREC.get(prec, prec), _ptr(qkv), _ptr(mask_bias), _ptr(ctx), B, S, heads, scale,
-                                C.c_void_p(s)))
+    _check(lib.spi_op_attention_hd(PREC.get(prec, prec), _ptr(qkv), _ptr(mask_bias), _ptr(ctx), B, S, heads, head_dim,
+                                   scale, C.c_void_p(s)))
     return ctx
 
 

@@ -385,6 +385,16 @@ def bert_base(seed: int = 0, **kw) -> BertWrapper:
     return bert(seed=seed, **kw)
 
 
+def minilm_l6(seed: int = 0, **kw) -> BertWrapper:
+    """all-MiniLM-L6-H384's graph: 6 layers, hidden 384 over 12 heads of 32, FFN 1536."""
+    return bert(**{**dict(layers=6, hidden=384, heads=12, intermediate=1536), **kw}, seed=seed)
+
+
+def minilm_l12(seed: int = 0, **kw) -> BertWrapper:
+    """all-MiniLM-L12-H384's graph: minilm_l6 with 12 layers."""
+    return bert(**{**dict(layers=12, hidden=384, heads=12, intermediate=1536), **kw}, seed=seed)
+
+
 class AddConstant(nn.Module):
     """The reference's toy TorchScript models (tests/e2e/fixtures/simple_model.ts: x + 1)."""
 
@@ -408,6 +418,8 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
         "vit_l_16": vit_l_16,
         "bert-base-uncased": bert_base,
         "bert_base": bert_base,
+        "minilm_l6": minilm_l6,
+        "minilm_l12": minilm_l12,
     }
     if name not in table:
         raise KeyError(f"unknown model {name!r}; known: {sorted(table)}")
