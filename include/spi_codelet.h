@@ -321,7 +321,35 @@ typedef struct spi_model_config {
  * spi_model_create also refuses: two head bits; a head bit on another family; a missing or ambiguous
  * head parameter (named); a weight that is not [L,D] or a bias that is not [L]; L outside the head's
  * range (QA: L != 2); SPI_BERT_HEAD_SEQUENCE without pooler.dense.weight / .bias.
+ *
+ * The two-layer sequence head.  With SPI_BERT_HEAD_SEQUENCE, a parameter list that holds a tensor named
+ * `classifier.out_proj.weight` (or ending in `.classifier.out_proj.weight`) is HF's
+ * RobertaClassificationHead: logits [B,L] = W_o . tanh(W_d . last_hidden_state[:, 0] + b_d) + b_o with
+ * classifier.dense.weight [D,D] / .bias [D] and classifier.out_proj.weight [L,D] / .bias [L], 1 <= L <=
+ * 1024.  The names decide, not SPI_BERT_POS_FROM_IDS.  The pooler's and the sequence head's launches
+ * compute it (dense is packed where pooler.dense goes), so the logits have the bits of a replica whose
+ * tensors are named pooler.dense.* and classifier.*.  Refused, naming the tensors: together with
+ * SPI_BERT_OUT_POOLER (that model has no pooler); a missing classifier.dense.*; wrong shapes.
+ *
+ * SPI_BERT_POS_FROM_IDS: RoBERTa's position rule (roberta, xlm-roberta, camembert checkpoints; HF's
+ * create_position_ids_from_input_ids).  Embedding row (b, s) is
+ *   n(b,s) = #{ j <= s : ids[b][j] != SPI_ROBERTA_PAD_ID }       (raw int64 ids, before any clamp)
+ *   p(b,s) = ids[b][s] != SPI_ROBERTA_PAD_ID ? 1 + n(b,s) : 1
+ *   row    = LN( (word[clamp(ids[b][s])] + type_row) + pos[p(b,s)] ) * gamma + beta
+ * -- the fp32 sum, in the order, of a replica without the bit; only the position row differs.  A pad
+ * token reads position row 1, whatever it holds.  The position depends on input_ids only, never on
+ * attention_mask; segment ids (SPI_BERT_TOKEN_TYPES) combine with it unchanged.  The pad id is fixed at
+ * SPI_ROBERTA_PAD_ID = 1, the value of every published RoBERTa / XLM-R / CamemBERT-family checkpoint;
+ * a model with another pad id is out of scope and must not be served with this bit.
+ * The replica's longest sequence is then position rows - 2 (512 for a 514-row table): seq_len = 0
+ * resolves to it, spi_model_create refuses a larger seq_len (the message names the rows and the rule),
+ * and a longer task is refused like any over-long task.  The bit changes no packed byte, FLOP count or
+ * workspace size; spi_model_describe appends " pos[ids]".  Without the bit nothing changes.
+ * Independence: a row's embedding depends on its own sequence's ids alone -- the count is an exact
+ * integer taken by the row's own wave -- not on B, the row's place in the batch or graphs being on; two
+ * runs give the same bits.
  * Bits 16, 32 and 64 stay unknown. */
+#define SPI_ROBERTA_PAD_ID 1
 enum spi_bert_io {
   SPI_BERT_OUT_POOLER = 1,
   SPI_BERT_OUT_MEAN = 2,
@@ -329,7 +357,8 @@ enum spi_bert_io {
   SPI_BERT_TOKEN_TYPES = 8,
   SPI_BERT_HEAD_SEQUENCE = 128,
   SPI_BERT_HEAD_TOKEN = 256,
-  SPI_BERT_HEAD_QA = 512
+  SPI_BERT_HEAD_QA = 512,
+  SPI_BERT_POS_FROM_IDS = 1024
 };
 
 spi_model* spi_model_create(int32_t device_id, const spi_model_config* config,

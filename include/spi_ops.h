@@ -308,6 +308,16 @@ int spi_op_bert_embed_types(int32_t precision, const int64_t* ids, const float* 
                             int32_t D, int32_t vocab, int32_t npos, float eps, const int64_t* mask,
                             float* mask_bias, void* stream);
 
+/* spi_op_bert_embed_types with RoBERTa's position rule (SPI_BERT_POS_FROM_IDS, spi_codelet.h): row (b, s)
+ * reads pos[1 + #{j <= s : ids[b][j] != 1}], or pos[1] where ids[b][s] == 1 (SPI_ROBERTA_PAD_ID), instead
+ * of pos[s].  The count is over the raw ids and exact.  The same checks, and S + 2 <= npos.  On pad-free
+ * ids the outputs have the bits of spi_op_bert_embed_types given pos + 2 D. */
+int spi_op_bert_embed_posids(int32_t precision, const int64_t* ids, const float* word, const float* pos,
+                             const float* type_table, int32_t type_vocab, const int64_t* type_ids,
+                             const float* gamma, const float* beta, float* yf, void* yt, int32_t B, int32_t S,
+                             int32_t D, int32_t vocab, int32_t npos, float eps, const int64_t* mask,
+                             float* mask_bias, void* stream);
+
 /* ---- BERT sentence outputs (bert_pool.hip); fp32 throughout, deterministic (no atomics) ---- */
 
 /* BERT pooler: y[b][n] = tanh(bias[n] + sum_k h[b ld + k] W[n][k]), b < B, n < D.  h: fp32 rows of D, ld

@@ -161,6 +161,8 @@ class ModelConfig(C.Structure):
 # enum spi_bert_io (spi_model_config.bert_io)
 BERT_OUT_POOLER, BERT_OUT_MEAN, BERT_NO_HIDDEN, BERT_TOKEN_TYPES = 1, 2, 4, 8
 BERT_HEAD_SEQUENCE, BERT_HEAD_TOKEN, BERT_HEAD_QA = 128, 256, 512  # 16, 32 and 64 stay unknown bits
+BERT_POS_FROM_IDS = 1024  # RoBERTa's position rule
+ROBERTA_PAD_ID = 1  # SPI_ROBERTA_PAD_ID
 # enum spi_image_io (spi_model_set_image_outputs)
 IMAGE_OUT_PROBS, IMAGE_OUT_TOPK, IMAGE_NO_LOGITS, IMAGE_TOPK_PROBS = 1, 2, 4, 8
 
@@ -310,6 +312,10 @@ _PROTOS = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "spi_op_bert_embed_posids": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "spi_op_bert_pooler": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_void_p]),
     "spi_op_bert_token_head": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,

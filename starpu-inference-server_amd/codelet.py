@@ -130,12 +130,14 @@ _FAMILIES = {None: N.FAMILY_AUTO, "auto": N.FAMILY_AUTO, "resnet": N.FAMILY_RESN
              "vit": N.FAMILY_VIT, "affine": N.FAMILY_AFFINE}
 BERT_IO = {"pooler": N.BERT_OUT_POOLER, "mean": N.BERT_OUT_MEAN, "no_hidden": N.BERT_NO_HIDDEN,
            "token_types": N.BERT_TOKEN_TYPES, "seq_head": N.BERT_HEAD_SEQUENCE, "token_head": N.BERT_HEAD_TOKEN,
-           "qa_head": N.BERT_HEAD_QA}
+           "qa_head": N.BERT_HEAD_QA, "roberta_positions": N.BERT_POS_FROM_IDS}
+ROBERTA_MODEL_TYPES = ("roberta", "xlm-roberta", "camembert")  # HF config.model_type values with RoBERTa's position rule
 
 
 def bert_io_bits(bert_io) -> int:
     """spi_model_config.bert_io from an int, one name or several: ("pooler", "mean", "no_hidden", "token_types",
-    and at most one task head of "seq_head", "token_head", "qa_head")."""
+    at most one task head of "seq_head", "token_head", "qa_head", and "roberta_positions" for RoBERTa's position
+    ids, which ModelReplica sets by itself for an HF RoBERTa-family module)."""
     if bert_io is None:
         return 0
     if isinstance(bert_io, int):
@@ -294,10 +296,41 @@ def module_num_heads(module: torch.nn.Module) -> int:
     return found.pop() if found else 0
 
 
+def module_roberta_positions(module: torch.nn.Module) -> bool:
+    """Whether the module is, or wraps, an HF model of the RoBERTa family (config.model_type in
+    ROBERTA_MODEL_TYPES), whose position ids are counted from the input ids (SPI_BERT_POS_FROM_IDS).  The
+    kernel's pad id is fixed at 1 (SPI_ROBERTA_PAD_ID): a config with another pad_token_id is refused."""
+    for m in module.modules():
+        cfg = getattr(m, "config", None)
+        if getattr(cfg, "model_type", None) in ROBERTA_MODEL_TYPES:
+            pad = getattr(cfg, "pad_token_id", None)
+            if pad != N.ROBERTA_PAD_ID:
+                raise InferenceExecutionException(
+                    f"{cfg.model_type} config states pad_token_id {pad!r}; position ids from the input ids are "
+                    f"served for pad_token_id {N.ROBERTA_PAD_ID} only")
+            return True
+    return False
+
+
+def module_layer_norm_eps(module: torch.nn.Module) -> float:
+    """The LayerNorm epsilon an HF config on the module, or on a model it wraps, states (config.layer_norm_eps:
+    1e-12 for BERT checkpoints, 1e-5 for RoBERTa's); 0.0 where nothing states one.  Two that disagree are an error."""
+    found = set()
+    for m in module.modules():
+        e = getattr(getattr(m, "config", None), "layer_norm_eps", None)
+        if isinstance(e, float) and e > 0:
+            found.add(e)
+    if len(found) > 1:
+        raise InferenceExecutionException(f"the module states several layer_norm_eps values: {sorted(found)}")
+    return found.pop() if found else 0.0
+
+
 class ModelReplica:
     """One device-resident weight replica (BN-folded, MFMA-packed) -- a `spi_model*`.  num_heads 0 takes
     the head count the module states (module_num_heads), else hidden / 64; a TorchScript file states
-    none, so a model with 32-wide heads loaded from a .pt needs num_heads."""
+    none, so a model with 32-wide heads loaded from a .pt needs num_heads.  Likewise eps 0 takes an HF
+    config's layer_norm_eps, and an HF RoBERTa-family module (module_roberta_positions) gets bert_io
+    "roberta_positions" by itself; a RoBERTa loaded from a .pt needs both stated."""
 
     def __init__(self, module: torch.nn.Module | str | None, device_id: int = 0, precision: str = "fp16",
                  max_batch: int = 8, family: str | None = None, num_heads: int = 0, seq_len: int = 0,
@@ -334,9 +367,11 @@ class ModelReplica:
         cfg.num_heads = num_heads or (module_num_heads(module) if module is not None else 0)
         cfg.seq_len = seq_len
         cfg.image_size = image_size
-        cfg.eps = eps
+        cfg.eps = eps or (module_layer_norm_eps(module) if module is not None else 0.0)
         cfg.affine_scale, cfg.affine_shift = affine
         cfg.bert_io = bert_io_bits(bert_io)
+        if module is not None and module_roberta_positions(module):
+            cfg.bert_io |= N.BERT_POS_FROM_IDS
         err = C.create_string_buffer(512)
         h = lib.spi_model_create(device_id, C.byref(cfg), arr, len(tensors), err, len(err))
         if not h:

@@ -1,6 +1,7 @@
 // The row-LayerNorm family (gfx950): LayerNorm of fp32 rows and of two-plane fp16 rows, the BERT
 // embedding gather + LayerNorm, and the attention-mask bias the embedding also writes.  One wave per
 // row, two-pass fp32 statistics in registers; HBM (latency) bound.
+#include "../../include/spi_codelet.h"
 #include "row_util.hpp"
 #include "spi_kernels.hpp"
 
@@ -202,7 +203,29 @@ __device__ __forceinline__ size_t type_row(const int64_t* types, int row, int ty
   return (size_t)(t < 0 ? 0 : (t >= type_vocab ? type_vocab - 1 : t));
 }
 
-template <typename T>
+// SPI_BERT_POS_FROM_IDS (RoBERTa): the position row of embedding row `row`, token s of its sequence, whose
+// raw id is `id`: 1 + the non-pad ids among ids[b][0..s], or SPI_ROBERTA_PAD_ID for a pad token.  The wave
+// reads its sequence's ids up to s, 64 a step, and counts each step's ballot: an exact integer that
+// depends on the sequence alone -- not on B or the grid -- with no LDS, atomics or shuffles.  The trip
+// count is wave-uniform (a wave owns one row), so every lane takes part in every ballot.
+__device__ __forceinline__ int pos_from_ids(const int64_t* ids, int row, int s, int64_t id, int lane) {
+  const int64_t* seq = ids + (row - s);
+  int n = 0;
+  // four steps' loads are issued together (one L2 round trip per 256 ids, not per 64): a lane past s
+  // re-reads ids[b][s], inside the sequence, and its vote is dropped
+  for (int c = 0; c <= s; c += 256) {
+    int64_t v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = seq[min(c + 64 * u + lane, s)];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      n += __popcll(__ballot(c + 64 * u + lane <= s && v[u] != SPI_ROBERTA_PAD_ID));
+  }
+  return id != SPI_ROBERTA_PAD_ID ? SPI_ROBERTA_PAD_ID + n : SPI_ROBERTA_PAD_ID;
+}
+
+// POSIDS: the position row is pos_from_ids' instead of s; false leaves the kernel's code what it was.
+template <typename T, bool POSIDS>
 __global__ __launch_bounds__(256) void bert_embed_kernel(
     const int64_t* ids, const float* word, const float* pos, const float* type0,
     const float* g, const float* b, float* yf, T* yt, int B, int S, int D, int vocab,
@@ -214,9 +237,10 @@ __global__ __launch_bounds__(256) void bert_embed_kernel(
   if (mask && lane == 0) mask_bias[row] = mask_bias_of(mask[row]);
   const int s = row % S;
   int64_t id = ids[row];
+  const int prow = POSIDS ? pos_from_ids(ids, row, s, id, lane) : s;
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
   const float* w = word + (size_t)id * D;
-  const float* p = pos + (size_t)s * D;
+  const float* p = pos + (size_t)prow * D;
   const float* t = type0 + type_row(types, row, type_vocab) * D;
   float v[VPL];
 #pragma unroll
@@ -230,7 +254,7 @@ __global__ __launch_bounds__(256) void bert_embed_kernel(
 
 // The same for D = NV * 256 in the vector form, with 16-byte gathers (round 6: BERT-base's
 // embedding ran 14.6 us in the loop trace, 1.7 % of C3).
-template <typename T, int NV>
+template <typename T, int NV, bool POSIDS>
 __global__ __launch_bounds__(256) void bert_embed_vec_kernel(const int64_t* ids, const float* __restrict__ word,
                                                              const float* __restrict__ pos,
                                                              const float* __restrict__ type0,
@@ -246,9 +270,10 @@ __global__ __launch_bounds__(256) void bert_embed_vec_kernel(const int64_t* ids,
   if (mask && lane == 0) mask_bias[row] = mask_bias_of(mask[row]);
   const int s = row % S;
   int64_t id = ids[row];
+  const int prow = POSIDS ? pos_from_ids(ids, row, s, id, lane) : s;
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
   const float4* w4 = reinterpret_cast<const float4*>(word + (size_t)id * D);
-  const float4* p4 = reinterpret_cast<const float4*>(pos + (size_t)s * D);
+  const float4* p4 = reinterpret_cast<const float4*>(pos + (size_t)prow * D);
   const float4* t4 = reinterpret_cast<const float4*>(type0 + type_row(types, row, type_vocab) * D);
   float4 v[NV], gg[NV], bb[NV];
 #pragma unroll
@@ -322,24 +347,31 @@ void layernorm_planes(const _Float16* xh, size_t plane, int ldx, const float* g,
 void bert_embed(const int64_t* ids, const float* word, const float* pos, const float* type0,
                 const float* g, const float* b, float* yf, void* yt, int B, int S, int D,
                 int vocab, float eps, bool f16, hipStream_t s, const int64_t* mask, float* mask_bias,
-                const int64_t* types, int type_vocab) {
+                const int64_t* types, int type_vocab, bool pos_from_ids) {
   // the scalar kernel stores every row through yf + row D, which is non-null past row 0 whatever yf
   // is (the vector one tests yf itself and would leave the fp32 rows unwritten)
   if (!yf) throw std::invalid_argument("bert_embed: the fp32 output yf is required");
   const dim3 grid((B * S + 3) / 4);
   const bool vec = (D == 768 || D == 1024) && aligned(word, 16) && aligned(pos, 16) && aligned(type0, 16) &&
                    aligned(g, 16) && aligned(b, 16) && aligned(yf, 16) && (!yt || aligned(yt, f16 ? 8 : 16));
-  with_type(f16, [&](auto t) {
+  auto launch = [&](auto t, auto posids) {
     using T = decltype(t);
+    constexpr bool P = decltype(posids)::value;
     if (vec)
       with_nv(D, [&](auto nv) {
         constexpr int NV = decltype(nv)::value;
-        SPI_LAUNCH((bert_embed_vec_kernel<T, NV>), grid, dim3(256), 0, s, ids, word, pos, type0, g, b, yf, (T*)yt, B, S,
-                   vocab, eps, mask, mask_bias, types, type_vocab);
+        SPI_LAUNCH((bert_embed_vec_kernel<T, NV, P>), grid, dim3(256), 0, s, ids, word, pos, type0, g, b, yf, (T*)yt, B,
+                   S, vocab, eps, mask, mask_bias, types, type_vocab);
       });
     else
-      SPI_LAUNCH((bert_embed_kernel<T>), grid, dim3(256), 0, s, ids, word, pos, type0, g, b, yf, (T*)yt, B, S, D,
+      SPI_LAUNCH((bert_embed_kernel<T, P>), grid, dim3(256), 0, s, ids, word, pos, type0, g, b, yf, (T*)yt, B, S, D,
                  vocab, eps, mask, mask_bias, types, type_vocab);
+  };
+  with_type(f16, [&](auto t) {
+    if (pos_from_ids)
+      launch(t, std::true_type{});
+    else
+      launch(t, std::false_type{});
   });
 }
 

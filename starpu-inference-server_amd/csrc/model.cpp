@@ -578,12 +578,14 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
       // SPI_BERT_TOKEN_TYPES: the whole type table and, when the task brings them, its segment ids
       const bool typed = (m_.bert_io & SPI_BERT_TOKEN_TYPES) != 0;
       const int64_t* types = typed ? static_cast<const int64_t*>(in[2]) : nullptr;
-      return prof_op(s, "bert_embed", 0, T * D * (4 * 3 + 4 + (f16 ? 2 : 0)) + (w.has_mask ? T * 12 : 0) + (types ? T * 8 : 0), [&] {
+      // SPI_BERT_POS_FROM_IDS: row (b, s) also reads its sequence's ids up to s, 8 (S + 1) / 2 bytes on average
+      const double ids_reread = m_.pos_from_ids ? T * 4 * (S + 1) : 0;
+      return prof_op(s, "bert_embed", 0, T * D * (4 * 3 + 4 + (f16 ? 2 : 0)) + (w.has_mask ? T * 12 : 0) + (types ? T * 8 : 0) + ids_reread, [&] {
         bert_embed(static_cast<const int64_t*>(in[0]), ptr<float>(m_.word), ptr<float>(m_.pos),
                    ptr<float>(typed ? m_.type_table : m_.type0), ptr<float>(m_.emb_ln.g), ptr<float>(m_.emb_ln.b),
                    static_cast<float*>(w.bufs[kBtHidden]), f16 ? w.bufs[kBtHidden16] : nullptr, B, S, D, m_.vocab,
                    m_.eps, f16, s, w.has_mask ? w.mask_ids : nullptr, w.has_mask ? w.mask_bias : nullptr, types,
-                   m_.type_vocab);
+                   m_.type_vocab, m_.pos_from_ids);
       });
     }
     case SPI_FAMILY_VIT:

@@ -278,7 +278,7 @@ struct Packer {
   }
   void build_resnet(const PMap& p);
   void build_bert(const PMap& p, const PMap& all);
-  void pack_bert_head(const PMap& all);
+  void pack_bert_head(const PMap& all, bool two_layer);
   void build_vit(const PMap& p);
 };
 
@@ -400,12 +400,19 @@ const spi_named_tensor* find_head_param(const PMap& all, const std::string& name
   return found;
 }
 
+// Whether the unstripped list holds a tensor find_head_param would find under `name`.
+bool has_head_param(const PMap& all, const std::string& name) {
+  return std::any_of(all.begin(), all.end(),
+                     [&](const auto& kv) { return kv.first == name || ends_with(kv.first, "." + name); });
+}
+
 // The task head's dense layer, appended as plain fp32 [L][D] and [L], each on its own 256-byte line.
-void Packer::pack_bert_head(const PMap& all) {
+// two_layer: the sequence head's last layer is classifier.out_proj (build_bert packed classifier.dense).
+void Packer::pack_bert_head(const PMap& all, bool two_layer) {
   const int io = m.bert_io, D = m.D;
   const bool qa = (io & SPI_BERT_HEAD_QA) != 0, seq = (io & SPI_BERT_HEAD_SEQUENCE) != 0;
   const char* bit = qa ? "SPI_BERT_HEAD_QA" : seq ? "SPI_BERT_HEAD_SEQUENCE" : "SPI_BERT_HEAD_TOKEN";
-  const std::string name = qa ? "qa_outputs" : "classifier";
+  const std::string name = qa ? "qa_outputs" : two_layer ? "classifier.out_proj" : "classifier";
   const spi_named_tensor* w = find_head_param(all, name + ".weight", bit);
   const spi_named_tensor* b = find_head_param(all, name + ".bias", bit);
   if (w->ndim != 2 || w->shape[1] != D || w->shape[0] < 1 || b->ndim != 1 || b->shape[0] != w->shape[0])
@@ -430,6 +437,16 @@ void Packer::build_bert(const PMap& p, const PMap& all) {
   const spi_named_tensor* pe = need(p, "embeddings.position_embeddings.weight");
   m.maxpos = (int)pe->shape[0];
   check_heads();
+  if (m.pos_from_ids) {
+    // position ids run 2 .. S + 1 (row 1 is the pad token's, row 0 unused), so the table serves rows - 2 tokens
+    const std::string rule = "position table has " + std::to_string(m.maxpos) +
+                             " rows and SPI_BERT_POS_FROM_IDS reads rows 1 .. S + 1, so S <= rows - 2";
+    if (m.maxpos < 3) throw std::runtime_error("bert_io: " + rule);
+    if (m.seq > m.maxpos - 2)
+      throw std::runtime_error("bert_io: seq_len " + std::to_string(m.seq) + " is too long: the " + rule + " = " +
+                               std::to_string(m.maxpos - 2));
+    if (m.seq <= 0) m.seq = m.maxpos - 2;
+  }
   if (m.seq <= 0) m.seq = m.maxpos;
   m.word = pack_vec(fdata(we), (int)numel(we));
   m.pos = pack_vec(fdata(pe), (int)numel(pe));
@@ -480,7 +497,21 @@ void Packer::build_bert(const PMap& p, const PMap& all) {
     if (te->ndim != 2 || te->shape[1] != D) throw std::runtime_error("bert: token_type_embeddings.weight must be [types][D]");
     m.type_table = pack_vec(fdata(te), (int)numel(te));
   }
-  if (m.bert_io & (SPI_BERT_OUT_POOLER | SPI_BERT_HEAD_SEQUENCE)) {  // the sequence head reads the pooled vector
+  // HF's RobertaClassificationHead: classifier.dense [D,D] + tanh on token 0, then classifier.out_proj [L,D].
+  // The names decide.  dense goes where the pooler's tensors go, so bert_pooler + bert_seq_head compute it.
+  const bool two_layer = (m.bert_io & SPI_BERT_HEAD_SEQUENCE) && has_head_param(all, "classifier.out_proj.weight");
+  if (two_layer) {
+    if (m.bert_io & SPI_BERT_OUT_POOLER)
+      throw std::runtime_error(
+          "bert_io: SPI_BERT_OUT_POOLER cannot be combined with the two-layer sequence head 'classifier.dense.weight' + "
+          "'classifier.out_proj.weight': that model has no pooler, and classifier.dense takes its place");
+    const spi_named_tensor* pw = find_head_param(all, "classifier.dense.weight", "SPI_BERT_HEAD_SEQUENCE");
+    const spi_named_tensor* pb = find_head_param(all, "classifier.dense.bias", "SPI_BERT_HEAD_SEQUENCE");
+    if (pw->ndim != 2 || pw->shape[0] != D || pw->shape[1] != D || numel(pb) != D)
+      throw std::runtime_error("bert: classifier.dense must be [D][D] with a [D] bias, D = " + std::to_string(D));
+    m.pool_w = pack_vec(fdata(pw), (int)numel(pw));
+    m.pool_b = pack_vec(fdata(pb), D);
+  } else if (m.bert_io & (SPI_BERT_OUT_POOLER | SPI_BERT_HEAD_SEQUENCE)) {  // the sequence head reads the pooled vector
     for (const char* nm : {"pooler.dense.weight", "pooler.dense.bias"})
       if (!has(p, nm))
         throw std::runtime_error(std::string("bert_io: SPI_BERT_OUT_POOLER needs parameter '") + nm +
@@ -492,7 +523,7 @@ void Packer::build_bert(const PMap& p, const PMap& all) {
     m.pool_w = pack_vec(fdata(pw), (int)numel(pw));
     m.pool_b = pack_vec(fdata(pb), D);
   }
-  if (m.bert_io & (SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA)) pack_bert_head(all);
+  if (m.bert_io & (SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA)) pack_bert_head(all, two_layer);
 }
 
 void Packer::build_vit(const PMap& p) {
@@ -575,14 +606,16 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
   }
   if (const int io = cfg.bert_io) {  // spi_codelet.h: enum spi_bert_io
     constexpr int heads = SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA;
-    constexpr int known = SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | SPI_BERT_NO_HIDDEN | SPI_BERT_TOKEN_TYPES | heads;
+    constexpr int known =
+        SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | SPI_BERT_NO_HIDDEN | SPI_BERT_TOKEN_TYPES | heads | SPI_BERT_POS_FROM_IDS;
     if (io & ~known) throw std::runtime_error("bert_io: unknown bits " + std::to_string(io & ~known));
     if (m.family != SPI_FAMILY_BERT) throw std::runtime_error("bert_io is set, but the model is not a BERT");
     if ((io & heads) & ((io & heads) - 1))
       throw std::runtime_error("bert_io: at most one of SPI_BERT_HEAD_SEQUENCE, SPI_BERT_HEAD_TOKEN, SPI_BERT_HEAD_QA");
     if ((io & SPI_BERT_NO_HIDDEN) && !(io & (SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | heads)))
       throw std::runtime_error("bert_io: SPI_BERT_NO_HIDDEN leaves no output; select SPI_BERT_OUT_POOLER or SPI_BERT_OUT_MEAN");
-    m.bert_io = io;
+    m.bert_io = io & ~SPI_BERT_POS_FROM_IDS;
+    m.pos_from_ids = (io & SPI_BERT_POS_FROM_IDS) != 0;
   }
   pk.blob.add(nullptr, 256);  // offset 0: zero line read by the GEMM for padded chunks
   std::ostringstream os;
@@ -629,6 +662,7 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     if (!head.empty()) outs += (outs.empty() ? "" : ",") + head;
     os << " out[" << outs << "] in[ids,mask" << ((m.bert_io & SPI_BERT_TOKEN_TYPES) ? ",types]" : "]");
   }
+  if (m.pos_from_ids) os << " pos[ids]";
   m.desc = os.str();
   m.blob = std::move(pk.blob.data);
   m.blob_bytes = m.blob.size();

@@ -85,9 +85,14 @@ struct PackedModel {
   // SPI_BERT_TOKEN_TYPES appends the whole fp32 [type_vocab][D] table, SPI_BERT_OUT_POOLER
   // pooler.dense as plain fp32 [D][D] plus its bias.
   int bert_io = 0, type_vocab = 1;
+  // SPI_BERT_POS_FROM_IDS (RoBERTa's position rule), kept out of bert_io: it selects the embedding kernel's
+  // form and bounds seq by maxpos - 2, and changes no packed byte, output or workspace size
+  bool pos_from_ids = false;
   size_t type_table = 0, pool_w = 0, pool_b = 0;
   // The task head (SPI_BERT_HEAD_*): classifier / qa_outputs as plain fp32 [num_labels][D] plus its bias,
   // appended after the above; SPI_BERT_HEAD_SEQUENCE also packs the pooler (once).  0 labels: no head.
+  // A sequence head named classifier.dense / classifier.out_proj (HF's RobertaClassificationHead) packs
+  // dense as pool_w / pool_b and out_proj as the head: the same two launches compute it.
   int num_labels = 0;
   size_t head_w = 0, head_b = 0;
   LnW emb_ln, final_ln;

@@ -694,6 +694,25 @@ int spi_op_bert_embed_types(int32_t precision, const int64_t* ids, const float* 
   });
 }
 
+int spi_op_bert_embed_posids(int32_t precision, const int64_t* ids, const float* word, const float* pos,
+                             const float* type_table, int32_t type_vocab, const int64_t* type_ids, const float* g,
+                             const float* b, float* yf, void* yt, int32_t B, int32_t S, int32_t D, int32_t vocab,
+                             int32_t npos, float eps, const int64_t* mask, float* mask_bias, void* stream) {
+  if ((precision != 0 && precision != 1) || !ids || !word || !pos || !type_table || !g || !b || B <= 0 || S <= 0 ||
+      D <= 0 || vocab <= 0 || npos <= 0 || type_vocab <= 0)
+    return fail("invalid bert_embed_posids arguments");
+  if (!yf) return fail("bert_embed_posids: the fp32 output yf is required");
+  if (D > 1024) return fail("bert_embed_posids: D <= 1024");
+  if ((int64_t)S + 2 > npos) return fail("bert_embed_posids: S + 2 exceeds the position table");
+  if ((mask == nullptr) != (mask_bias == nullptr))
+    return fail("bert_embed_posids: mask and mask_bias come both or neither");
+  return guarded([&] {
+    spi::bert_embed(ids, word, pos, type_table, g, b, yf, yt, B, S, D, vocab, eps, precision == 1,
+                    static_cast<hipStream_t>(stream), mask, mask_bias, type_ids, type_vocab, true);
+    return check_launch();
+  });
+}
+
 int spi_op_bert_pooler(const float* h, int64_t ld, const float* W, const float* bias, float* y, int32_t B, int32_t D,
                        void* stream) {
   if (!h || !W || !bias || !y || B <= 0 || D <= 0 || ld < D) return fail("invalid bert_pooler arguments");

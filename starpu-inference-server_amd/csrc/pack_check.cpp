@@ -2,11 +2,14 @@
 // tensors are synthesised here with the closed-form fill of tests/golden/make_replica_digests.py
 // and prints the digests, which equal that table's resnet_basic / bert_d128 / vit_d128 entries; then the
 // BERT once more with every spi_model_config.bert_io bit set, and once per task head (SPI_BERT_HEAD_*),
-// checking what the bits append to the blob.
+// checking what the bits append to the blob; then RoBERTa's position rule, which appends nothing, and the
+// two-layer sequence head.
 // Built with the address and undefined-behaviour sanitizers, no HIP.
 #include <cstdio>
+#include <cstring>
 #include <deque>
 #include <initializer_list>
+#include <stdexcept>
 
 #include "model_pack.hpp"
 
@@ -118,6 +121,50 @@ int main() {
                    m.blob_bytes, m.num_labels, m.desc.c_str());
       return 1;
     }
+  }
+  // SPI_BERT_POS_FROM_IDS: the plain blob, byte for byte, and the plain description plus a marker; seq_len 0
+  // resolves to the 32-row table's 30 tokens and 31 are refused.
+  cfg.bert_io = SPI_BERT_POS_FROM_IDS;
+  const spi::PackedModel rp = spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+  std::printf("bert_d128|fp16|pos_from_ids %016llx %zu %s\n", (unsigned long long)rp.digest, rp.blob_bytes, rp.desc.c_str());
+  cfg.seq_len = 0;
+  const int longest = spi::pack_model(cfg, bt.t.data(), (int)bt.t.size()).seq;
+  bool refused = false;
+  try {
+    cfg.seq_len = 31;
+    spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+  } catch (const std::runtime_error& e) {
+    refused = std::string(e.what()).find("32 rows") != std::string::npos;
+  }
+  if (rp.digest != plain.digest || rp.blob_bytes != plain.blob_bytes || rp.desc != plain.desc + " pos[ids]" ||
+      !rp.pos_from_ids || rp.bert_io != 0 || longest != 30 || !refused) {
+    std::fprintf(stderr, "pos_from_ids packing: %s, longest sequence %d, seq_len 31 %s\n", rp.desc.c_str(), longest,
+                 refused ? "refused" : "not refused as expected");
+    return 1;
+  }
+  // The two-layer sequence head (HF's RobertaClassificationHead): its names select it, dense [128][128] goes where
+  // the pooler's tensors go and out_proj [3][128] is the head; with the pooler output it is refused.
+  bt.linear("classifier.dense", 128, 128), bt.linear("classifier.out_proj", 3, 128);
+  cfg.seq_len = 16, cfg.bert_io = SPI_BERT_POS_FROM_IDS | SPI_BERT_HEAD_SEQUENCE;
+  const spi::PackedModel two = spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+  std::printf("bert_d128|fp16|pos_from_ids|seq_head2 %016llx %zu %s\n", (unsigned long long)two.digest, two.blob_bytes,
+              two.desc.c_str());
+  const float* dense = bt.data[bt.data.size() - 4].data();  // classifier.dense.weight as synthesised
+  const size_t grow2 = (128 * 128 + 128 + 3 * 128 + 3) * sizeof(float);
+  bool refused2 = false;
+  try {
+    cfg.bert_io |= SPI_BERT_OUT_POOLER;
+    spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+  } catch (const std::runtime_error& e) {
+    refused2 = std::string(e.what()).find("classifier.out_proj.weight") != std::string::npos;
+  }
+  if (two.num_labels != 3 || two.blob_bytes < plain.blob_bytes + grow2 || two.blob_bytes > plain.blob_bytes + grow2 + 4 * 256 ||
+      two.pool_w < plain.blob_bytes || two.head_w <= two.pool_b || two.head_b + 3 * sizeof(float) != two.blob_bytes ||
+      std::memcmp(two.blob.data() + two.pool_w, dense, 128 * 128 * sizeof(float)) != 0 || !refused2 ||
+      two.desc != plain.desc + " out[hidden,seq_logits3] in[ids,mask] pos[ids]") {
+    std::fprintf(stderr, "two-layer sequence head packing: unexpected blob %zu -> %zu, %d labels, %s\n", plain.blob_bytes,
+                 two.blob_bytes, two.num_labels, two.desc.c_str());
+    return 1;
   }
   return 0;
 }

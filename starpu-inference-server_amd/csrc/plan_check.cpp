@@ -155,13 +155,20 @@ int main() {
   // pooler, mean, start, end) -- the pooled vector's place in the workspace, and the walk at max_batch.
   bt.linear("bert.pooler.dense", 128, 128), bt.linear("classifier", 5, 128), bt.linear("qa_outputs", 2, 128);
   const int64_t B = 2, S = 16, D = 128, Lh = 5;
-  const struct { const char* name; int io; std::vector<size_t> out; size_t cls; } heads[] = {
+  // Then RoBERTa's position rule (SPI_BERT_POS_FROM_IDS: the plan of the plain replica, sequences up to position
+  // rows - 2) and the two-layer sequence head (classifier.dense + classifier.out_proj, 3 labels, added to the
+  // tensors when its case comes: from then on the names select it).
+  const struct { const char* name; int io; std::vector<size_t> out; size_t cls; bool two_layer; } heads[] = {
       {"seq_head", SPI_BERT_HEAD_SEQUENCE, {(size_t)(B * S * D), (size_t)(B * Lh)}, 8 * 128 * 4},
       {"no_hidden|seq_head", SPI_BERT_NO_HIDDEN | SPI_BERT_HEAD_SEQUENCE, {(size_t)(B * Lh)}, 2 * 8 * 128 * 4},
       {"no_hidden|token_head", SPI_BERT_NO_HIDDEN | SPI_BERT_HEAD_TOKEN, {(size_t)(B * S * Lh)}, 8 * 128 * 4},
       {"pooler|mean|qa_head", SPI_BERT_OUT_POOLER | SPI_BERT_OUT_MEAN | SPI_BERT_HEAD_QA,
-       {(size_t)(B * S * D), (size_t)(B * D), (size_t)(B * D), (size_t)(B * S), (size_t)(B * S)}, 0}};
+       {(size_t)(B * S * D), (size_t)(B * D), (size_t)(B * D), (size_t)(B * S), (size_t)(B * S)}, 0},
+      {"pos_from_ids", SPI_BERT_POS_FROM_IDS, {(size_t)(B * S * D)}, 0},
+      {"pos_from_ids|no_hidden|seq_head2", SPI_BERT_POS_FROM_IDS | SPI_BERT_NO_HIDDEN | SPI_BERT_HEAD_SEQUENCE,
+       {(size_t)(B * 3)}, 2 * 8 * 128 * 4, true}};
   for (const auto& h : heads) {
+    if (h.two_layer) bt.linear("classifier.dense", 128, 128), bt.linear("classifier.out_proj", 3, 128);
     spi_model_config cfg{};
     cfg.family = SPI_FAMILY_AUTO, cfg.precision = SPI_PREC_F16, cfg.max_batch = 8, cfg.num_heads = 2, cfg.seq_len = 16;
     cfg.bert_io = h.io;
@@ -193,6 +200,17 @@ int main() {
     } catch (const std::runtime_error& e) {
       std::fprintf(stderr, "bert_d128|fp16|%s: %s\n", h.name, e.what());
       ok = false;
+    }
+    if (h.io & SPI_BERT_POS_FROM_IDS) {  // seq_len 0: the 32-row table serves 30 tokens, and 31 are refused
+      cfg.seq_len = 0;
+      const spi::PackedModel longest = spi::pack_model(cfg, bt.t.data(), (int)bt.t.size());
+      ok = ok && longest.seq == 30 && m.pos_from_ids && spi::plan_check(longest, o, 1, 30) > 0;
+      try {
+        spi::plan_check(longest, o, 1, 31);
+        ok = false;
+      } catch (const std::runtime_error&) {
+      }
+      ok = ok && (!h.two_layer || m.num_labels == 3);
     }
     if (!ok || plan.bytes.size() != (size_t)spi::kBtBufs || plan.bytes[spi::kBtCls] != h.cls) {
       std::fprintf(stderr, "bert_d128|fp16|%s: outputs, check_io or the workspace plan are not the expected ones\n", h.name);

@@ -137,12 +137,13 @@ void layernorm(const float* x, int ldx, const float* g, const float* b,
 // token's additive attention bias too (mask_to_bias's, one launch fewer per forward).  yf is
 // required (throws on null); yt may be null.  With types (int64 [B,S] segment ids), type0 is the
 // whole [type_vocab][D] table and row (b, s) adds its row clamp(types[b][s], 0, type_vocab - 1);
-// null types add row 0, the same sums in the same order.
+// null types add row 0, the same sums in the same order.  pos_from_ids (SPI_BERT_POS_FROM_IDS): the position
+// row is 1 + the non-pad ids of ids[b][0..s], or 1 for a pad id, instead of s; the table needs S + 2 rows.
 void bert_embed(const int64_t* ids, const float* word, const float* pos,
                 const float* type0, const float* g, const float* b, float* yf,
                 void* yt, int B, int S, int D, int vocab, float eps, bool f16,
                 hipStream_t s, const int64_t* mask = nullptr, float* mask_bias = nullptr,
-                const int64_t* types = nullptr, int type_vocab = 1);
+                const int64_t* types = nullptr, int type_vocab = 1, bool pos_from_ids = false);
 // BERT sentence outputs (bert_pool.hip): fp32, fixed summation order, D % 64 == 0 and D <= 1024.
 // Pooler: y[b][n] = tanh(bias[n] + sum_k h[b ld + k] W[n][k]); W fp32 [D][D], y [B][D].
 void bert_pooler(const float* h, size_t ld, const float* W, const float* bias, float* y, int B, int D,

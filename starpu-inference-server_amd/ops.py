@@ -490,6 +490,17 @@ def bert_embed_types(prec, ids, word, pos, type_table, type_ids, gamma, beta, yf
     return yf, yt
 
 
+def bert_embed_posids(prec, ids, word, pos, type_table, type_ids, gamma, beta, yf, yt, B, S, D, eps, mask=None,
+                      mask_bias=None, stream=None):
+    """bert_embed_types with RoBERTa's position rule: row (b, s) reads pos[1 + #non-pad ids up to s], or pos[1]
+    at a pad id (1), so pos needs S + 2 rows."""
+    _check(lib.spi_op_bert_embed_posids(PREC[prec], _ptr(ids), _ptr(word), _ptr(pos), _ptr(type_table),
+                                        type_table.shape[0], _ptr(type_ids), _ptr(gamma), _ptr(beta), _ptr(yf),
+                                        _ptr(yt), B, S, D, word.shape[0], pos.shape[0], eps, _ptr(mask),
+                                        _ptr(mask_bias), _stream(stream)))
+    return yf, yt
+
+
 def bert_pooler(h, ld, W, bias, out, B, D, stream=None):
     """out fp32 [B][D] = tanh(bias + h_rows W^T): row b of h starts ld floats after row b - 1 (fp32 throughout)."""
     _check(lib.spi_op_bert_pooler(_ptr(h), ld, _ptr(W), _ptr(bias), _ptr(out), B, D, _stream(stream)))

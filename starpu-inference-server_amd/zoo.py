@@ -307,31 +307,35 @@ class BertHeadWrapper(nn.Module):
     BertForQuestionAnswering, eval) returning HF's tuple as a replica with a task head serves it:
     last_hidden_state and pooler_output first, where `outputs` names them ("hidden", "pooler"), then the
     logits -- [B,L] ("sequence"), [B,S,L] ("token"), or start and end logits [B,S] each ("qa").  The
-    parameters are model.bert.* beside model.classifier.* / model.qa_outputs.*, as HF names them."""
+    parameters are model.bert.* beside model.classifier.* / model.qa_outputs.*, as HF names them.
+    A RoBERTa head model (model.roberta.*) is wrapped the same way; its sequence head has no pooler and is
+    the two-layer model.classifier(last_hidden_state) (classifier.dense + tanh, classifier.out_proj)."""
 
     def __init__(self, model: nn.Module, head: str, outputs=("hidden",)):
         super().__init__()
         if head not in ("sequence", "token", "qa"):
             raise ValueError(f"unknown BERT head {head!r}; known: 'sequence', 'token', 'qa'")
-        if "pooler" in outputs and head != "sequence":
-            raise ValueError("HF's token and QA head models have no pooler (add_pooling_layer=False)")
+        if "pooler" in outputs and (head != "sequence" or not hasattr(model, "bert")):
+            raise ValueError("HF's token and QA head models, and RoBERTa's, have no pooler (add_pooling_layer=False)")
         self.model = model
         self.head = head
         self.outputs = tuple(outputs)
 
     @property
     def bert(self) -> nn.Module:
-        return self.model.bert
+        return self.model.bert if hasattr(self.model, "bert") else self.model.roberta
 
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor):
-        out = self.model.bert(input_ids=input_ids, attention_mask=attention_mask, return_dict=False)
+        out = self.bert(input_ids=input_ids, attention_mask=attention_mask, return_dict=False)
         hidden = out[0]
         res = []
         if "hidden" in self.outputs:
             res.append(hidden)
         if "pooler" in self.outputs:
             res.append(out[1])
-        if self.head == "sequence":
+        if self.head == "sequence" and not hasattr(self.model, "bert"):
+            res.append(self.model.classifier(hidden))
+        elif self.head == "sequence":
             res.append(self.model.classifier(self.model.dropout(out[1])))
         elif self.head == "token":
             res.append(self.model.classifier(self.model.dropout(hidden)))
@@ -395,6 +399,67 @@ def minilm_l12(seed: int = 0, **kw) -> BertWrapper:
     return bert(**{**dict(layers=12, hidden=384, heads=12, intermediate=1536), **kw}, seed=seed)
 
 
+def roberta(layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072,
+            vocab: int = 50265, max_position: int = 514, seed: int = 0, init_std: float = 0.02,
+            head: str | None = None, num_labels: int = 2, outputs=("hidden",)) -> nn.Module:
+    """HF RobertaModel in BertWrapper (type_vocab_size 1, pad_token_id 1, layer_norm_eps 1e-5: the published
+    checkpoints' values); with head = "sequence" | "token" | "qa" the HF head model in BertHeadWrapper.  A
+    replica serves it with bert_io "roberta_positions", which ModelReplica sets by itself from the config.
+    max_position counts the table's rows: the longest sequence is max_position - 2.  Position row 1, the
+    pad token's, is drawn like the others (HF zeroes it), so a kernel that skipped it would show."""
+    import logging
+
+    from transformers import (RobertaConfig, RobertaForQuestionAnswering, RobertaForSequenceClassification,
+                              RobertaForTokenClassification, RobertaModel)
+    from transformers.utils import logging as hf_logging
+
+    hf_logging.set_verbosity_error()
+    logging.getLogger("transformers").setLevel(logging.ERROR)
+    torch.manual_seed(seed)
+    cfg = RobertaConfig(num_hidden_layers=layers, hidden_size=hidden, num_attention_heads=heads,
+                        intermediate_size=intermediate, vocab_size=vocab, max_position_embeddings=max_position,
+                        type_vocab_size=1, pad_token_id=1, bos_token_id=0, eos_token_id=2, layer_norm_eps=1e-5,
+                        initializer_range=init_std, torchscript=True)
+    if head is None:
+        model = BertWrapper(RobertaModel(cfg))
+    else:
+        cfg.num_labels = 2 if head == "qa" else num_labels
+        hf = {"sequence": RobertaForSequenceClassification, "token": RobertaForTokenClassification,
+              "qa": RobertaForQuestionAnswering}
+        if head not in hf:
+            raise ValueError(f"unknown BERT head {head!r}; known: {sorted(hf)}")
+        model = BertHeadWrapper(hf[head](cfg), head, outputs)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, nn.LayerNorm):
+                m.weight.copy_(1.0 + 0.1 * torch.randn_like(m.weight))
+                m.bias.copy_(0.05 * torch.randn_like(m.bias))
+        pos = model.bert.embeddings.position_embeddings.weight
+        pos[1].copy_(init_std * torch.randn_like(pos[1]))
+        if head is not None:  # bert()'s re-draw, for the same reason; the two-layer head's first layer too
+            inner = model.model
+            dense = [inner.qa_outputs] if head == "qa" else \
+                [inner.classifier.dense, inner.classifier.out_proj] if head == "sequence" else [inner.classifier]
+            for d in dense:
+                d.weight.copy_(torch.randn_like(d.weight) / hidden ** 0.5)
+                d.bias.copy_(0.1 * torch.randn_like(d.bias))
+    return model.eval()
+
+
+def roberta_base(seed: int = 0, **kw) -> nn.Module:
+    return roberta(seed=seed, **kw)
+
+
+def xlm_roberta_base(seed: int = 0, **kw) -> nn.Module:
+    """xlm-roberta-base's graph: roberta_base over a 250002-row vocabulary (pass vocab= for a smaller table)."""
+    return roberta(**{**dict(vocab=250002), **kw}, seed=seed)
+
+
+def xlm_roberta_large(seed: int = 0, **kw) -> nn.Module:
+    """xlm-roberta-large's graph: 24 layers, hidden 1024 over 16 heads, FFN 4096, vocabulary 250002."""
+    return roberta(**{**dict(layers=24, hidden=1024, heads=16, intermediate=4096, vocab=250002), **kw}, seed=seed)
+
+
 class AddConstant(nn.Module):
     """The reference's toy TorchScript models (tests/e2e/fixtures/simple_model.ts: x + 1)."""
 
@@ -420,6 +485,9 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
         "bert_base": bert_base,
         "minilm_l6": minilm_l6,
         "minilm_l12": minilm_l12,
+        "roberta_base": roberta_base,
+        "xlm_roberta_base": xlm_roberta_base,
+        "xlm_roberta_large": xlm_roberta_large,
     }
     if name not in table:
         raise KeyError(f"unknown model {name!r}; known: {sorted(table)}")
