@@ -124,6 +124,10 @@ struct TileGeo {
   static constexpr int WTM = BM / (NW / 2), WTN = BN / 2;  // rows, columns per wave
   static constexpr int TI = WTM / 16, TJ = WTN / 16;
   static_assert(BM * BN * 4 <= LDSB - 16, "the epilogue's fp32 C tile must fit the LDS");
+  // a pooled problem (GemmDesc::pool_rows) may run on any dense tile SPI_GEMM_PLAN can force: each must
+  // hold the pooled epilogue's 256 partial sums behind the C tile, or its [B pool_rows][N] rows would take
+  // the ordinary store path into a [B][N] buffer
+  static_assert(KIND != kDense || BM * BN * 4 + 256 * 4 <= LDSB - 16, "every dense tile compiles the pooled epilogue");
   // the residual tile prefetch (gemm_epilogue.hpp): 64 x 64 tiles on the vector epilogue path
   static constexpr bool RPF = BM == 64 && BN == 64 && !HALO && NW == 4;
   // the LayerNorm fold lives in the dense fp16 instances only (the transformer GEMMs)

@@ -316,7 +316,8 @@ int spi_op_avgpool_fc(int32_t precision, const void* x, int32_t B, int32_t HW, i
   d.out_f32 = true;
   d.pool_rows = HW;
   d.a_split = precision == kSplitPrecision;
-  return run_gemm(d, p, x, W, bias, nullptr, y, {}, workspace, stream, nullptr);
+  // the plan rule never splits a pooled GEMM, a forced SPI_GEMM_PLAN may: its slabs must fit like any other's
+  return run_gemm(d, p, x, W, bias, nullptr, y, {}, workspace, stream, "avgpool_fc too large for the op workspace");
 }
 
 size_t spi_op_stem_pool_bytes(void) { return spi::stem_pool_bytes(); }

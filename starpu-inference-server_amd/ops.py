@@ -225,10 +225,12 @@ def layernorm(prec, x, gamma, beta, eps, stream=None):
     return yf, yt
 
 
-def avgpool_fc(prec, x, W_packed, N_, bias=None, act=None, ws=None, stream=None):
-    """Fused global average pool + linear layer: x [B][HW][C] -> fp32 [B][N] (one launch)."""
+def avgpool_fc(prec, x, W_packed, N_, bias=None, act=None, ws=None, stream=None, out=None):
+    """Fused global average pool + linear layer: x [B][HW][C] -> fp32 [B][N] (one launch); out: the contiguous
+    buffer to write (default: a fresh one)."""
     B, HW, Cc = x.shape
-    out = torch.empty(B, N_, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(B, N_, device=x.device, dtype=torch.float32)
     ws = workspace(x.device) if ws is None else ws
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     _check(lib.spi_op_avgpool_fc(PREC[prec], _ptr(x), B, HW, Cc, _ptr(W_packed), N_, _ptr(bias), _ptr(out), ACT[act],
@@ -241,10 +243,11 @@ def avgpool_fc(prec, x, W_packed, N_, bias=None, act=None, ws=None, stream=None)
 STEM_PREC = {"fp16": 1, "fp16m": 2, "fp16x3s": 3, "fp16x3": 4}
 
 
-def stem_pool(prec, x_nchw, w_folded, bias, rows_per_block=0, stream=None):
+def stem_pool(prec, x_nchw, w_folded, bias, rows_per_block=0, stream=None, out=None):
     """Fused ResNet stem (7x7/s2 conv over 3 channels, 64 out, folded BN bias, ReLU, 3x3/s2 max pool)
     on the NCHW fp32 image, one launch.  Returns NHWC [B][PH][PW][64]: fp16, or for fp16x3s the split
-    layout in a float32-storage tensor."""
+    layout in a float32-storage tensor; out: the contiguous buffer of that shape and type to write
+    (default: a fresh one)."""
     B, _, H, W_ = x_nchw.shape
     oh, ow = (H - 1) // 2 + 1, (W_ - 1) // 2 + 1
     ph, pw = (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
@@ -253,18 +256,20 @@ def stem_pool(prec, x_nchw, w_folded, bias, rows_per_block=0, stream=None):
     host = np.empty(lib.spi_op_stem_pool_bytes(), dtype=np.uint8)
     _check(lib.spi_op_stem_pool_pack(w.ctypes.data, host.ctypes.data))
     wp = torch.from_numpy(host).to(x_nchw.device)
-    out = torch.empty(B, ph, pw, 64, device=x_nchw.device,
-                      dtype=torch.float32 if prec == "fp16x3s" else torch.float16)
+    if out is None:
+        out = torch.empty(B, ph, pw, 64, device=x_nchw.device,
+                          dtype=torch.float32 if prec == "fp16x3s" else torch.float16)
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     _check(lib.spi_op_stem_pool(STEM_PREC[prec], _ptr(x_nchw), B, H, W_, _ptr(wp), _ptr(bias), _ptr(out),
                                 rows_per_block, C.c_void_p(s)))
     return out
 
 
-def stem_pool_u8(prec, x_u8, w_folded, bias, scale=None, shift=None, nhwc=False, rows_per_block=0, stream=None):
+def stem_pool_u8(prec, x_u8, w_folded, bias, scale=None, shift=None, nhwc=False, rows_per_block=0, stream=None,
+                 out=None):
     """stem_pool on 8-bit pixels: x_u8 uint8 [B][3][H][W], or [B][H][W][3] with nhwc; a pixel p of
     channel c enters as float32(p) * scale[c] + shift[c] (default 1, 0).  x_u8 may start at any byte
-    address (a slice of a larger buffer), but must be contiguous."""
+    address (a slice of a larger buffer), but must be contiguous.  out as stem_pool's."""
     if x_u8.dtype != torch.uint8 or not x_u8.is_contiguous():
         raise OpError("stem_pool_u8: a contiguous uint8 tensor")
     if nhwc:
@@ -278,7 +283,8 @@ def stem_pool_u8(prec, x_u8, w_folded, bias, scale=None, shift=None, nhwc=False,
     host = np.empty(lib.spi_op_stem_pool_bytes(), dtype=np.uint8)
     _check(lib.spi_op_stem_pool_pack(w.ctypes.data, host.ctypes.data))
     wp = torch.from_numpy(host).to(x_u8.device)
-    out = torch.empty(B, ph, pw, 64, device=x_u8.device, dtype=torch.float32 if prec == "fp16x3s" else torch.float16)
+    if out is None:
+        out = torch.empty(B, ph, pw, 64, device=x_u8.device, dtype=torch.float32 if prec == "fp16x3s" else torch.float16)
     s = torch.cuda.current_stream().cuda_stream if stream is None else stream
     _check(lib.spi_op_stem_pool_u8(STEM_PREC[prec], _ptr(x_u8), int(nhwc), B, H, W_, _ptr(wp), _ptr(bias),
                                    N.float3(scale), N.float3(shift), _ptr(out), rows_per_block, C.c_void_p(s)))

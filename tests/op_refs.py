@@ -1,7 +1,7 @@
 """Plain float64 / bit-exact references of the ops behind include/spi_ops.h that the GPU op tests
 (test_qkv_attention_ops_gpu.py, test_attention_ops_gpu.py, test_elementwise_ops_gpu.py, test_conv_pair_ops_gpu.py,
-test_hilo_weight_ops_gpu.py, test_conv_kinds_ops_gpu.py, the hi + lo consumer of test_ln_fold_ops_gpu.py) compare the
-HIP kernels with,
+test_hilo_weight_ops_gpu.py, test_conv_kinds_ops_gpu.py, test_stem_ops_gpu.py, test_fc_ops_gpu.py, the hi + lo
+consumer of test_ln_fold_ops_gpu.py) compare the HIP kernels with,
 plus the inputs and case lists those tests share.  Nothing here touches a GPU; test_op_refs.py checks every reference
 against the torch op it restates, so the GPU bars rest on checked ground.
 """
@@ -734,3 +734,266 @@ def conv3_window_walk(xv, wv, shape, bm=64, col_mask=True, pitch=None):
                 acc += np.where((row_ok & col_ok)[:, None], win[rows + kw], 0.0) @ w[:, kh, kw].T
         out[m[valid]] = acc[valid]
     return out.reshape(B, H, W, cout)
+
+
+# ---------------------------------------------------------------------------------------------
+# the fused stem (stem.hip; test_stem_ops_gpu.py): 7x7/s2/p3 conv over 3 channels + bias + ReLU + 3x3/s2/p1 max
+# pool, NCHW image -> NHWC [B][PH][PW][64]
+#
+# A precision code is spi_op_stem_pool's: 1 fp16 image x fp16 weights, 2 fp16 image x hi + lo weights (fp16m),
+# 3 split image x hi + lo weights into the split layout, 4 the same arithmetic into fp16.
+
+STEM_CODES = {"fp16": 1, "fp16m": 2, "fp16x3s": 3, "fp16x3": 4}
+STEM_BAR = {1: 1e-3, 2: 1e-3, 3: 1e-5, 4: 1e-3}
+# (B, H, W, image kind).  OW = (W - 1) // 2 + 1 stem columns in groups of 64, PH / PW pooled rows / columns; a
+# workgroup takes PR pooled rows (rows_per_block 1 / 2: PR = 1 / 2 on 4 waves; 0: PR = 2 on 8 waves when
+# OW > 64, else PR = 1 on 4).  test_stem_ops_gpu's docstring says which shape reaches which edge.
+STEM_SHAPES = [
+    (1, 1, 1, "randn"), (3, 9, 7, "rand"), (1, 2, 8, "randn"), (1, 10, 47, "rand"), (3, 11, 127, "randn"),
+    (1, 13, 128, "rand"), (1, 2, 129, "randn"), (3, 9, 131, "randn"), (1, 23, 130, "rand"), (1, 11, 132, "randn"),
+    (1, 13, 190, "rand"), (1, 10, 221, "randn"), (3, 1, 223, "rand"), (1, 40, 222, "randn"), (1, 23, 224, "randn"),
+]
+STEM_REFUSED_W = (225, 226)
+# the ImageNet transform: three distinct scales and non-zero shifts, signed images
+STEM_SCALE = (np.float32(1) / (np.float32(255) * np.float32([0.229, 0.224, 0.225]))).astype(np.float32)
+STEM_SHIFT = (-np.float32([0.485, 0.456, 0.406]) / np.float32([0.229, 0.224, 0.225])).astype(np.float32)
+
+
+def stem_out_hw(H, W):
+    """(OH, OW, PH, PW) of an H x W image."""
+    oh, ow = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return oh, ow, (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
+
+
+def stem_form(rows_per_block, OW):
+    """(PR, NW) of the instance stem_pool() launches (stem.hip): 2 -> (2, 4); 1, or a one-group map -> (1, 4);
+    else two pooled rows on 8 waves."""
+    return (2, 4) if rows_per_block == 2 else (1, 4) if rows_per_block == 1 or OW <= 64 else (2, 8)
+
+
+def stem_case(B, H, W, kind):
+    """One shape's inputs: x fp32 [B][3][H][W] (N(0, 1), or U[0, 1) for "rand"), 8-bit pixels u8 [B][3][H][W]
+    (their NHWC form is a transpose), the weight [64][3][7][7] and bias [64] of sigma 0.1 (test_ops_gpu's)."""
+    rng = np.random.default_rng(B * 100000 + H * 1000 + W)
+    x = (rng.standard_normal((B, 3, H, W)) if kind == "randn" else rng.random((B, 3, H, W))).astype(np.float32)
+    u8 = rng.integers(0, 256, (B, 3, H, W), dtype=np.uint8)
+    w = (0.1 * rng.standard_normal((64, 3, 7, 7))).astype(np.float32)
+    b = (0.1 * rng.standard_normal(64)).astype(np.float32)
+    return x, u8, w, b
+
+
+def stem_operands(code, x, w):
+    """float64 (image, weight) values a precision code multiplies: fp16(x) for codes 1 and 2, hi + lo for 3 and 4;
+    fp16(w) for code 1, hi + lo otherwise.  (The kernel leaves out the lo x lo products, about 2^-22 of a term:
+    stem_lattice_ref models that where a bit depends on it.)"""
+    xv = hi_values(x) if code <= 2 else split_values(x)
+    return xv, (hi_values(w) if code == 1 else hilo_values(w))
+
+
+def stem_conv64(xv, wv, pad_value=None):
+    """float64 7x7/s2/p3 conv of [B][3][H][W] values -> NHWC [B][OH][OW][64]; the padding is 0, or with
+    pad_value [3] that constant per channel (a mutant)."""
+    x = torch.from_numpy(np.ascontiguousarray(xv, np.float64))
+    if pad_value is not None:
+        p = torch.from_numpy(np.asarray(pad_value, np.float64)).view(1, 3, 1, 1)
+        x = torch.nn.functional.pad(x - p, (3, 3, 3, 3)) + p
+    else:
+        x = torch.nn.functional.pad(x, (3, 3, 3, 3))
+    y = torch.nn.functional.conv2d(x, torch.from_numpy(np.ascontiguousarray(wv, np.float64)), None, 2, 0)
+    return y.permute(0, 2, 3, 1).contiguous().numpy()
+
+
+def stem_pool64(s, no_left_at=None, no_row_above=None):
+    """3x3/s2/p1 max pool of the ReLU'd stem map s [B][OH][OW][64] (>= 0, so padding may enter as 0).
+    Mutants: no_left_at = pc: pooled column pc misses its left stem column 2 pc - 1 (the column a 64-column
+    group takes from the group before: pc = 32); no_row_above = PR: every pooled row pr > 0 that starts a
+    workgroup of PR rows misses stem row 2 pr - 1 (the row the workgroup recomputes)."""
+    B, OH, OW, C = s.shape
+    PH, PW = (OH - 1) // 2 + 1, (OW - 1) // 2 + 1
+    sp = np.zeros((B, 2 * PH + 2, 2 * PW + 2, C))
+    sp[:, 1:OH + 1, 1:OW + 1] = s
+    out = np.zeros((B, PH, PW, C))
+    for dr in range(3):
+        for dc in range(3):
+            t = sp[:, dr:dr + 2 * PH:2, dc:dc + 2 * PW:2].copy()
+            if dc == 0 and no_left_at is not None and no_left_at < PW:
+                t[:, :, no_left_at] = 0
+            if dr == 0 and no_row_above:
+                t[:, no_row_above::no_row_above] = 0
+            out = np.maximum(out, t)
+    return out
+
+
+def stem_ref(xv, wv, bias, **mutant):
+    """float64 pooled stem output [B][PH][PW][64] on the operand values as given."""
+    pad = mutant.pop("pad_value", None)
+    return stem_pool64(np.maximum(stem_conv64(xv, wv, pad) + np.asarray(bias, np.float64), 0), **mutant)
+
+
+def stem_split_bits(ref):
+    """The split layout of a float64 [..][64] reference as fp16 [..][128]: per pixel [32 hi | 32 lo] x 2."""
+    r = np.asarray(ref, np.float64).astype(np.float32)
+    hi = r.astype(np.float16)
+    lo = (r - hi.astype(np.float32)).astype(np.float16)
+    sh = r.shape[:-1]
+    return np.concatenate([hi.reshape(*sh, 2, 32), lo.reshape(*sh, 2, 32)], axis=-1).reshape(*sh, 128)
+
+
+def stem_from_split(bits16):
+    """fp16 [..][128] split layout -> float64 hi + lo [..][64]."""
+    h = np.asarray(bits16, np.float16).astype(np.float64)
+    sh = h.shape[:-1]
+    h = h.reshape(*sh, 2, 64)
+    return (h[..., :32] + h[..., 32:]).reshape(*sh, 64)
+
+
+def stem_hi_of_split(bits16):
+    """The hi halves of an fp16 [..][128] split output as fp16 [..][64]."""
+    sh = bits16.shape[:-1]
+    return np.ascontiguousarray(np.asarray(bits16).reshape(*sh, 2, 64)[..., :32]).reshape(*sh, 64)
+
+
+# the exact-lattice cases, (B, H, W): one group (tall enough for pooled pixels clear of the border), a second
+# group of two columns with an odd PH and odd image starts, the widest map
+STEM_LATTICE_SHAPES = [(1, 15, 47), (3, 9, 131), (1, 11, 224)]
+
+
+def stem_lattice_case(B, H, W, variant="mixed"):
+    """Inputs whose every product and partial sum is exact in fp32 in any order: the image integers in [0, 7]
+    (xi; what a u8 source feeds under the default transform) plus, for the fp32 source, a lo part of +-2^-10 on
+    the pixels >= 4 (a quarter of an fp16 ulp there: fp16(x) is the integer and the lo plane +-2^-10); weights
+    hi in {-1, 0, 1} plus lo in {-2 .. 2} x 2^-13 where hi != 0, another pattern per tap and channel; bias
+    multiples of 2^-13.  Every term is a multiple of 2^-13 (the lo x lo products, 2^-23, are the ones the
+    kernel omits) and every sum stays below 147 x 7 (1 + 2^-11) + 8 < 2^11.
+    variant "lowt" (the lo-weight case at fp16m): a constant image of 4s, and hi weights that sum to zero per
+    channel, so an interior output is bias + 4 sum(lo) -- a kernel without the lo MFMA gives bias.
+    Returns xi uint8 [B][3][H][W], x fp32 (xi + lo), w fp32 [64][3][7][7], bias fp32 [64]."""
+    rng = np.random.default_rng(5000 + B * 100000 + H * 1000 + W + (variant == "lowt"))
+    n, c, kh, kw = np.meshgrid(np.arange(64), np.arange(3), np.arange(7), np.arange(7), indexing="ij")
+    tap = (c * 7 + kh) * 7 + kw
+    if variant == "lowt":
+        xi = np.full((B, 3, H, W), 4, np.uint8)
+        hi = np.where(tap == (n % 147), 0, np.where((tap + (tap > n % 147) + n) % 2, 1, -1))  # 73 of each sign
+        assert (hi.reshape(64, -1).sum(1) == 0).all()
+        bias = 1 + rng.integers(0, 64, 64) * 2.0 ** -13
+    else:
+        xi = rng.integers(0, 8, (B, 3, H, W)).astype(np.uint8)
+        hi = (n * 5 + tap * 3 + (tap // 7)) % 3 - 1
+        bias = rng.integers(-8 * 2 ** 13, 8 * 2 ** 13, 64) * 2.0 ** -13
+    lo = np.where(hi != 0, (n * 7 + tap * 11 + kw * 3) % 5 - 2, 0) * 2.0 ** -13
+    xlo = np.where(xi >= 4, rng.integers(-1, 2, xi.shape), 0) * 2.0 ** -10
+    x = (xi + xlo).astype(np.float32)
+    w = (hi + lo).astype(np.float32)
+    assert np.array_equal(x.astype(np.float16).astype(np.float64), xi) and np.array_equal(split_values(x), xi + xlo)
+    assert np.array_equal(hi_values(w), hi) and np.array_equal(hilo_values(w), hi + lo)
+    return xi, x, w, bias.astype(np.float32)
+
+
+def stem_lattice_ref(code, x, w, bias, drop_lo_w=False, drop_lo_x=False):
+    """The exact float64 output of a lattice case from the products the kernel forms: hi x hi, then hi x lo
+    (weights; codes >= 2) and lo x hi (image; codes 3 and 4), never lo x lo."""
+    xh, wh = hi_values(x), hi_values(w)
+    xl, wl = split_values(x) - xh, hilo_values(w) - wh
+    acc = stem_conv64(xh, wh)
+    if code >= 2 and not drop_lo_w:
+        acc = acc + stem_conv64(xh, wl)
+    if code >= 3 and not drop_lo_x:
+        acc = acc + stem_conv64(xl, wh)
+    assert np.abs(acc).max() + 8 < 2048 and np.array_equal(acc * 2 ** 13, np.rint(acc * 2 ** 13))
+    return stem_pool64(np.maximum(acc + np.asarray(bias, np.float64), 0))
+
+
+def stem_expected_bits(code, ref):
+    """A float64 reference rounded once as the kernel stores it: fp16 [..][64], or for code 3 the split
+    layout fp16 [..][128]."""
+    return stem_split_bits(ref) if code == 3 else np.asarray(ref, np.float64).astype(np.float32).astype(np.float16)
+
+
+# ---------------------------------------------------------------------------------------------
+# fused avgpool + FC (GemmDesc::pool_rows; test_fc_ops_gpu.py): x [B][HW][C] -> act(mean_HW(x) W^T + bias) [B][N]
+
+# (B, HW, C, N, bias, act): HW = 1, 2, 3, 5 leave some of the four row parts empty; 63 / 64 fill the tile;
+# B = 65 is more than a tile's rows; N = 1, 64 / 65 (one tile to the column, one column into the next), 70, 1000;
+# C = 2048 is 32 (fp16) or 64 k-steps: the 3-stage ring; C = 32 one k-step or half of one
+FC_CASES = [
+    (1, 1, 32, 1, True, None), (65, 2, 96, 64, False, "relu"), (3, 3, 32, 65, True, "relu"),
+    (65, 4, 32, 70, True, None), (3, 5, 96, 64, False, None), (3, 7, 512, 70, True, "relu"),
+    (1, 16, 2048, 65, True, None), (3, 49, 512, 1000, True, None), (3, 49, 512, 1000, False, "relu"),
+    (3, 63, 96, 65, False, None), (3, 64, 32, 1, True, None), (1, 64, 96, 1000, True, None),
+]
+FC_EXACT = [(3, HW, 96, 70) for HW in (1, 2, 4, 16, 64)]
+FC_BAR = 1e-5
+# SPI_GEMM_PLAN forced on one pooled case: every dense tile compiles the pooled epilogue (gemm_tile.hpp)
+FC_FORCED = ["128,128,2,1", "128,64,2,1", "128,64,3,1", "64,64,2,1", "64,64,4,1", "64,64,3,2"]
+FC_FORCED_CASE = (3, 7, 512, 70, True, "relu")
+
+
+def fc_case(B, HW, C, N):
+    """x fp32 [B][HW][C] of N(0, 1) + 0.5 (a mean that does not vanish), W [N][C] of N(0, 1 / C), bias N(0, 1)."""
+    rng = np.random.default_rng(B * 1000003 + HW * 10007 + C * 13 + N)
+    x = (rng.standard_normal((B, HW, C)) + 0.5).astype(np.float32)
+    W = (rng.standard_normal((N, C)) / np.sqrt(C)).astype(np.float32)
+    return x, W, rng.standard_normal(N).astype(np.float32)
+
+
+def fc_exact_case(B, HW, C, N):
+    """Integers: x in [-4, 4], W in {-1, 0, 1}, bias multiples of 1 / 4 -- with HW a power of two every sum,
+    the division and the bias add are exact in fp32 (|sum| <= 64 C 4 < 2^24), in every precision's operands."""
+    rng = np.random.default_rng(77 + HW)
+    x = rng.integers(-4, 5, (B, HW, C)).astype(np.float32)
+    W = rng.integers(-1, 2, (N, C)).astype(np.float32)
+    return x, W, (rng.integers(-16, 17, N) / 4).astype(np.float32)
+
+
+def fc_ref(xv, wv, bias, act, mutant=None):
+    """float64 act(mean over HW of (x W^T) + bias) on the operand values.  Mutants (what a slipped index in the
+    pooled epilogue computes): "next": the tile's 64 rows summed, the next images' included, where they
+    exist; "div64": divided by 64; "part3": the rows r = 3 mod 4 (one of the four partial sums) dropped."""
+    xv = np.asarray(xv, np.float64)
+    B, HW, _ = xv.shape
+    rows = xv.reshape(B * HW, -1) @ np.asarray(wv, np.float64).T
+    if mutant == "next":
+        tot = np.stack([rows[b * HW:b * HW + 64].sum(0) for b in range(B)])
+    elif mutant == "part3":
+        tot = (rows.reshape(B, HW, -1) * (np.arange(HW) % 4 != 3)[None, :, None]).sum(1)
+    else:
+        tot = rows.reshape(B, HW, -1).sum(1)
+    return epilogue64(tot / (64 if mutant == "div64" else HW), bias, None, act)
+
+
+# ---------------------------------------------------------------------------------------------
+# dense GEMM at fp32 / fp16x3 / fp16x3s (spi_op_gemm, precisions 0, 2, 3): the k-step is 32
+
+DENSE32_PRECS = ("fp32", "fp16x3", "fp16x3s")
+# KREP_DENSE's pattern: ragged M and N, K tails of half a step (176 = 160 + 16, 40); the default plan splits the
+# last three
+DENSE32_SHAPES = [(64, 64, 96), (100, 96, 176), (50, 1000, 40), (8, 128, 768), (197, 128, 1024), (64, 64, 1152)]
+DENSE32_FORMS = ["plain", "res", "relu", "gelu"]
+DENSE32_FORCED = [("128,128,2,1", (50, 1000, 96)), ("128,64,2,1", (197, 128, 176)), ("128,64,3,2", (197, 128, 1024)),
+                  ("64,64,2,5", (100, 96, 448)), ("64,64,3,3", (64, 64, 1152)), ("64,64,4,2", (100, 96, 448))]
+DENSE32_XCD = (300, 320, 64)  # under "64,64,2,1": 5 x 5 tiles
+
+
+def dense32_shape(prec, M, N, K):
+    """The split layout keeps its multiples of 32 (K and N rounded down)."""
+    return (M, N // 32 * 32, K // 32 * 32) if prec == "fp16x3s" else (M, N, K)
+
+
+def dense32_case(M, N, K):
+    """fp32 A of N(0, 1), W of N(0, 1 / K), bias and residual at a quarter of the output's sigma."""
+    rng = np.random.default_rng(M * 7 + N * 3 + K + 1)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    W = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    return A, W, (0.25 * rng.standard_normal(N)).astype(np.float32), (0.25 * rng.standard_normal((M, N))).astype(np.float32)
+
+
+def dense32_ksteps(K):
+    """k-steps of 32 in the packed K (padded to a multiple of 64)."""
+    return -(-K // 64) * 2
+
+
+def forced_splits(ksteps, splits, max_split=8):
+    """finish_plan's slice count for a 64-column tile: slices of ceil(ksteps / splits) steps."""
+    s = max(1, min(splits, max_split, ksteps))
+    kt = -(-ksteps // s)
+    return -(-ksteps // kt), kt

@@ -133,3 +133,48 @@ def test_gemm256_ln_chunk_guard(spi, chunks, bm):
     finally:
         gen.apply_setting(spi.lib, {k: v for k, v in saved.items() if v is not None})
     assert plain[0] == 256 and got[0] == bm, (chunks, got, plain)
+
+
+POOLED_FORCED = ["128,128,2,1", "128,64,2,1", "128,64,3,1", "64,64,2,1", "64,64,3,2", "64,64,4,1"]
+
+
+@pytest.mark.parametrize("plan", POOLED_FORCED)
+def test_forced_plan_on_a_pooled_gemm(spi, plan):
+    """A pooled problem (avgpool + FC, pool_rows) under SPI_GEMM_PLAN takes the forced tile, ring depth and
+    split: every dense instance compiles the pooled epilogue (gemm_tile.hpp's static_assert), so none falls
+    through to the ordinary [M][N] store.  One image per tile row whatever the tile height: tiles = B x
+    ceil(N / bn), and a forced split's slabs and tickets are sized from that."""
+    bm, bn, stages, splits = (int(v) for v in plan.split(","))
+    saved = {k: os.environ.get(k) for k in gen.KNOBS}
+    try:
+        gen.apply_setting(spi.lib, {"SPI_GEMM_PLAN": plan})
+        for prec, ksteps in ((0, 16), (1, 8), (2, 16), (3, 16)):
+            v = gen.query(spi.lib, f"d:{prec},21,70,512,512,1,7,{gen.OUT_F32}")  # B = 3, HW = 7, C = 512, N = 70
+            pl = dict(zip(PLAN, v[4:12]))
+            want = splits if bn == 64 else 1
+            assert (v[0], pl["bm"], pl["bn"], pl["stages"], pl["splits"]) == (0, bm, bn, stages, want), (plan, v)
+            assert pl["k_per_split"] * want == ksteps * (64 if prec == 1 else 32), (plan, v)
+            tiles = 3 * -(-70 // bn)
+            assert v[12:] == ([tiles * want * bm * bn, tiles] if want > 1 else [0, 0]), (plan, v)
+    finally:
+        gen.apply_setting(spi.lib, {k: v for k, v in saved.items() if v is not None})
+
+
+def test_forced_split_of_a_pooled_gemm_must_fit_the_op_workspace(spi):
+    """The plan rule never splits a pooled GEMM, so spi_op_avgpool_fc used to skip the workspace check; a forced
+    8-way split of B = 65, N = 1000 needs 65 x 16 x 8 slabs of 64 x 64 floats, twice the op workspace's 16 Mi
+    floats.  Refused before anything is launched (the pointers here are never dereferenced)."""
+    import ctypes as C
+
+    from importlib import import_module
+    native = import_module("starpu-inference-server_amd._native")
+    saved = {k: os.environ.get(k) for k in gen.KNOBS}
+    fake = [C.c_void_p(0x10000000 * i) for i in range(1, 6)]
+    try:
+        gen.apply_setting(spi.lib, {"SPI_GEMM_PLAN": "64,64,2,8", "SPI_GEMM_MAXSPLIT": "0"})
+        v = gen.query(spi.lib, f"d:0,260,1000,512,512,1,4,{gen.OUT_F32}")
+        assert v[7] == 8 and v[12] == 65 * 16 * 8 * 64 * 64 > 16 << 20, v
+        rc = spi.lib.spi_op_avgpool_fc(0, fake[0], 65, 4, 512, fake[1], 1000, fake[2], fake[3], 0, fake[4], None)
+        assert rc != 0 and "too large for the op workspace" in native.last_error()
+    finally:
+        gen.apply_setting(spi.lib, {k: v for k, v in saved.items() if v is not None})

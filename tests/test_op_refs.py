@@ -515,3 +515,174 @@ def test_small_refs_equal_torch():
     x = rng.standard_normal((21, 12)).astype(np.float32)
     np.testing.assert_array_equal(R.gather_rows_ref(x, 4, 5, False), x[[0, 5, 10, 15]])
     np.testing.assert_array_equal(R.gather_rows_ref(x, 4, 5, True), torch.from_numpy(x[[0, 5, 10, 15]]).half().numpy())
+
+
+# ---- the fused stem (test_stem_ops_gpu.py) ------------------------------------------------------
+
+
+def moved(mutant, ref):
+    """The largest move of an output element, in units of max|ref| (what normalized_max_error would report)."""
+    return R.nerr(mutant, ref)
+
+
+@pytest.mark.parametrize("B,H,W,kind", [(3, 9, 7, "rand"), (1, 13, 190, "rand"), (3, 1, 223, "rand")])
+def test_stem_ref_equals_torch_float64(B, H, W, kind):
+    x, _, w, b = R.stem_case(B, H, W, kind)
+    t = lambda a: torch.from_numpy(np.asarray(a, np.float64))  # noqa: E731
+    ref = F.max_pool2d(F.relu(F.conv2d(t(x), t(w), t(b), 2, 3)), 3, 2, 1).permute(0, 2, 3, 1).numpy()
+    got = R.stem_ref(x.astype(np.float64), w.astype(np.float64), b)
+    assert got.shape == (B,) + R.stem_out_hw(H, W)[2:] + (64,)
+    assert R.nerr(got, ref) < TOL64
+
+
+def test_stem_shapes_reach_the_edges_they_name():
+    """The case table against test_stem_ops_gpu's docstring: every width and height the kernel's paths turn
+    on, odd image starts, and which shapes run the 8-wave form."""
+    widths, heights = {s[2] for s in R.STEM_SHAPES}, {s[1] for s in R.STEM_SHAPES}
+    assert widths >= {1, 7, 8, 47, 127, 128, 129, 130, 131, 132, 190, 221, 222, 223, 224}
+    assert heights >= {1, 2, 9, 10, 11, 13, 23, 40}
+    geo = {s[:3]: R.stem_out_hw(s[1], s[2]) for s in R.STEM_SHAPES}
+    assert geo[(1, 2, 129)] == (1, 65, 1, 33) and geo[(1, 23, 130)][1] == 65  # a second group of one column
+    assert geo[(3, 9, 131)][1:] == (66, 3, 33) and geo[(1, 11, 132)][1] == 66  # of two; PH odd under PR = 2
+    assert any(ow > 64 and ph == 1 for (_, ow, ph, _) in geo.values())          # PH = 1 under PR = 2, 8 waves
+    assert any(ow > 64 and ow % 2 and pw % 2 == 0 for (_, ow, _, pw) in geo.values())
+    assert any(ow > 64 and pw % 2 for (_, ow, _, pw) in geo.values())           # odd PW
+    assert sum(B == 3 and (3 * H * W) % 2 == 1 for (B, H, W, _) in R.STEM_SHAPES) >= 3  # images 16 bytes off
+    assert {k for (_, _, _, k) in R.STEM_SHAPES} == {"rand", "randn"}
+    for W in R.STEM_REFUSED_W:
+        assert R.stem_out_hw(9, W)[1] == 113
+    # the 8-wave form away from 224, and every form at every shape's three rows_per_block settings
+    assert sum(R.stem_form(0, ow) == (2, 8) for (_, ow, _, _) in geo.values()) >= 8
+    assert {R.stem_form(r, ow) for r in (0, 1, 2) for (_, ow, _, _) in geo.values()} == {(1, 4), (2, 4), (2, 8)}
+
+
+@pytest.mark.parametrize("B,H,W,kind", R.STEM_SHAPES, ids=[f"{s[0]}x{s[1]}x{s[2]}" for s in R.STEM_SHAPES])
+def test_stem_cases_discriminate(B, H, W, kind):
+    """What a subtly wrong stem kernel computes, on the GPU test's own inputs: each mutant moves an output
+    element by more than 10x the bar of the case that is to catch it (1e-5 into the split output for the two
+    lo halves, which an fp16 output cannot see; 1e-3 for the rest, caught at every precision)."""
+    x, u8, w, b = R.stem_case(B, H, W, kind)
+    _, _, PH, PW = R.stem_out_hw(H, W)
+    xv, wv = R.stem_operands(3, x, w)
+    ref = R.stem_ref(xv, wv, b)
+    got = {}
+    if PW > 32:  # two groups: the column a group takes from the one before
+        got["left neighbour at pooled column 32"] = (moved(R.stem_ref(xv, wv, b, no_left_at=32), ref), 1e-3)
+    for PR in (1, 2):
+        if PH > PR:
+            got[f"recomputed row above, PR = {PR}"] = (moved(R.stem_ref(xv, wv, b, no_row_above=PR), ref), 1e-3)
+    got["lo weights"] = (moved(R.stem_ref(xv, R.hi_values(w), b), ref), 1e-5)
+    got["lo image"] = (moved(R.stem_ref(R.hi_values(x), wv, b), ref), 1e-5)
+    xu = R.split_values(R.xf_image(u8, False, R.STEM_SCALE, R.STEM_SHIFT))
+    got["padding as shift[c]"] = (moved(R.stem_ref(xu, wv, b, pad_value=R.split_values(R.STEM_SHIFT)),
+                                        R.stem_ref(xu, wv, b)), 1e-3)
+    if W > 3:  # tap kw = 6 is image column 2 ow + 3
+        w6 = wv.copy()
+        w6[..., 6] = 0
+        got["tap kw = 6"] = (moved(R.stem_ref(xv, w6, b), ref), 1e-3)
+    if W % 2:
+        xl = xv.copy()
+        xl[..., W - 1] = 0
+        got["last column of an odd W"] = (moved(R.stem_ref(xl, wv, b), ref), 1e-3)
+    print({k: f"{v / bar:.0f}x" for k, (v, bar) in got.items()})
+    for name, (v, bar) in got.items():
+        assert v > 10 * bar, f"{name}: moves {v:.2e}, bar {bar:.0e}"
+
+
+@pytest.mark.parametrize("B,H,W", R.STEM_LATTICE_SHAPES)
+def test_stem_lattice_cases_discriminate(B, H, W):
+    """The lattice cases: the stored bits change when a lo half is dropped -- at every code that has it, and
+    in the lo-weight variant at fp16m, whose fp16 output a parity bar of 1e-3 cannot hold to the lo weights."""
+    for variant in ("mixed", "lowt"):
+        _, x, w, b = R.stem_lattice_case(B, H, W, variant)
+        for code in (1, 2, 3, 4):
+            want = R.stem_expected_bits(code, R.stem_lattice_ref(code, x, w, b))
+            assert float(want.astype(np.float64).max()) > 0
+            if code >= 2:
+                no_w = R.stem_expected_bits(code, R.stem_lattice_ref(code, x, w, b, drop_lo_w=True))
+                assert not np.array_equal(no_w.view(np.int16), want.view(np.int16)), (variant, code)
+            if code >= 3 and variant == "mixed":
+                no_x = R.stem_expected_bits(code, R.stem_lattice_ref(code, x, w, b, drop_lo_x=True))
+                assert not np.array_equal(no_x.view(np.int16), want.view(np.int16)), code
+    # the lo-weight variant's interior is bias + 4 sum(lo), on the lattice and not the bias
+    _, x, w, b = R.stem_lattice_case(B, H, W, "lowt")
+    lo_sum = (R.hilo_values(w) - R.hi_values(w)).reshape(64, -1).sum(1)
+    np.testing.assert_array_equal(R.stem_conv64(R.hi_values(x), R.hilo_values(w))[0, 2, 4], 4 * lo_sum)
+    if H >= 14:  # a pooled pixel whose nine stem pixels are all interior
+        np.testing.assert_array_equal(R.stem_lattice_ref(2, x, w, b)[0, 2, 3], b.astype(np.float64) + 4 * lo_sum)
+    assert (np.abs(4 * lo_sum) >= 2.0 ** -10).sum() > 32  # above an fp16 ulp at 1 in most channels
+
+
+def test_stem_split_bits_round_trip(ops):
+    ref = np.random.default_rng(9).standard_normal((2, 3, 5, 64)) * 3
+    bits = R.stem_split_bits(ref)
+    want = ops.to_split(torch.from_numpy(ref.astype(np.float32))).view(torch.float16).numpy()
+    np.testing.assert_array_equal(bits.view(np.int16), want.reshape(bits.shape).view(np.int16))
+    assert R.nerr(R.stem_from_split(bits), ref) < 2.0 ** -21
+    np.testing.assert_array_equal(R.stem_hi_of_split(bits), ref.astype(np.float32).astype(np.float16))
+
+
+# ---- fused avgpool + FC (test_fc_ops_gpu.py) ----------------------------------------------------
+
+
+def test_fc_ref_equals_torch_float64():
+    x, W, b = R.fc_case(3, 7, 96, 70)
+    t = lambda a: torch.from_numpy(np.asarray(a, np.float64))  # noqa: E731
+    ref = F.relu(F.linear(t(x).mean(1), t(W), t(b))).numpy()
+    assert R.nerr(R.fc_ref(x, W, b, "relu"), ref) < TOL64
+
+
+@pytest.mark.parametrize("case", R.FC_CASES, ids=["x".join(map(str, c[:4])) for c in R.FC_CASES])
+def test_fc_cases_discriminate(case):
+    """The pooled epilogue's slipped indices on the GPU test's inputs, each above 10x the 1e-5 bar wherever the
+    case can show it: the next image's rows (B > 1, HW < 64), / 64 (HW < 64), a row part dropped (HW >= 4)."""
+    B, HW, C, N, has_bias, act = case
+    x, W, b = R.fc_case(B, HW, C, N)
+    for prec in ("fp32", "fp16", "fp16x3s"):
+        xv, wv = R.operand_values(prec, x, W)
+        bias = b if has_bias else None
+        ref = R.fc_ref(xv, wv, bias, act)
+        assert np.abs(ref).max() > 0.1
+        if B > 1 and HW < 64:
+            assert moved(R.fc_ref(xv, wv, bias, act, "next"), ref) > 10 * R.FC_BAR
+        if HW < 64:
+            assert moved(R.fc_ref(xv, wv, bias, act, "div64"), ref) > 10 * R.FC_BAR
+        if HW >= 4:
+            assert moved(R.fc_ref(xv, wv, bias, act, "part3"), ref) > 10 * R.FC_BAR
+
+
+def test_fc_case_table_covers_the_issue():
+    col = lambda i: {c[i] for c in R.FC_CASES}  # noqa: E731
+    assert col(1) >= {1, 2, 3, 4, 5, 7, 16, 49, 63, 64} and col(0) == {1, 3, 65}
+    assert col(3) == {1, 64, 65, 70, 1000} and col(2) == {32, 96, 512, 2048}
+    assert col(4) == {True, False} and col(5) == {None, "relu"}
+    assert all(B * HW <= 320 for (B, HW, _, _, _, _) in R.FC_CASES)
+
+
+@pytest.mark.parametrize("B,HW,C,N", R.FC_EXACT)
+def test_fc_exact_case_is_exact(B, HW, C, N):
+    x, W, b = R.fc_exact_case(B, HW, C, N)
+    ref = R.fc_ref(x, W, b, None)
+    assert np.array_equal(ref, ref.astype(np.float32)) and np.abs(x.reshape(B * HW, C) @ W.T).max() * HW < 2 ** 24
+    for prec in ("fp16", "fp16x3s"):  # the operands survive every precision's rounding
+        xv, wv = R.operand_values(prec, x, W)
+        assert np.array_equal(xv, x) and np.array_equal(wv, W)
+    assert not np.array_equal(R.fc_ref(x, W, b, None, "part3") if HW >= 4 else ref + 1, ref)
+
+
+def test_forced_splits_restates_finish_plan(spi):
+    """op_refs.forced_splits against the planner under SPI_GEMM_PLAN (the GPU tests assert plans with it)."""
+    import ctypes as C
+    import os
+    try:
+        for plan, (M, N, K) in R.DENSE32_FORCED:
+            bm, bn, st, sp = (int(v) for v in plan.split(","))
+            os.environ["SPI_GEMM_PLAN"] = plan
+            spi.lib.spi_debug_gemm_reload_env()
+            out = (C.c_longlong * 14)()
+            assert spi.lib.spi_debug_gemm_plan(0, M, N, K, K, 1, 0, C.c_uint(0), out) == 0
+            splits, kt = R.forced_splits(R.dense32_ksteps(K), sp if bn == 64 else 1)
+            assert [int(v) for v in out[4:8]] == [bm, bn, st, splits] and int(out[11]) == kt * 32, (plan, list(out))
+    finally:
+        os.environ.pop("SPI_GEMM_PLAN", None)
+        spi.lib.spi_debug_gemm_reload_env()
