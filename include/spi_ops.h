@@ -381,6 +381,28 @@ int spi_op_softmax_topk(const float* x, int64_t ldx, float* probs, float* topv, 
 int spi_op_gather_rows(const float* x, void* y, int32_t rows, int32_t stride_rows, int32_t D, int32_t out_f16,
                        void* stream);
 
+/* ---- ConvNeXt kernels (dwconv_ln.hip): precision 0 (fp32) or 1 (fp16) is the type of x, w_packed and y;
+ * bias, gamma and beta are fp32 [C].  C a multiple of 32 from 32 to 1536; every device pointer 16-byte aligned.
+ * A refused call returns non-zero, launches nothing and leaves its reason in spi_last_error(). ---- */
+/* torch's depthwise weight [C][1][7][7] (host fp32) -> [49][C] of the precision's type (host). */
+int spi_op_dwconv7_pack_weight(int32_t precision, const float* w_host, int32_t C, void* dst_host);
+/* y [B H W][C] = LayerNorm(dwconv7x7(x NHWC [B][H][W][C], pad 3, stride 1) + bias) * gamma + beta, one launch,
+ * fp32 accumulation and two-pass fp32 statistics. */
+int spi_op_dwconv7_ln(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C,
+                      const void* w_packed, const float* bias, const float* gamma, const float* beta, float eps, void* y,
+                      void* stream);
+/* LayerNorm over C of each pixel of x NHWC [B][H][W][C] (even H, W), written to columns ((h & 1) 2 + (w & 1)) C + c
+ * of row (b, h / 2, w / 2) of y [B (H/2) (W/2)][4 C]: the A operand of a 2x2 / stride 2 conv as a dense GEMM. */
+int spi_op_ln_space_to_depth(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C,
+                             const float* gamma, const float* beta, float eps, void* y, void* stream);
+/* A 2x2 / stride 2 conv weight [N][C][2][2] (host fp32) -> [N][4 C] in that column order (host fp32);
+ * 1 <= N, C <= 65536.  The packer's own permutation, exported so that a host test can hold it against a conv. */
+int spi_op_s2d_pack_weight(const float* w_host, int32_t N, int32_t C, float* dst_host);
+/* LayerNorm over C of `rows` rows: x fp32 (x_f32) or the precision's type, y the precision's type.  pool_hw > 0:
+ * row r is LayerNorm(mean of input rows r pool_hw .. (r + 1) pool_hw - 1): global average pool + LayerNorm. */
+int spi_op_ln_rows(int32_t precision, const void* x, int32_t x_f32, int32_t rows, int32_t C, int32_t pool_hw,
+                   const float* gamma, const float* beta, float eps, void* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

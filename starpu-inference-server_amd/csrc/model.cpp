@@ -2,6 +2,7 @@
 // helpers; forward plans for ResNet (basic / bottleneck), BERT (post-LN) and ViT (pre-LN).
 // Reference counterparts: the per-device clones (src/core/inference_runner.cpp:251-275) and the
 // forward that LibTorch runs inside the codelet (src/core/starpu_setup.cpp:610).
+#include "convnext_pack.hpp"
 #include "gconv.hpp"
 #include "model.hpp"
 
@@ -549,6 +550,54 @@ void Model::body_vit_folded(Workspace& w, int B, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------
+// ConvNeXt plan: the launching visitor of walk_convnext (model_plan.hpp)
+// ---------------------------------------------------------------------------
+void Model::body_convnext(Workspace& w, int B, hipStream_t s) {
+  struct Launch {
+    Model& M;
+    Workspace& w;
+    hipStream_t s;
+    const PackedModel& m = M.m_;
+    void* const* buf = w.bufs.data();
+    const size_t es = m.f16 ? 2 : 4;
+    void stem(int B, int H, int out) {
+      const int rows = B * H * H, C = m.cn_stem.n;
+      M.run_gemm(m.cn_stem, cn_gemm_desc(m.cn_stem, rows, Act::None, false, true), buf[kCnPatches], buf[kCnHidden], nullptr,
+                 LnPtrs{}, w, s);
+      M.prof_op(s, [&] { return "ln_rows_c" + std::to_string(C); }, 0, (double)rows * C * (4 + es), [&] {
+        ln_rows(buf[kCnHidden], true, buf[out], M.ptr<float>(m.cn_stem_ln.g), M.ptr<float>(m.cn_stem_ln.b), rows, C, 0,
+                m.eps, m.f16, s);
+      });
+    }
+    void down(int B, int H, const CnDown& d, int in, int out) {
+      const int C = d.conv.k / 4, rows = B * (H / 2) * (H / 2);
+      M.prof_op(s, [&] { return "ln_s2d_c" + std::to_string(C); }, 0, 2.0 * B * H * H * C * es, [&] {
+        ln_space_to_depth(buf[in], buf[kCnLn], M.ptr<float>(d.ln.g), M.ptr<float>(d.ln.b), B, H, H, C, m.eps, m.f16, s);
+      });
+      M.run_gemm(d.conv, cn_gemm_desc(d.conv, rows, Act::None, false, false), buf[kCnLn], buf[out], nullptr, LnPtrs{}, w, s);
+    }
+    void block(int B, int H, const CnBlock& k, int in, int out) {
+      const int rows = B * H * H;
+      M.prof_op(s, [&] { return "dwconv7_ln_c" + std::to_string(k.C) + "_h" + std::to_string(H); },
+                2.0 * kDwconvTaps * k.C * (double)rows, 2.0 * rows * k.C * es + (double)kDwconvTaps * k.C * es, [&] {
+                  dwconv7_ln(buf[in], M.ptr<void>(k.dw_w), M.ptr<float>(k.dw_b), M.ptr<float>(k.ln.g), M.ptr<float>(k.ln.b),
+                             buf[kCnLn], B, H, H, k.C, m.eps, m.f16, s);
+                });
+      M.run_gemm(k.fc1, cn_gemm_desc(k.fc1, rows, Act::Gelu, false, false), buf[kCnLn], buf[kCnHidden], nullptr, LnPtrs{}, w, s);
+      M.run_gemm(k.fc2, cn_gemm_desc(k.fc2, rows, Act::None, true, false), buf[kCnHidden], buf[out], buf[in], LnPtrs{}, w, s);
+    }
+    void tail(int B, int H, int in) {
+      const int C = m.feat;
+      M.prof_op(s, [&] { return "pool_ln_c" + std::to_string(C); }, 0, ((double)B * H * H + B) * C * es, [&] {
+        ln_rows(buf[in], false, buf[kCnPooled], M.ptr<float>(m.final_ln.g), M.ptr<float>(m.final_ln.b), B, C, H * H, m.eps,
+                m.f16, s);
+      });
+    }
+  };
+  walk_convnext(m_, B, Launch{*this, w, s});
+}
+
+// ---------------------------------------------------------------------------
 // Forward: prologue -> body (graph-capturable) -> epilogue, each dispatched by family (model.hpp)
 // ---------------------------------------------------------------------------
 void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStream_t s, ImageSrc isrc) {
@@ -560,7 +609,9 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
     // the input resize: one launch writes the normalised fp32 NCHW image into the workspace, and the
     // family's fp32-source prologue below reads it as it reads an fp32 task
     if (!opt_.resize_short) throw std::logic_error("prologue: a resized source without the input resize");
-    float* y = static_cast<float*>(w.bufs[m_.family == SPI_FAMILY_RESNET ? (int)kRnResized : (int)kVtResized]);
+    float* y = static_cast<float*>(w.bufs[m_.family == SPI_FAMILY_RESNET     ? (int)kRnResized
+                                          : m_.family == SPI_FAMILY_CONVNEXT ? (int)kCnResized
+                                                                             : (int)kVtResized]);
     prof_op(s, "resize_crop_u8", 0, (double)B * 3 * ((double)isrc.H * isrc.W + (double)image * image * 4), [&] {
       resize_crop_u8(in[0], src == kSrcU8Nhwc, B, isrc.H, isrc.W, opt_.resize_short, image, input_xf_, y, s);
     });
@@ -592,6 +643,10 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
       return prof_op(s, "patchify", 0, (double)B * 3 * image * image * (4 + (f16 ? 2 : 4)), [&] {
         patchify(image_in, w.bufs[kVtPatches], B, 3, image, image, m_.patch, f16, s, src, input_xf_);
       });
+    case SPI_FAMILY_CONVNEXT:  // the 4x4 / stride 4 stem's patches: ViT's kernel at patch 4
+      return prof_op(s, "patchify", 0, (double)B * 3 * image * image * (4 + (f16 ? 2 : 4)), [&] {
+        patchify(image_in, w.bufs[kCnPatches], B, 3, image, image, 4, f16, s, src, input_xf_);
+      });
   }
 }
 
@@ -600,6 +655,7 @@ void Model::body(Workspace& w, int B, int S, hipStream_t s) {
     case SPI_FAMILY_RESNET: return body_resnet(w, B, s);
     case SPI_FAMILY_BERT: return body_bert(w, B, S, s);
     case SPI_FAMILY_VIT: return body_vit(w, B, s);
+    case SPI_FAMILY_CONVNEXT: return body_convnext(w, B, s);
   }
 }
 
@@ -619,6 +675,11 @@ void Model::epilogue(Workspace& w, int B, int S, void* const* out, hipStream_t s
     case SPI_FAMILY_VIT: {
       float* logits = logits_dst(w.bufs[kVtLogits], out);
       run_gemm(m_.head, linear_layer_desc(m_.head, B), w.bufs[kVtCls], logits, nullptr, LnPtrs{}, w, s);
+      return run_image_outputs(logits, B, out, s);
+    }
+    case SPI_FAMILY_CONVNEXT: {
+      float* logits = logits_dst(w.bufs[kCnLogits], out);
+      run_gemm(m_.fc, linear_layer_desc(m_.fc, B), w.bufs[kCnPooled], logits, nullptr, LnPtrs{}, w, s);
       return run_image_outputs(logits, B, out, s);
     }
   }

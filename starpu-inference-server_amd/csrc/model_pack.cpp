@@ -12,6 +12,7 @@
 #include <sstream>
 #include <stdexcept>
 
+#include "convnext_pack.hpp"
 #include "gconv.hpp"
 #include "ln_fold_pack.hpp"
 #include "pack.hpp"
@@ -280,6 +281,7 @@ struct Packer {
   void build_bert(const PMap& p, const PMap& all);
   void pack_bert_head(const PMap& all, bool two_layer);
   void build_vit(const PMap& p);
+  void build_convnext(const PMap& p);
 };
 
 void Packer::build_resnet(const PMap& p) {
@@ -577,6 +579,92 @@ void Packer::build_vit(const PMap& p) {
   m.seq = m.npatch + 1;
 }
 
+// torchvision's ConvNeXt: features.0 the stem (4x4 / stride 4 conv, LayerNorm2d), features.1, 3, 5, 7 the
+// stages of CNBlocks, features.2, 4, 6 the downsamples (LayerNorm2d, 2x2 / stride 2 conv), classifier.0 / .2.
+void Packer::build_convnext(const PMap& p) {
+  auto refuse = [](const std::string& what) { throw std::runtime_error("convnext: " + what); };
+  auto feat = [](int i) { return "features." + std::to_string(i) + "."; };
+  if (m.image % 32) refuse("image size " + std::to_string(m.image) + " must be a multiple of 32");
+  const spi_named_tensor* sw = need(p, "features.0.0.weight");
+  if (sw->ndim != 4 || sw->shape[1] != 3 || sw->shape[2] != 4 || sw->shape[3] != 4)
+    refuse("features.0.0.weight must be a 4x4 conv over 3 channels");
+  auto width_ok = [&](int C) {
+    if (!dwconv7_supported(C)) refuse("stage width " + std::to_string(C) + " must be a multiple of 32, at most 1536");
+  };
+  int C = (int)sw->shape[0];
+  width_ok(C);
+  // patchify's (c, kh, kw) column order is the conv weight's own flattening, as ViT's conv_proj
+  m.cn_stem = pack_linear(fdata(sw), has(p, "features.0.0.bias") ? fdata(need(p, "features.0.0.bias")) : nullptr, C, 48, false);
+  m.cn_stem_ln = pack_ln(p, "features.0.1");
+  const size_t es = m.f16 ? 2 : 4;
+  int H = m.image / 4;  // the map's side: every downsample halves it and needs it even
+  for (int stage = 0; has(p, feat(2 * stage + 1) + "0.block.0.weight"); ++stage) {
+    if (stage > 0) {
+      const std::string pre = feat(2 * stage);
+      if (H % 2)
+        refuse("the downsample before stage " + std::to_string(stage) + " would halve a map of odd side " + std::to_string(H) +
+               " (image " + std::to_string(m.image) + " over " + std::to_string(stage) + " stages)");
+      H /= 2;
+      const spi_named_tensor* dw = need(p, pre + "1.weight");
+      if (dw->ndim != 4 || dw->shape[1] != C || dw->shape[2] != 2 || dw->shape[3] != 2)
+        refuse(pre + "1.weight must be a 2x2 conv over the " + std::to_string(C) + " channels of stage " + std::to_string(stage - 1));
+      const int N = (int)dw->shape[0];
+      if (N != 2 * C)
+        refuse("stage " + std::to_string(stage) + " has " + std::to_string(N) + " channels: a downsample must double the " +
+               std::to_string(C) + " before it");
+      width_ok(N);
+      CnDown d;
+      d.ln = pack_ln(p, pre + "0");
+      std::vector<float> wp((size_t)N * 4 * C);
+      s2d_permute_weight(fdata(dw), N, C, wp.data());
+      d.conv = pack_linear(wp.data(), has(p, pre + "1.bias") ? fdata(need(p, pre + "1.bias")) : nullptr, N, 4 * C, false);
+      m.cn_down.push_back(d);
+      C = N;
+    }
+    m.cn_dims.push_back(C);
+    int nb = 0;
+    for (;; ++nb) {
+      const std::string pre = feat(2 * stage + 1) + std::to_string(nb) + ".";
+      if (!has(p, pre + "block.0.weight")) break;
+      const spi_named_tensor* dw = need(p, pre + "block.0.weight");
+      if (dw->ndim != 4 || dw->shape[0] != C || dw->shape[1] != 1 || dw->shape[2] != 7 || dw->shape[3] != 7)
+        refuse(pre + "block.0.weight must be a depthwise [C][1][7][7] weight with C = " + std::to_string(C));
+      CnBlock blk;
+      blk.C = C;
+      blk.dw_w = blob.add(nullptr, (size_t)kDwconvTaps * C * es);
+      if (m.f16)
+        dwconv7_pack_into(reinterpret_cast<_Float16*>(blob.data.data() + blk.dw_w), fdata(dw), C);
+      else
+        dwconv7_pack_into(reinterpret_cast<float*>(blob.data.data() + blk.dw_w), fdata(dw), C);
+      std::vector<float> zeros(C, 0.f);
+      blk.dw_b = pack_vec(has(p, pre + "block.0.bias") ? fdata(need(p, pre + "block.0.bias")) : zeros.data(), C);
+      blk.ln = pack_ln(p, pre + "block.2");
+      blk.fc1 = pack_linear_named(p, pre + "block.3", false);
+      // layer_scale [C][1][1] folded into block.5 in fp32, before the compute type's rounding
+      const spi_named_tensor* w2 = need(p, pre + "block.5.weight");
+      const spi_named_tensor* ls = need(p, pre + "layer_scale");
+      if (blk.fc1.k != C || blk.fc1.n < 1 || w2->ndim != 2 || w2->shape[0] != C || w2->shape[1] != blk.fc1.n || numel(ls) != C)
+        refuse(pre + "block.3 / block.5 / layer_scale do not chain over " + std::to_string(C) + " channels");
+      const int K = blk.fc1.n;
+      const float *wsrc = fdata(w2), *g = fdata(ls), *bsrc = fdata(need(p, pre + "block.5.bias"));
+      std::vector<float> wf((size_t)C * K), bf(C);
+      for (int n = 0; n < C; ++n) {
+        for (int k = 0; k < K; ++k) wf[(size_t)n * K + k] = g[n] * wsrc[(size_t)n * K + k];
+        bf[n] = g[n] * bsrc[n];
+      }
+      blk.fc2 = pack_linear(wf.data(), bf.data(), C, K, false);
+      m.cn_blocks.push_back(blk);
+    }
+    m.stage_blocks.push_back(nb);
+  }
+  if (m.cn_blocks.empty()) refuse("no blocks (features.1.0.block.0.weight)");
+  m.final_ln = pack_ln(p, "classifier.0");
+  m.fc = pack_linear_named(p, "classifier.2", false);
+  if (m.fc.k != C) refuse("classifier.2 reads " + std::to_string(m.fc.k) + " of " + std::to_string(C) + " features");
+  m.classes = m.fc.n;
+  m.feat = m.fc.k;
+}
+
 }  // namespace
 
 PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* params, int n) {
@@ -602,7 +690,10 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     if (ends_with(p, "embeddings.word_embeddings.weight")) m.family = SPI_FAMILY_BERT;
     else if (ends_with(p, "conv_proj.weight") && ends_with(p, "class_token")) m.family = SPI_FAMILY_VIT;
     else if (ends_with(p, "layer1.0.conv1.weight")) m.family = SPI_FAMILY_RESNET;
-    else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT parameter names");
+    else if (ends_with(p, "features.0.0.weight") && ends_with(p, "features.1.0.block.0.weight") &&
+             ends_with(p, "features.1.0.layer_scale"))
+      m.family = SPI_FAMILY_CONVNEXT;
+    else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT/ConvNeXt parameter names");
   }
   if (const int io = cfg.bert_io) {  // spi_codelet.h: enum spi_bert_io
     constexpr int heads = SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA;
@@ -643,6 +734,15 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     pk.build_vit(strip_prefix(p, "conv_proj.weight"));
     os << "vit L" << m.layers << " D" << m.D << " H" << m.heads << " MLP" << m.ffn << " patch" << m.patch
        << " img" << m.image << " classes" << m.classes;
+  } else if (m.family == SPI_FAMILY_CONVNEXT) {
+    if (cfg.precision != SPI_PREC_F16 && cfg.precision != SPI_PREC_F32)
+      throw std::runtime_error(
+          "convnext: SPI_PREC_F16X3 and SPI_PREC_F16M are not served for this family; use SPI_PREC_F16 or SPI_PREC_F32");
+    m.eps = cfg.eps > 0 ? cfg.eps : 1e-6f;
+    pk.build_convnext(strip_prefix(p, "features.0.0.weight"));
+    os << "convnext[";
+    for (size_t i = 0; i < m.stage_blocks.size(); ++i) os << (i ? "," : "") << m.stage_blocks[i];
+    os << "] C" << m.cn_dims.front() << " img" << m.image << " classes" << m.classes;
   } else {
     throw std::runtime_error("unsupported model family");
   }

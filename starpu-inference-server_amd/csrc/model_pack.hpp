@@ -53,6 +53,18 @@ struct TfLayer {  // BERT (post-LN) / ViT (pre-LN) encoder layer
   LnW ln1, ln2;
 };
 
+struct CnBlock {  // ConvNeXt block: depthwise 7x7 + LayerNorm (dwconv_ln.hip), Linear C -> 4C, GELU, Linear 4C -> C
+  int C = 0;
+  size_t dw_w = 0, dw_b = 0;  // [49][C] in the compute type, fp32 [C]
+  LnW ln;
+  LinearW fc1, fc2;  // fc2 with layer_scale folded in: W' = diag(gamma) W, b' = gamma b
+};
+
+struct CnDown {  // ConvNeXt stage change: LayerNorm2d, then the 2x2 / stride 2 conv as a dense GEMM with K = 4 C
+  LnW ln;
+  LinearW conv;  // [2 C][(kh 2 + kw) C + c] (convnext_pack.hpp)
+};
+
 struct PackedModel {
   int family = 0;
   Prec prec = Prec::F16;
@@ -101,6 +113,15 @@ struct PackedModel {
   int patch = 16, npatch = 196;
   LinearW patch_proj, head;
   size_t cls = 0, vpos = 0;
+
+  // ConvNeXt: the 4x4 / stride 4 stem as a linear layer over patchify's rows + its LayerNorm; the blocks in
+  // order (stage_blocks counts them per stage, cn_dims holds the stage widths); the downsample in front of
+  // stages 1..; classifier.0 (final_ln) and classifier.2 (fc; classes, feat as for ResNet)
+  LinearW cn_stem;
+  LnW cn_stem_ln;
+  std::vector<int> cn_dims;
+  std::vector<CnBlock> cn_blocks;
+  std::vector<CnDown> cn_down;
 
   std::string desc;
   uint64_t digest = 0;  // FNV-1a 64 of the blob

@@ -5,12 +5,15 @@
 #include <stdexcept>
 #include <utility>
 
+#include "convnext_pack.hpp"
 #include "resample.hpp"
 
 namespace spi {
 
 namespace {
-bool image_family(const PackedModel& m) { return m.family == SPI_FAMILY_RESNET || m.family == SPI_FAMILY_VIT; }
+bool image_family(const PackedModel& m) {
+  return m.family == SPI_FAMILY_RESNET || m.family == SPI_FAMILY_VIT || m.family == SPI_FAMILY_CONVNEXT;
+}
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -241,6 +244,14 @@ GemmDesc linear_layer_desc(const LinearW& L, int M) {
   return d;
 }
 
+GemmDesc cn_gemm_desc(const LinearW& L, int M, Act act, bool residual, bool out_f32) {
+  GemmDesc d = linear_desc(L, M, L.k, L.n);
+  d.act = act;
+  d.ldr = residual ? L.n : 0;
+  d.out_f32 = out_f32;
+  return d;
+}
+
 bool pooled_fc(const PackedModel& m, int hw) { return hw > 0 && hw <= 64 && (!m.split || m.feat % 32 == 0); }
 
 GemmDesc pooled_fc_desc(const PackedModel& m, int B, int hw) {
@@ -306,9 +317,50 @@ struct FlopsVisitor {
   void conv_pair(int B, const RnConv& k0, const RnConv& k1) { add(B, k0), add(B, k1); }
   void tail(int B, int, int, bool) { f += 2.0 * B * m.fc.n * m.fc.k; }
 };
+
+
+// The GEMMs of the ConvNeXt graph, each as the desc Model::body_convnext builds for it: on_gemm(step name,
+// layer, desc).  Also the largest map kept in an activation slot, in elements, and the depthwise FLOPs.
+template <class F>
+struct CnGemmVisitor {
+  const PackedModel& m;
+  F on_gemm;
+  size_t amax = 0, hmax = 0;  // ... and the largest hidden (fc1 output) rows
+  double dw_flops = 0;
+  void stored(int B, int H, int C) { amax = std::max(amax, (size_t)B * H * H * C); }
+  void stem(int B, int H, int) {
+    stored(B, H, m.cn_stem.n);
+    on_gemm("stem", m.cn_stem, cn_gemm_desc(m.cn_stem, B * H * H, Act::None, false, true));
+  }
+  void down(int B, int H, const CnDown& d, int, int) {
+    stored(B, H / 2, d.conv.n);
+    on_gemm("downsample", d.conv, cn_gemm_desc(d.conv, B * (H / 2) * (H / 2), Act::None, false, false));
+  }
+  void block(int B, int H, const CnBlock& k, int, int) {
+    dw_flops += 2.0 * kDwconvTaps * k.C * (double)H * H * B;
+    hmax = std::max(hmax, (size_t)B * H * H * k.fc1.n);
+    on_gemm("fc1", k.fc1, cn_gemm_desc(k.fc1, B * H * H, Act::Gelu, false, false));
+    on_gemm("fc2", k.fc2, cn_gemm_desc(k.fc2, B * H * H, Act::None, true, false));
+  }
+  void tail(int B, int, int) { on_gemm("fc", m.fc, linear_layer_desc(m.fc, B)); }
+};
+
+template <class F>
+CnGemmVisitor<F> walk_convnext_gemms(const PackedModel& m, int B, F&& f) {
+  CnGemmVisitor<F> v{m, std::forward<F>(f)};
+  walk_convnext(m, B, v);
+  return v;
+}
 }  // namespace
 
 double model_flops(const PackedModel& m, int64_t B) {
+  if (m.family == SPI_FAMILY_CONVNEXT) {
+    double f = 0;
+    const auto v = walk_convnext_gemms(m, (int)B, [&](const char*, const LinearW&, const GemmDesc& d) {
+      f += 2.0 * d.M * d.N * (double)d.K;
+    });
+    return f + v.dw_flops;
+  }
   if (m.family == SPI_FAMILY_RESNET) {
     FlopsVisitor v(m);
     walk_resnet(m, (int)B, v);
@@ -428,6 +480,17 @@ WorkspacePlan workspace_plan(const PackedModel& m, const ReplicaOptions& o) {
     sz[kVtLogits] = logits;
     sz[kVtResized] = resized;
   }
+  if (m.family == SPI_FAMILY_CONVNEXT) {
+    const auto v = walk_convnext_gemms(m, (int)B, [&](const char*, const LinearW& L, const GemmDesc& d) { slabs(d, L.prec); });
+    const size_t H0 = m.image / 4;
+    sz.assign(kCnBufs, 0);
+    sz[kCnPatches] = B * H0 * H0 * m.cn_stem.k * es;
+    sz[kCnAct0] = sz[kCnAct1] = sz[kCnLn] = v.amax * es;
+    sz[kCnHidden] = std::max(v.hmax * es, B * H0 * H0 * m.cn_stem.n * 4);  // the hidden rows; the stem's fp32 rows
+    sz[kCnPooled] = B * m.feat * es;
+    sz[kCnLogits] = logits;
+    sz[kCnResized] = resized;
+  }
   if (m.family == SPI_FAMILY_BERT || m.family == SPI_FAMILY_VIT)
     walk_transformer_gemms(m, (int)B, m.seq, [&](const char*, const LinearW& L, const GemmDesc& d) { slabs(d, L.prec); });
   // Split-K slabs: choose_plan only splits grids of < 128 tiles into <= 512 +
@@ -449,6 +512,8 @@ int plan_check(const PackedModel& m, const ReplicaOptions& o, int B, int S) {
   };
   if (m.family == SPI_FAMILY_RESNET) {
     walk_resnet_gemms(m, B, [&](const char* name, const GemmDesc& d, Prec prec, const GemmDesc* d1) { hold(name, d, prec, d1); });
+  } else if (m.family == SPI_FAMILY_CONVNEXT) {
+    walk_convnext_gemms(m, B, [&](const char* name, const LinearW& L, const GemmDesc& d) { hold(name, d, L.prec, nullptr); });
   } else if (m.family == SPI_FAMILY_BERT || m.family == SPI_FAMILY_VIT) {
     if (m.family == SPI_FAMILY_BERT && (S < 1 || S > m.seq)) throw std::runtime_error("plan_check: sequence outside 1 .. seq");
     walk_transformer_gemms(m, B, S, [&](const char* name, const LinearW& L, const GemmDesc& d) { hold(name, d, L.prec, nullptr); });

@@ -41,6 +41,11 @@ enum BertBuf { kBtHidden, kBtHidden16, kBtQkv, kBtCtx, kBtAttn, kBtFfn, kBtStats
 // ViT: patches (plus vit_patches_tail_bytes, zeroed, where the rows are ragged); projected patches f32; residual stream x f32 (fold: two fp16 planes); LN output; qkv;
 // ctx; mlp hidden; the LayerNorm'd class-token rows; the LayerNorm-fold row statistics of x.
 enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, kVtStats, kVtLogits, kVtResized, kVtBufs };
+// ConvNeXt: the stem's 4x4 patches; two activation slots (NHWC maps in the compute type) the blocks and
+// downsamples alternate between; the LayerNorm'd rows (a block's dwconv + LN output, a downsample's
+// space-to-depth rows); the 4C hidden rows (first the stem GEMM's fp32 output); the pooled + LayerNorm'd
+// features; logits scratch and resized image as above.
+enum CnBuf { kCnPatches, kCnAct0, kCnAct1, kCnLn, kCnHidden, kCnPooled, kCnLogits, kCnResized, kCnBufs };
 
 // ---------------------------------------------------------------------------
 // I/O contract
@@ -158,6 +163,37 @@ void walk_resnet(const PackedModel& m, int B, V&& v) {
     cur = o;
   }
   v.tail(B, cur, H * H, pooled_fc(m, H * H));
+}
+
+// ---------------------------------------------------------------------------
+// The ConvNeXt graph, walked once: Model::body_convnext launches from it, model_flops counts it,
+// workspace_plan and plan_check size and hold its GEMMs.  H: the side of the square map; in / out: CnBuf slots.
+// ---------------------------------------------------------------------------
+// A GEMM of the ConvNeXt forward over M dense rows: compute-type output (fp32 for the stem, whose LayerNorm
+// reads it), with the block input as a compute-type residual for a block's second Linear.
+GemmDesc cn_gemm_desc(const LinearW& L, int M, Act act, bool residual, bool out_f32);
+// The visitor V sees, in launch order:
+//   v.stem(B, H, out)            stem GEMM on kCnPatches (fp32 into kCnHidden) + LayerNorm into slot out
+//   v.down(B, H, d, in, out)     LayerNorm + space to depth of the H x H map in slot in (into kCnLn), GEMM into out
+//   v.block(B, H, blk, in, out)  dwconv + LN (in -> kCnLn), Linear + GELU (-> kCnHidden), Linear + residual in -> out
+//   v.tail(B, H, in)             mean over the map + LayerNorm into kCnPooled (the FC is the epilogue's)
+template <class V>
+void walk_convnext(const PackedModel& m, int B, V&& v) {
+  int H = m.image / 4, cur = kCnAct0;
+  v.stem(B, H, cur);
+  size_t blk = 0;
+  for (size_t stage = 0; stage < m.stage_blocks.size(); ++stage) {
+    if (stage > 0) {
+      v.down(B, H, m.cn_down[stage - 1], cur, cur ^ (kCnAct0 ^ kCnAct1));
+      cur ^= kCnAct0 ^ kCnAct1;
+      H /= 2;
+    }
+    for (int i = 0; i < m.stage_blocks[stage]; ++i, ++blk) {
+      v.block(B, H, m.cn_blocks[blk], cur, cur ^ (kCnAct0 ^ kCnAct1));
+      cur ^= kCnAct0 ^ kCnAct1;
+    }
+  }
+  v.tail(B, H, cur);
 }
 
 // ---------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/spi_ops.h"
+#include "convnext_pack.hpp"
 #include "gconv.hpp"
 #include "gemm_plan.hpp"
 #include "ln_fold_pack.hpp"
@@ -300,6 +301,55 @@ int spi_op_conv2d_grouped(const void* x, int32_t B, int32_t H, int32_t W, int32_
     if (reinterpret_cast<uintptr_t>(p) & 15) return fail("grouped conv: 16-byte aligned x, W_packed, y and bias");
   return guarded([&] {
     spi::conv_group(x, Wp, bias, y, B, H, W, C, groups, stride, act == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+// ---- ConvNeXt kernels (dwconv_ln.hip, convnext_pack.hpp) ----
+
+int spi_op_dwconv7_pack_weight(int32_t precision, const float* w, int32_t C, void* dst) {
+  if ((precision != 0 && precision != 1) || !w || !dst) return fail("invalid dwconv7 pack arguments");
+  if (!spi::dwconv7_supported(C)) return fail("dwconv7: C must be a multiple of 32 from 32 to 1536");
+  if (precision == 1)
+    spi::dwconv7_pack_into(static_cast<_Float16*>(dst), w, C);
+  else
+    spi::dwconv7_pack_into(static_cast<float*>(dst), w, C);
+  return 0;
+}
+
+int spi_op_dwconv7_ln(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, const void* Wp,
+                      const float* bias, const float* gamma, const float* beta, float eps, void* y, void* stream) {
+  if (precision != 0 && precision != 1) return fail("dwconv7_ln: precision 0 (fp32) or 1 (fp16)");
+  if (!x || !Wp || !bias || !gamma || !beta || !y) return fail("dwconv7_ln: null x, w_packed, bias, gamma, beta or y");
+  return guarded([&] {
+    spi::dwconv7_ln(x, Wp, bias, gamma, beta, y, B, H, W, C, eps, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_ln_space_to_depth(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C,
+                             const float* gamma, const float* beta, float eps, void* y, void* stream) {
+  if (precision != 0 && precision != 1) return fail("ln_space_to_depth: precision 0 (fp32) or 1 (fp16)");
+  if (!x || !gamma || !beta || !y) return fail("ln_space_to_depth: null x, gamma, beta or y");
+  return guarded([&] {
+    spi::ln_space_to_depth(x, y, gamma, beta, B, H, W, C, eps, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_s2d_pack_weight(const float* w, int32_t N, int32_t C, float* dst) {
+  if (!w || !dst) return fail("invalid s2d pack arguments");
+  if (N < 1 || N > 65536 || C < 1 || C > 65536) return fail("s2d pack: 1 <= N, C <= 65536");
+  spi::s2d_permute_weight(w, N, C, dst);
+  return 0;
+}
+
+int spi_op_ln_rows(int32_t precision, const void* x, int32_t x_f32, int32_t rows, int32_t C, int32_t pool_hw,
+                   const float* gamma, const float* beta, float eps, void* y, void* stream) {
+  if (precision != 0 && precision != 1) return fail("ln_rows: precision 0 (fp32) or 1 (fp16)");
+  if (!x || !gamma || !beta || !y) return fail("ln_rows: null x, gamma, beta or y");
+  return guarded([&] {
+    spi::ln_rows(x, x_f32 != 0, y, gamma, beta, rows, C, pool_hw, eps, precision == 1, static_cast<hipStream_t>(stream));
     return check_launch();
   });
 }

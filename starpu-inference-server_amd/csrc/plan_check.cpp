@@ -3,12 +3,13 @@
 // workspace, walks the forward at every batch 1 .. max_batch against it (plan_check: the checks of each
 // launch, with no launch) and holds one accepted and one refused task against the I/O contract; prints
 // one line per model; then the BERT with task heads (SPI_BERT_HEAD_*): output counts up to five, their byte
-// sizes, the pooled vector's place in the workspace.  Built with the address and undefined-behaviour
+// sizes, the pooled vector's place in the workspace; then one ConvNeXt walk.  Built with the address and undefined-behaviour
 // sanitizers, no HIP.
 #include <cstdio>
 #include <deque>
 #include <initializer_list>
 #include <stdexcept>
+#include <utility>
 
 #include "model_plan.hpp"
 
@@ -219,6 +220,48 @@ int main() {
     std::printf("bert_d128|fp16|%s| %d outputs, %d labels, flops(3) %.0f, class-token buffer %zu bytes, %d steps fit, %s\n",
                 h.name, spi::num_outputs(m, o), m.num_labels, spi::model_flops(m, 3), plan.bytes[spi::kBtCls], steps,
                 spi::replica_desc(m, o).c_str());
+  }
+  // ConvNeXt ([1, 1, 2, 1] blocks over 96 .. 768 channels at 64 x 64): both served precisions, every batch walked
+  // against the planned workspace, the I/O contract of an image family, and the two refused precisions.
+  Tensors cn;
+  cn.add("features.0.0.weight", {96, 3, 4, 4}), cn.add("features.0.0.bias", {96}), cn.norm("features.0.1", 96, false);
+  const int depths[4] = {1, 1, 2, 1};
+  for (int st = 0, c = 96; st < 4; ++st, c *= 2) {
+    if (st > 0) {
+      const std::string d = "features." + std::to_string(2 * st) + ".";
+      cn.norm(d + "0", c / 2, false), cn.add(d + "1.weight", {c, c / 2, 2, 2}), cn.add(d + "1.bias", {c});
+    }
+    for (int i = 0; i < depths[st]; ++i) {
+      const std::string b = "features." + std::to_string(2 * st + 1) + "." + std::to_string(i) + ".";
+      cn.add(b + "block.0.weight", {c, 1, 7, 7}), cn.add(b + "block.0.bias", {c}), cn.norm(b + "block.2", c, false);
+      cn.linear(b + "block.3", 4 * c, c), cn.linear(b + "block.5", c, 4 * c), cn.add(b + "layer_scale", {c, 1, 1});
+    }
+  }
+  cn.norm("classifier.0", 768, false), cn.linear("classifier.2", 10, 768);
+  for (const auto& pr : {std::make_pair("fp16", (int)SPI_PREC_F16), std::make_pair("fp32", (int)SPI_PREC_F32),
+                         std::make_pair("fp16x3", (int)SPI_PREC_F16X3), std::make_pair("fp16m", (int)SPI_PREC_F16M)}) {
+    spi_model_config cfg{};
+    cfg.family = SPI_FAMILY_AUTO, cfg.precision = pr.second, cfg.max_batch = 8, cfg.image_size = 64;
+    const bool served = pr.second == SPI_PREC_F16 || pr.second == SPI_PREC_F32;
+    try {
+      const spi::PackedModel m = spi::pack_model(cfg, cn.t.data(), (int)cn.t.size());
+      spi::ReplicaOptions o;
+      o.resize_short = 2 * m.image;
+      const spi::WorkspacePlan plan = spi::workspace_plan(m, o);
+      int steps = 0;
+      for (int B = 1; B <= m.max_batch; ++B) steps += spi::plan_check(m, o, B, 0);
+      const size_t out = (size_t)2 * m.classes * 4;
+      const bool ok = served && m.family == SPI_FAMILY_CONVNEXT && plan.bytes.size() == (size_t)spi::kCnBufs &&
+                      accepted(m, o, SPI_DTYPE_F32, 2, {3, 64, 64}, 4, out) && !accepted(m, o, SPI_DTYPE_F32, 2, {3, 63, 64}, 4, out) &&
+                      accepted(m, o, SPI_DTYPE_U8, 2, {100, 75, 3}, 1, out);
+      if (!ok) std::fprintf(stderr, "convnext|%s: family, plan or check_io are not the expected ones\n", pr.first), rc = 1;
+      std::printf("convnext|%s| flops(1) %.0f flops(3) %.0f, %zu buffers, slabs %zu (planned %zu), %d steps fit, %s\n", pr.first,
+                  spi::model_flops(m, 1), spi::model_flops(m, 3), plan.bytes.size(), plan.partial_floats, plan.partial_planned,
+                  steps, spi::replica_desc(m, o).c_str());
+    } catch (const std::runtime_error& e) {
+      if (served) std::fprintf(stderr, "convnext|%s: %s\n", pr.first, e.what()), rc = 1;
+      else std::printf("convnext|%s| refused: %s\n", pr.first, e.what());
+    }
   }
   return rc;
 }

@@ -76,6 +76,22 @@ void qkv_attn_reload_env();   // SPI_QKV_HP
 void conv_group(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C, int groups,
                 int stride, bool relu, hipStream_t s);
 
+// ConvNeXt (dwconv_ln.hip; layouts and the supported C: convnext_pack.hpp).  Depthwise 7x7 / pad 3 / stride 1 conv
+// + bias + LayerNorm over channels, one launch: x NHWC [B][H][W][C] -> y [B H W][C] = LN(dwconv(x) + bias) * gamma +
+// beta, x / w / y in the compute type, w [49][C] from dwconv7_pack_into, bias / gamma / beta fp32 [C]; fp32
+// accumulation and two-pass fp32 statistics in both types.  C % 32 == 0, 32 .. 1536; every pointer 16-byte
+// aligned.  Throws std::invalid_argument outside that.
+void dwconv7_ln(const void* x, const void* w, const float* bias, const float* gamma, const float* beta, void* y, int B,
+                int H, int W, int C, float eps, bool f16, hipStream_t s);
+// LayerNorm over C of `rows` rows (same C set): x fp32 (x_f32) or the compute type, y the compute type.
+// pool_hw > 0: output row r is LN(mean of input rows r pool_hw .. (r + 1) pool_hw - 1) -- avgpool + LayerNorm.
+void ln_rows(const void* x, bool x_f32, void* y, const float* gamma, const float* beta, int rows, int C, int pool_hw,
+             float eps, bool f16, hipStream_t s);
+// LayerNorm of each pixel of x NHWC [B][H][W][C] (even H, W) written into the dense row of its 2x2 / stride 2
+// output pixel: y [B (H/2) (W/2)][4 C], columns ((h & 1) 2 + (w & 1)) C + c (s2d_permute_weight's order).
+void ln_space_to_depth(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W, int C,
+                       float eps, bool f16, hipStream_t s);
+
 // The kind of an image task's input buffer (SrcKind) and its 8-bit input transform (InputXf): image_src.hpp.
 // The transform of one pixel of channel c.  Contraction is switched off for the two operations:
 // HIP compiles with -ffp-contract=fast, under which __fmul_rn / __fadd_rn are a plain * and + that

@@ -204,6 +204,50 @@ def conv2d_grouped(x_nhwc, W_packed, groups, stride, bias=None, act=None, out=No
     return out
 
 
+# ---- ConvNeXt kernels (spi_ops.h: spi_op_dwconv7_ln, spi_op_ln_space_to_depth, spi_op_ln_rows) ----
+
+
+def pack_weight_dwconv7(prec, w, device="cuda") -> torch.Tensor:
+    """torch depthwise weight [C][1][7][7] fp32 -> [49][C] device tensor of prec's type ("fp16" / "fp32")."""
+    w = np.ascontiguousarray(np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float32))
+    c = w.shape[0]
+    host = np.empty((49, c), dtype=np.float16 if prec == "fp16" else np.float32)
+    _check(lib.spi_op_dwconv7_pack_weight(PREC[prec], w.ctypes.data, c, host.ctypes.data))
+    return torch.from_numpy(host).to(device)
+
+
+def dwconv7_ln(prec, x_nhwc, w_packed, bias, gamma, beta, eps, out, stream=None):
+    """out [B H W][C] = LayerNorm(depthwise 7x7 conv(x_nhwc, pad 3) + bias) * gamma + beta, one launch."""
+    B, H, W_, c = x_nhwc.shape
+    _check(lib.spi_op_dwconv7_ln(PREC[prec], _ptr(x_nhwc), B, H, W_, c, _ptr(w_packed), _ptr(bias), _ptr(gamma),
+                                 _ptr(beta), eps, _ptr(out), _stream(stream)))
+    return out
+
+
+def s2d_weight(w) -> np.ndarray:
+    """A 2x2 / stride 2 conv weight [N][C][2][2] -> the [N][4 C] matrix over ln_space_to_depth's rows."""
+    w = np.ascontiguousarray(np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float32))
+    out = np.empty((w.shape[0], 4 * w.shape[1]), np.float32)
+    _check(lib.spi_op_s2d_pack_weight(w.ctypes.data, w.shape[0], w.shape[1], out.ctypes.data))
+    return out
+
+
+def ln_space_to_depth(prec, x_nhwc, gamma, beta, eps, out, stream=None):
+    """LayerNorm over C of each pixel, written into out [B (H/2) (W/2)][4 C] (s2d_weight's column order)."""
+    B, H, W_, c = x_nhwc.shape
+    _check(lib.spi_op_ln_space_to_depth(PREC[prec], _ptr(x_nhwc), B, H, W_, c, _ptr(gamma), _ptr(beta), eps, _ptr(out),
+                                        _stream(stream)))
+    return out
+
+
+def ln_rows(prec, x, rows, c, gamma, beta, eps, out, pool_hw=0, stream=None):
+    """out [rows][C] (prec's type) = LayerNorm of x's rows, x fp32 or prec's type by its dtype; pool_hw > 0:
+    of the mean of each pool_hw consecutive rows of x."""
+    _check(lib.spi_op_ln_rows(PREC[prec], _ptr(x), int(x.dtype == torch.float32), rows, c, pool_hw, _ptr(gamma),
+                              _ptr(beta), eps, _ptr(out), _stream(stream)))
+    return out
+
+
 def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None, out=None, head_dim=64):
     """ctx [B S][D] of packed qkv [B S][3 D], D = heads * head_dim (32 or 64); out: the buffer to write
     (default: a fresh one).  prec may be the integer precision code itself."""

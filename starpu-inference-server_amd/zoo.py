@@ -266,6 +266,93 @@ def vit_l_16(seed: int = 0, image: int = 224, **kw) -> VisionTransformer:
 
 
 # ---------------------------------------------------------------------------
+# ConvNeXt (torchvision.models.convnext naming)
+# ---------------------------------------------------------------------------
+class LayerNorm2d(nn.LayerNorm):
+    def forward(self, x):
+        x = x.permute(0, 2, 3, 1)
+        x = nn.functional.layer_norm(x, self.normalized_shape, self.weight, self.bias, self.eps)
+        return x.permute(0, 3, 1, 2)
+
+
+class Permute(nn.Module):
+    def __init__(self, dims):
+        super().__init__()
+        self.dims = list(dims)
+
+    def forward(self, x):
+        return torch.permute(x, self.dims)
+
+
+class CNBlock(nn.Module):
+    def __init__(self, dim: int, layer_scale: float = 1e-6):
+        super().__init__()
+        self.block = nn.Sequential(
+            nn.Conv2d(dim, dim, 7, padding=3, groups=dim, bias=True), Permute([0, 2, 3, 1]),
+            nn.LayerNorm(dim, eps=1e-6), nn.Linear(dim, 4 * dim), nn.GELU(), nn.Linear(4 * dim, dim),
+            Permute([0, 3, 1, 2]))
+        self.layer_scale = nn.Parameter(torch.ones(dim, 1, 1) * layer_scale)
+
+    def forward(self, x):  # eval: stochastic depth is the identity
+        return x + self.layer_scale * self.block(x)
+
+
+class ConvNeXt(nn.Module):
+    def __init__(self, depths: Sequence[int], dims: Sequence[int], num_classes: int = 1000):
+        super().__init__()
+        layers = [nn.Sequential(nn.Conv2d(3, dims[0], 4, 4), LayerNorm2d(dims[0], eps=1e-6))]
+        for i, (depth, dim) in enumerate(zip(depths, dims)):
+            if i > 0:
+                layers.append(nn.Sequential(LayerNorm2d(dims[i - 1], eps=1e-6), nn.Conv2d(dims[i - 1], dim, 2, 2)))
+            layers.append(nn.Sequential(*[CNBlock(dim) for _ in range(depth)]))
+        self.features = nn.Sequential(*layers)
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+        self.classifier = nn.Sequential(LayerNorm2d(dims[-1], eps=1e-6), nn.Flatten(1), nn.Linear(dims[-1], num_classes))
+
+    def forward(self, x):
+        return self.classifier(self.avgpool(self.features(x)))
+
+
+def convnext(depths: Sequence[int], dims: Sequence[int], image: int = 224, num_classes: int = 1000,
+             seed: int = 0) -> ConvNeXt:
+    """ConvNeXt with seeded random weights (image only documents the size the model is meant for).
+    torchvision initialises layer_scale to 1e-6 and the weights to N(0, 0.02^2), which would hide every
+    block behind its residual: here layer_scale is drawn from U(0.05, 0.3), conv and linear weights from
+    N(0, 1 / fan_in) with biases N(0, 0.05^2), and the LayerNorm gains and biases are re-drawn as vit()
+    does, so that a wrong block shows in the logits."""
+    torch.manual_seed(seed)
+    model = ConvNeXt(depths, dims, num_classes)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, (nn.Conv2d, nn.Linear)):
+                fan_in = m.weight[0].numel()
+                m.weight.normal_(std=fan_in ** -0.5)
+                m.bias.normal_(std=0.05)
+            elif isinstance(m, nn.LayerNorm):
+                m.weight.copy_(1.0 + 0.1 * torch.randn_like(m.weight))
+                m.bias.copy_(0.05 * torch.randn_like(m.bias))
+            elif isinstance(m, CNBlock):
+                m.layer_scale.uniform_(0.05, 0.3)
+    return model.eval()
+
+
+def convnext_tiny(seed: int = 0, image: int = 224, **kw) -> ConvNeXt:
+    return convnext([3, 3, 9, 3], [96, 192, 384, 768], image, seed=seed, **kw)
+
+
+def convnext_small(seed: int = 0, image: int = 224, **kw) -> ConvNeXt:
+    return convnext([3, 3, 27, 3], [96, 192, 384, 768], image, seed=seed, **kw)
+
+
+def convnext_base(seed: int = 0, image: int = 224, **kw) -> ConvNeXt:
+    return convnext([3, 3, 27, 3], [128, 256, 512, 1024], image, seed=seed, **kw)
+
+
+def convnext_large(seed: int = 0, image: int = 224, **kw) -> ConvNeXt:
+    return convnext([3, 3, 27, 3], [192, 384, 768, 1536], image, seed=seed, **kw)
+
+
+# ---------------------------------------------------------------------------
 # BERT (HF transformers BertModel, wrapped like models/import_bert-base-uncased.py)
 # ---------------------------------------------------------------------------
 class BertWrapper(nn.Module):
@@ -481,6 +568,10 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
         "wide_resnet50_2": wide_resnet50_2,
         "wide_resnet101_2": wide_resnet101_2,
         "vit_l_16": vit_l_16,
+        "convnext_tiny": convnext_tiny,
+        "convnext_small": convnext_small,
+        "convnext_base": convnext_base,
+        "convnext_large": convnext_large,
         "bert-base-uncased": bert_base,
         "bert_base": bert_base,
         "minilm_l6": minilm_l6,
@@ -497,6 +588,7 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
 # TorchScript names a class by its Python module path; this package's directory
 # name is not an identifier, so give the zoo's modules a loadable qualified name
 # (a traced/scripted model must round-trip through .pt like the reference's).
-for _cls in (BasicBlock, Bottleneck, ResNet, MLPBlock, EncoderBlock, Encoder, VisionTransformer, BertWrapper,
+for _cls in (BasicBlock, Bottleneck, ResNet, MLPBlock, EncoderBlock, Encoder, VisionTransformer, LayerNorm2d, Permute,
+             CNBlock, ConvNeXt, BertWrapper,
              BertTupleWrapper, BertSegmentsWrapper, BertHeadWrapper, AddConstant):
     _cls.__module__ = "spi_zoo"
