@@ -240,7 +240,8 @@ enum spi_family {
   SPI_FAMILY_BERT = 2,   /* HF BertModel naming, returns last_hidden_state */
   SPI_FAMILY_VIT = 3,    /* torchvision vit_*_16 naming */
   SPI_FAMILY_AFFINE = 4, /* y = x * scale + shift (toy models of the reference tests) */
-  SPI_FAMILY_CONVNEXT = 5 /* torchvision convnext_* naming; SPI_PREC_F16 and SPI_PREC_F32 */
+  SPI_FAMILY_CONVNEXT = 5, /* torchvision convnext_* naming; SPI_PREC_F16 and SPI_PREC_F32 */
+  SPI_FAMILY_SWIN = 6      /* torchvision swin_t / _s / _b naming (v1 blocks); SPI_PREC_F16 and SPI_PREC_F32 */
 };
 
 /* SPI_PREC_F16X3: split fp16 -- fp32 activations, each MFMA operand split into

@@ -403,6 +403,30 @@ int spi_op_s2d_pack_weight(const float* w_host, int32_t N, int32_t C, float* dst
 int spi_op_ln_rows(int32_t precision, const void* x, int32_t x_f32, int32_t rows, int32_t C, int32_t pool_hw,
                    const float* gamma, const float* beta, float eps, void* y, void* stream);
 
+/* ---- Swin kernels (window_attn.hip, s2d_ln in dwconv_ln.hip): precision 0 (fp32) or 1 (fp16) is the type of
+ * qkv / ctx / x / y.  A refused call returns non-zero, launches nothing and leaves its reason in spi_last_error(). ---- */
+/* relative_position_bias_table [(2 ws - 1)^2][heads] (host fp32) -> the attention kernel's bias, host fp32
+ * [heads][16][64][4]: value (head, query q, key k) of a window's ws^2 tokens, table row
+ * (qy - ky + ws - 1)(2 ws - 1) + (qx - kx + ws - 1), lies at ((head 16 + k / 4) 64 + q) 4 + k % 4; keys
+ * ws^2 .. 63 hold -inf, query slots ws^2 .. 63 hold 0.  The index is recomputed from ws.  2 <= ws <= 8. */
+int spi_op_window_bias_pack(const float* table_host, int32_t window, int32_t heads, float* dst_host);
+/* Shifted-window attention, head_dim 32: qkv [B H W][3 C] (q | k | v, C = 32 heads) and ctx [B H W][C] in NHWC
+ * pixel order; window (wy, wx), token (ty, tx) is the pixel ((wy ws + ty + shift) mod H, (wx ws + tx + shift)
+ * mod W) (torch.roll by -shift, then the window partition; ctx goes back to that pixel).  Scores
+ * (q scale) k^T + rel_bias + mask: rel_bias the device copy of spi_op_window_bias_pack's output, the mask -100
+ * where the two tokens' shift regions differ (region of rolled coordinate p on an axis of length L: 0 for
+ * p < L - ws, 1 for p < L - shift, else 2), computed in the kernel.  Supported: head_dim 32, window 2 .. 8, H and W
+ * multiples of it, 0 <= shift < window, heads <= 65535, B (H / ws)(W / ws) < 2^31, 16-byte aligned qkv, ctx and
+ * rel_bias. */
+int spi_op_window_attention(int32_t precision, const void* qkv, const float* rel_bias, void* ctx, int32_t B, int32_t H,
+                            int32_t W, int32_t heads, int32_t head_dim, int32_t window, int32_t shift, float scale,
+                            void* stream);
+/* Patch merging's rows: y [B (H/2) (W/2)][4 C] = LayerNorm over 4 C (gamma, beta fp32 [4 C]) of the row gathered
+ * from x NHWC [B][H][W][C], pixel (2 i + dy, 2 j + dx) at columns (dx 2 + dy) C.  C a multiple of 32, 4 C <= 2048,
+ * even H and W, 16-byte aligned pointers. */
+int spi_op_s2d_ln(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* gamma,
+                  const float* beta, float eps, void* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,7 +49,7 @@ SPI_ERR_MODEL = 6
 SPI_ERR_CPU_FORWARD = 7
 
 # enum spi_family / spi_precision
-FAMILY_AUTO, FAMILY_RESNET, FAMILY_BERT, FAMILY_VIT, FAMILY_AFFINE, FAMILY_CONVNEXT = 0, 1, 2, 3, 4, 5
+FAMILY_AUTO, FAMILY_RESNET, FAMILY_BERT, FAMILY_VIT, FAMILY_AFFINE, FAMILY_CONVNEXT, FAMILY_SWIN = 0, 1, 2, 3, 4, 5, 6
 PREC_F32, PREC_F16, PREC_F16X3, PREC_F16M = 0, 1, 2, 3
 
 
@@ -262,6 +262,11 @@ _PROTOS = {
     "spi_op_s2d_pack_weight": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "spi_op_ln_rows": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                  C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "spi_op_window_bias_pack": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "spi_op_window_attention": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "spi_op_s2d_ln": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.c_float, C.c_void_p, C.c_void_p]),
     "spi_op_avgpool_fc": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "spi_op_stem_pool_bytes": (C.c_size_t, []),

@@ -1,6 +1,7 @@
 // The ConvNeXt kernels (gfx950): depthwise 7x7 conv + bias + LayerNorm over channels in one pass over an
 // NHWC map, and the two row kernels beside it -- LayerNorm of rows of any C % 32 == 0 (optionally behind a
-// mean over a map's rows) and LayerNorm into the space-to-depth rows of a 2x2 / stride 2 conv.
+// mean over a map's rows) and LayerNorm into the space-to-depth rows of a 2x2 / stride 2 conv -- and Swin's
+// patch merging row kernel s2d_ln (gather the four pixels, then LayerNorm over 4 C).
 //
 // dwconv7_ln.  Every channel is its own 49-tap filter: no contraction across channels, nothing for the
 // MFMA, 49 FMAs per output on the VALU and the map read once.  A workgroup of 256 threads owns a TH x TW
@@ -20,6 +21,7 @@
 #include "convnext_pack.hpp"
 #include "row_util.hpp"
 #include "spi_kernels.hpp"
+#include "swin_pack.hpp"
 
 namespace spi {
 namespace {
@@ -232,6 +234,44 @@ __global__ __launch_bounds__(256) void ln_rows_c_kernel(const TI* __restrict__ x
       [&](int c, const float(&o)[4]) { store4(dst + c, o); });
 }
 
+// Swin's patch merging in front of its Linear: one wave per output row (b, i, j) of y [B (H/2) (W/2)][4 C].
+// The row is gathered from its four pixels into registers -- pixel (2 i + dy, 2 j + dx) at columns
+// (dx 2 + dy) C .., torchvision's cat(x[0::2, 0::2], x[1::2, 0::2], x[0::2, 1::2], x[1::2, 1::2]) -- and then
+// normalised over all 4 C columns (two-pass fp32 statistics, gain and bias of 4 C).  4 C <= 2048: eight float4
+// per lane.  C % 32 == 0, so a float4 never straddles two pixels.
+template <typename T>
+__global__ __launch_bounds__(256) void s2d_ln_kernel(const T* __restrict__ x, T* __restrict__ y,
+                                                     const float* __restrict__ g, const float* __restrict__ b, int rows,
+                                                     int H, int W, int C, float eps) {
+  constexpr int NV = kS2dMaxRow / 256;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int W2 = W / 2, H2 = H / 2;
+  const int j2 = row % W2, i2 = (row / W2) % H2, img = row / (W2 * H2);
+  const T* x00 = x + (((size_t)img * H + 2 * i2) * W + 2 * j2) * C;
+  float4 v[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int c = (lane + 64 * j) * 4;
+    v[j] = float4{0.f, 0.f, 0.f, 0.f};
+    if (c >= 4 * C) continue;
+    const int q = c / C;  // dx 2 + dy
+    v[j] = load4(x00 + ((size_t)(q & 1) * W + (q >> 1)) * C + (c - q * C));
+  }
+  T* dst = y + (size_t)row * 4 * C;
+  ln_row_c(
+      4 * C, lane, g, b, eps,
+      [&](int c) {
+        float4 r = v[0];
+#pragma unroll
+        for (int j = 1; j < NV; ++j)
+          if (c >= 256 * j) r = v[j];
+        return r;
+      },
+      [&](int c, const float(&o)[4]) { store4(dst + c, o); });
+}
+
 void check_rows(const char* what, const void* x, const void* y, const float* g, const float* b, int C) {
   if (!dwconv7_supported(C)) throw std::invalid_argument(std::string(what) + ": C must be a multiple of 32 from 32 to 1536");
   if (!aligned(x, 16) || !aligned(y, 16) || !aligned(g, 16) || !aligned(b, 16))
@@ -296,6 +336,21 @@ void ln_space_to_depth(const void* x, void* y, const float* gamma, const float* 
     using T = decltype(t);
     SPI_LAUNCH((ln_rows_c_kernel<T, T>), dim3((rows + 3) / 4), dim3(256), 0, s, static_cast<const T*>(x),
                static_cast<T*>(y), gamma, beta, rows, C, 0, H, W, eps);
+  });
+}
+
+void s2d_ln(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W, int C, float eps,
+            bool f16, hipStream_t s) {
+  if (!s2d_ln_supported(C)) throw std::invalid_argument("s2d_ln: C must be a multiple of 32 with 4 C at most 2048");
+  if (!aligned(x, 16) || !aligned(y, 16) || !aligned(gamma, 16) || !aligned(beta, 16))
+    throw std::invalid_argument("s2d_ln: 16-byte aligned x, y, gamma and beta");
+  if (B < 1 || H < 2 || W < 2 || H % 2 || W % 2) throw std::invalid_argument("s2d_ln: B >= 1, even H and W");
+  if ((long long)B * H * W > 0x7fffffffLL) throw std::invalid_argument("s2d_ln: too many pixels");
+  const int rows = B * (H / 2) * (W / 2);
+  with_type(f16, [&](auto t) {
+    using T = decltype(t);
+    SPI_LAUNCH((s2d_ln_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, static_cast<const T*>(x), static_cast<T*>(y),
+               gamma, beta, rows, H, W, C, eps);
   });
 }
 

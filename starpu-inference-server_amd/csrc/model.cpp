@@ -5,6 +5,7 @@
 #include "convnext_pack.hpp"
 #include "gconv.hpp"
 #include "model.hpp"
+#include "swin_pack.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -598,6 +599,61 @@ void Model::body_convnext(Workspace& w, int B, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------
+// Swin plan: the launching visitor of walk_swin (model_plan.hpp)
+// ---------------------------------------------------------------------------
+void Model::body_swin(Workspace& w, int B, hipStream_t s) {
+  struct Launch {
+    Model& M;
+    Workspace& w;
+    hipStream_t s;
+    const PackedModel& m = M.m_;
+    void* const* buf = w.bufs.data();
+    const size_t es = m.f16 ? 2 : 4;
+    void ln(const void* x, bool x_f32, void* y, const LnW& l, int rows, int C) {
+      M.prof_op(s, [&] { return "ln_rows_c" + std::to_string(C); }, 0, (double)rows * C * ((x_f32 ? 4 : es) + es), [&] {
+        ln_rows(x, x_f32, y, M.ptr<float>(l.g), M.ptr<float>(l.b), rows, C, 0, m.eps, m.f16, s);
+      });
+    }
+    void gemm(const LinearW& L, int rows, Act act, const void* a, void* y, const void* res, bool out_f32 = false) {
+      M.run_gemm(L, cn_gemm_desc(L, rows, act, res != nullptr, out_f32), a, y, res, LnPtrs{}, w, s);
+    }
+    void stem(int B, int H, int out) {
+      const int rows = B * H * H;
+      gemm(m.sw_stem, rows, Act::None, buf[kSwPatches], buf[kSwHidden], nullptr, true);
+      ln(buf[kSwHidden], true, buf[out], m.sw_stem_ln, rows, m.sw_stem.n);
+    }
+    void merge(int B, int H, const SwMerge& g, int in, int out) {
+      const int C = g.red.k / 4, rows = B * (H / 2) * (H / 2);
+      M.prof_op(s, [&] { return "s2d_ln_c" + std::to_string(C); }, 0, 2.0 * B * H * H * C * es, [&] {
+        s2d_ln(buf[in], buf[kSwLn], M.ptr<float>(g.ln.g), M.ptr<float>(g.ln.b), B, H, H, C, m.eps, m.f16, s);
+      });
+      gemm(g.red, rows, Act::None, buf[kSwLn], buf[out], nullptr);
+    }
+    void block(int B, int H, const SwBlock& k, int shift, int x, int t) {
+      const int rows = B * H * H, C = k.C, ws = m.sw_window, N = ws * ws;
+      ln(buf[x], false, buf[kSwLn], k.ln1, rows, C);
+      gemm(k.qkv, rows, Act::None, buf[kSwLn], buf[kSwQkv], nullptr);
+      M.prof_op(s, [&] { return "window_attn_c" + std::to_string(C) + "_h" + std::to_string(H) + "_s" + std::to_string(shift); },
+                4.0 * N * kWinHeadDim * (double)rows * k.heads, 4.0 * rows * C * es, [&] {
+                  window_attention(buf[kSwQkv], M.ptr<float>(k.bias), buf[kSwCtx], B, H, H, k.heads, kWinHeadDim, ws, shift,
+                                   1.0f / std::sqrt((float)kWinHeadDim), m.f16, s);
+                });
+      gemm(k.proj, rows, Act::None, buf[kSwCtx], buf[t], buf[x]);
+      ln(buf[t], false, buf[kSwLn], k.ln2, rows, C);
+      gemm(k.fc1, rows, Act::Gelu, buf[kSwLn], buf[kSwHidden], nullptr);
+      gemm(k.fc2, rows, Act::None, buf[kSwHidden], buf[x], buf[t]);
+    }
+    void tail(int B, int H, int in) {
+      const int C = m.feat, hw = H * H;
+      ln(buf[in], false, buf[kSwLn], m.final_ln, B * hw, C);
+      if (pooled_fc(m, hw)) return;  // avgpool + fc run as one GEMM in the epilogue
+      M.prof_op(s, "avgpool", 0, (double)B * hw * C * es, [&] { avgpool_nhwc(buf[kSwLn], buf[kSwPooled], B, hw, C, m.f16, s, false); });
+    }
+  };
+  walk_swin(m_, B, Launch{*this, w, s});
+}
+
+// ---------------------------------------------------------------------------
 // Forward: prologue -> body (graph-capturable) -> epilogue, each dispatched by family (model.hpp)
 // ---------------------------------------------------------------------------
 void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStream_t s, ImageSrc isrc) {
@@ -611,6 +667,7 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
     if (!opt_.resize_short) throw std::logic_error("prologue: a resized source without the input resize");
     float* y = static_cast<float*>(w.bufs[m_.family == SPI_FAMILY_RESNET     ? (int)kRnResized
                                           : m_.family == SPI_FAMILY_CONVNEXT ? (int)kCnResized
+                                          : m_.family == SPI_FAMILY_SWIN     ? (int)kSwResized
                                                                              : (int)kVtResized]);
     prof_op(s, "resize_crop_u8", 0, (double)B * 3 * ((double)isrc.H * isrc.W + (double)image * image * 4), [&] {
       resize_crop_u8(in[0], src == kSrcU8Nhwc, B, isrc.H, isrc.W, opt_.resize_short, image, input_xf_, y, s);
@@ -647,6 +704,10 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
       return prof_op(s, "patchify", 0, (double)B * 3 * image * image * (4 + (f16 ? 2 : 4)), [&] {
         patchify(image_in, w.bufs[kCnPatches], B, 3, image, image, 4, f16, s, src, input_xf_);
       });
+    case SPI_FAMILY_SWIN:  // the same 4x4 / stride 4 stem
+      return prof_op(s, "patchify", 0, (double)B * 3 * image * image * (4 + (f16 ? 2 : 4)), [&] {
+        patchify(image_in, w.bufs[kSwPatches], B, 3, image, image, 4, f16, s, src, input_xf_);
+      });
   }
 }
 
@@ -656,6 +717,7 @@ void Model::body(Workspace& w, int B, int S, hipStream_t s) {
     case SPI_FAMILY_BERT: return body_bert(w, B, S, s);
     case SPI_FAMILY_VIT: return body_vit(w, B, s);
     case SPI_FAMILY_CONVNEXT: return body_convnext(w, B, s);
+    case SPI_FAMILY_SWIN: return body_swin(w, B, s);
   }
 }
 
@@ -680,6 +742,15 @@ void Model::epilogue(Workspace& w, int B, int S, void* const* out, hipStream_t s
     case SPI_FAMILY_CONVNEXT: {
       float* logits = logits_dst(w.bufs[kCnLogits], out);
       run_gemm(m_.fc, linear_layer_desc(m_.fc, B), w.bufs[kCnPooled], logits, nullptr, LnPtrs{}, w, s);
+      return run_image_outputs(logits, B, out, s);
+    }
+    case SPI_FAMILY_SWIN: {  // the mean of the LayerNorm'd last map, then head
+      float* logits = logits_dst(w.bufs[kSwLogits], out);
+      const int hw = swin_last_side(m_) * swin_last_side(m_);
+      if (pooled_fc(m_, hw))
+        run_pooled_fc(w.bufs[kSwLn], B, hw, logits, w, s);
+      else
+        run_gemm(m_.fc, linear_layer_desc(m_.fc, B), w.bufs[kSwPooled], logits, nullptr, LnPtrs{}, w, s);
       return run_image_outputs(logits, B, out, s);
     }
   }

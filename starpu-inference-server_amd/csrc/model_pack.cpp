@@ -13,6 +13,7 @@
 #include <stdexcept>
 
 #include "convnext_pack.hpp"
+#include "swin_pack.hpp"
 #include "gconv.hpp"
 #include "ln_fold_pack.hpp"
 #include "pack.hpp"
@@ -282,6 +283,7 @@ struct Packer {
   void pack_bert_head(const PMap& all, bool two_layer);
   void build_vit(const PMap& p);
   void build_convnext(const PMap& p);
+  void build_swin(const PMap& p);
 };
 
 void Packer::build_resnet(const PMap& p) {
@@ -665,6 +667,100 @@ void Packer::build_convnext(const PMap& p) {
   m.feat = m.fc.k;
 }
 
+// torchvision's SwinTransformer (v1): features.0 the stem (4x4 / stride 4 conv, Permute, LayerNorm),
+// features.1, 3, 5, 7 the stages of SwinTransformerBlocks, features.2, 4, 6 the PatchMerging layers, norm, head.
+// Embed dim, depths, heads per stage and the window are read from the tensors: the bias table is
+// [(2 ws - 1)^2][heads].
+void Packer::build_swin(const PMap& p) {
+  auto refuse = [](const std::string& what) { throw std::runtime_error("swin: " + what); };
+  auto feat = [](int i) { return "features." + std::to_string(i) + "."; };
+  for (const auto& kv : p)
+    if (kv.first.find("logit_scale") != std::string::npos || kv.first.find("cpb_mlp") != std::string::npos)
+      refuse("'" + kv.first + "' is a Swin-v2 parameter (logit_scale / cpb_mlp): only v1 blocks are served");
+  if (m.image % 4) refuse("image size " + std::to_string(m.image) + " must be a multiple of 4");
+  const spi_named_tensor* sw = need(p, "features.0.0.weight");
+  if (sw->ndim != 4 || sw->shape[1] != 3 || sw->shape[2] != 4 || sw->shape[3] != 4)
+    refuse("features.0.0.weight must be a 4x4 conv over 3 channels");
+  auto width_ok = [&](int C) {
+    if (!dwconv7_supported(C))
+      refuse("stage width " + std::to_string(C) + " must be a multiple of 32, at most 1536 (the LayerNorm row kernel's range)");
+  };
+  int C = (int)sw->shape[0];
+  width_ok(C);
+  m.sw_stem = pack_linear(fdata(sw), has(p, "features.0.0.bias") ? fdata(need(p, "features.0.0.bias")) : nullptr, C, 48, false);
+  m.sw_stem_ln = pack_ln(p, "features.0.2");
+  int H = m.image / 4;
+  for (int stage = 0; has(p, feat(2 * stage + 1) + "0.attn.qkv.weight"); ++stage) {
+    if (stage > 0) {
+      const std::string pre = feat(2 * stage);
+      if (H % 2)
+        refuse("the merge before stage " + std::to_string(stage) + " would halve a map of odd side " + std::to_string(H));
+      if (!s2d_ln_supported(C))
+        refuse("the merge before stage " + std::to_string(stage) + " normalises rows of " + std::to_string(4 * C) +
+               " columns: at most 2048 (the merge row kernel's range)");
+      const spi_named_tensor* rw = need(p, pre + "reduction.weight");
+      if (rw->ndim != 2 || rw->shape[1] != 4 * C)
+        refuse(pre + "reduction.weight must read the " + std::to_string(4 * C) + " gathered columns of stage " + std::to_string(stage - 1));
+      const int N = (int)rw->shape[0];
+      if (N != 2 * C)
+        refuse("stage " + std::to_string(stage) + " has " + std::to_string(N) + " channels: a merge must double the " +
+               std::to_string(C) + " before it");
+      width_ok(N);
+      SwMerge g;
+      g.ln = pack_ln(p, pre + "norm");
+      g.red = pack_linear_named(p, pre + "reduction", false);
+      m.sw_merge.push_back(g);
+      C = N;
+      H /= 2;
+    }
+    m.sw_dims.push_back(C);
+    int nb = 0;
+    for (;; ++nb) {
+      const std::string pre = feat(2 * stage + 1) + std::to_string(nb) + ".";
+      if (!has(p, pre + "attn.qkv.weight")) break;
+      const spi_named_tensor* tb = need(p, pre + "attn.relative_position_bias_table");
+      if (tb->ndim != 2 || tb->shape[1] < 1) refuse(pre + "attn.relative_position_bias_table must be [(2 ws - 1)^2][heads]");
+      int ws = 0;
+      for (int w = 1; w <= 64 && !ws; ++w)
+        if ((int64_t)(2 * w - 1) * (2 * w - 1) == tb->shape[0]) ws = w;
+      if (!window_supported(ws))
+        refuse(pre + "attn.relative_position_bias_table has " + std::to_string(tb->shape[0]) +
+               " rows: (2 ws - 1)^2 for a window ws of 2 .. 8 is served");
+      if (m.sw_window && ws != m.sw_window)
+        refuse(pre + "attn: window " + std::to_string(ws) + " differs from the " + std::to_string(m.sw_window) + " of the blocks before");
+      m.sw_window = ws;
+      const int heads = (int)tb->shape[1];
+      if (C % heads || C / heads != kWinHeadDim)
+        refuse(pre + "attn: " + std::to_string(C) + " channels over " + std::to_string(heads) + " heads: head_dim must be 32");
+      if (H % ws)
+        refuse("stage " + std::to_string(stage) + "'s map of side " + std::to_string(H) + " (image " + std::to_string(m.image) +
+               ") is no multiple of the window " + std::to_string(ws) + " (padded windows are not served)");
+      SwBlock blk;
+      blk.C = C;
+      blk.heads = heads;
+      blk.bias = blob.add(nullptr, (size_t)heads * kWinBiasHead * sizeof(float));
+      window_bias_pack(fdata(tb), ws, heads, reinterpret_cast<float*>(blob.data.data() + blk.bias));
+      blk.ln1 = pack_ln(p, pre + "norm1");
+      blk.ln2 = pack_ln(p, pre + "norm2");
+      blk.qkv = pack_linear_named(p, pre + "attn.qkv", false);
+      blk.proj = pack_linear_named(p, pre + "attn.proj", false);
+      blk.fc1 = pack_linear_named(p, pre + "mlp.0", false);
+      blk.fc2 = pack_linear_named(p, pre + "mlp.3", false);
+      if (blk.qkv.k != C || blk.qkv.n != 3 * C || blk.proj.k != C || blk.proj.n != C || blk.fc1.k != C || blk.fc1.n < 1 ||
+          blk.fc2.k != blk.fc1.n || blk.fc2.n != C)
+        refuse(pre + "attn.qkv / attn.proj / mlp.0 / mlp.3 do not chain over " + std::to_string(C) + " channels");
+      m.sw_blocks.push_back(blk);
+    }
+    m.stage_blocks.push_back(nb);
+  }
+  if (m.sw_blocks.empty()) refuse("no blocks (features.1.0.attn.qkv.weight)");
+  m.final_ln = pack_ln(p, "norm");
+  m.fc = pack_linear_named(p, "head", false);
+  if (m.fc.k != C) refuse("head reads " + std::to_string(m.fc.k) + " of " + std::to_string(C) + " features");
+  m.classes = m.fc.n;
+  m.feat = m.fc.k;
+}
+
 }  // namespace
 
 PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* params, int n) {
@@ -693,7 +789,9 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     else if (ends_with(p, "features.0.0.weight") && ends_with(p, "features.1.0.block.0.weight") &&
              ends_with(p, "features.1.0.layer_scale"))
       m.family = SPI_FAMILY_CONVNEXT;
-    else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT/ConvNeXt parameter names");
+    else if (ends_with(p, "features.0.0.weight") && ends_with(p, "features.1.0.attn.relative_position_bias_table"))
+      m.family = SPI_FAMILY_SWIN;
+    else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT/ConvNeXt/Swin parameter names");
   }
   if (const int io = cfg.bert_io) {  // spi_codelet.h: enum spi_bert_io
     constexpr int heads = SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA;
@@ -743,6 +841,15 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     os << "convnext[";
     for (size_t i = 0; i < m.stage_blocks.size(); ++i) os << (i ? "," : "") << m.stage_blocks[i];
     os << "] C" << m.cn_dims.front() << " img" << m.image << " classes" << m.classes;
+  } else if (m.family == SPI_FAMILY_SWIN) {
+    if (cfg.precision != SPI_PREC_F16 && cfg.precision != SPI_PREC_F32)
+      throw std::runtime_error(
+          "swin: SPI_PREC_F16X3 and SPI_PREC_F16M are not served for this family; use SPI_PREC_F16 or SPI_PREC_F32");
+    m.eps = cfg.eps > 0 ? cfg.eps : 1e-5f;
+    pk.build_swin(strip_prefix(p, "features.0.0.weight"));
+    os << "swin[";
+    for (size_t i = 0; i < m.stage_blocks.size(); ++i) os << (i ? "," : "") << m.stage_blocks[i];
+    os << "] C" << m.sw_dims.front() << " ws" << m.sw_window << " img" << m.image << " classes" << m.classes;
   } else {
     throw std::runtime_error("unsupported model family");
   }

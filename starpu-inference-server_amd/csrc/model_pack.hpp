@@ -65,6 +65,18 @@ struct CnDown {  // ConvNeXt stage change: LayerNorm2d, then the 2x2 / stride 2 
   LinearW conv;  // [2 C][(kh 2 + kw) C + c] (convnext_pack.hpp)
 };
 
+struct SwBlock {  // Swin block: norm1, QKV, shifted-window attention (window_attn.hip), proj + x, norm2, MLP + x
+  int C = 0, heads = 0;
+  size_t bias = 0;  // fp32 [heads][16][64][4] (swin_pack.hpp: window_bias_pack)
+  LnW ln1, ln2;
+  LinearW qkv, proj, fc1, fc2;
+};
+
+struct SwMerge {  // Swin patch merging: gather 2x2 + LayerNorm over 4 C (s2d_ln), then the bias-free Linear 4 C -> 2 C
+  LnW ln;
+  LinearW red;  // torch's [2 C][4 C] as it is
+};
+
 struct PackedModel {
   int family = 0;
   Prec prec = Prec::F16;
@@ -122,6 +134,16 @@ struct PackedModel {
   std::vector<int> cn_dims;
   std::vector<CnBlock> cn_blocks;
   std::vector<CnDown> cn_down;
+
+  // Swin: the 4x4 / stride 4 stem as a linear layer over patchify's rows + its LayerNorm; the blocks in order
+  // (stage_blocks per stage, sw_dims the stage widths); the merge in front of stages 1..; the window side;
+  // `norm` (final_ln, over every pixel of the last map) and `head` (fc; classes, feat as for ResNet)
+  LinearW sw_stem;
+  LnW sw_stem_ln;
+  std::vector<int> sw_dims;
+  std::vector<SwBlock> sw_blocks;
+  std::vector<SwMerge> sw_merge;
+  int sw_window = 0;
 
   std::string desc;
   uint64_t digest = 0;  // FNV-1a 64 of the blob

@@ -7,12 +7,14 @@
 
 #include "convnext_pack.hpp"
 #include "resample.hpp"
+#include "swin_pack.hpp"
 
 namespace spi {
 
 namespace {
 bool image_family(const PackedModel& m) {
-  return m.family == SPI_FAMILY_RESNET || m.family == SPI_FAMILY_VIT || m.family == SPI_FAMILY_CONVNEXT;
+  return m.family == SPI_FAMILY_RESNET || m.family == SPI_FAMILY_VIT || m.family == SPI_FAMILY_CONVNEXT ||
+         m.family == SPI_FAMILY_SWIN;
 }
 }  // namespace
 
@@ -351,9 +353,55 @@ CnGemmVisitor<F> walk_convnext_gemms(const PackedModel& m, int B, F&& f) {
   walk_convnext(m, B, v);
   return v;
 }
+
+// The GEMMs of the Swin graph, each as the desc Model::body_swin (and the epilogue) builds for it; also the
+// largest map of the residual stream and the largest hidden rows, in elements, and the attention FLOPs.
+template <class F>
+struct SwGemmVisitor {
+  const PackedModel& m;
+  F on_gemm;
+  size_t amax = 0, hmax = 0;
+  double attn_flops = 0;
+  void stored(int B, int H, int C) { amax = std::max(amax, (size_t)B * H * H * C); }
+  void stem(int B, int H, int) {
+    stored(B, H, m.sw_stem.n);
+    on_gemm("stem", m.sw_stem, cn_gemm_desc(m.sw_stem, B * H * H, Act::None, false, true));
+  }
+  void merge(int B, int H, const SwMerge& g, int, int) {
+    stored(B, H / 2, g.red.n);
+    on_gemm("merge", g.red, cn_gemm_desc(g.red, B * (H / 2) * (H / 2), Act::None, false, false));
+  }
+  void block(int B, int H, const SwBlock& k, int, int, int) {
+    const int rows = B * H * H, N = m.sw_window * m.sw_window;
+    attn_flops += 4.0 * N * N * kWinHeadDim * k.heads * (double)(rows / N);
+    hmax = std::max(hmax, (size_t)rows * k.fc1.n);
+    on_gemm("qkv", k.qkv, cn_gemm_desc(k.qkv, rows, Act::None, false, false));
+    on_gemm("proj", k.proj, cn_gemm_desc(k.proj, rows, Act::None, true, false));
+    on_gemm("fc1", k.fc1, cn_gemm_desc(k.fc1, rows, Act::Gelu, false, false));
+    on_gemm("fc2", k.fc2, cn_gemm_desc(k.fc2, rows, Act::None, true, false));
+  }
+  void tail(int B, int H, int) {
+    if (pooled_fc(m, H * H)) on_gemm("avgpool_fc", m.fc, pooled_fc_desc(m, B, H * H));
+    else on_gemm("fc", m.fc, linear_layer_desc(m.fc, B));
+  }
+};
+
+template <class F>
+SwGemmVisitor<F> walk_swin_gemms(const PackedModel& m, int B, F&& f) {
+  SwGemmVisitor<F> v{m, std::forward<F>(f)};
+  walk_swin(m, B, v);
+  return v;
+}
 }  // namespace
 
 double model_flops(const PackedModel& m, int64_t B) {
+  if (m.family == SPI_FAMILY_SWIN) {
+    double f = 0;
+    const auto v = walk_swin_gemms(m, (int)B, [&](const char*, const LinearW&, const GemmDesc& d) {
+      f += 2.0 * (d.pool_rows ? d.M / d.pool_rows : d.M) * d.N * (double)d.K;
+    });
+    return f + v.attn_flops;
+  }
   if (m.family == SPI_FAMILY_CONVNEXT) {
     double f = 0;
     const auto v = walk_convnext_gemms(m, (int)B, [&](const char*, const LinearW&, const GemmDesc& d) {
@@ -491,6 +539,18 @@ WorkspacePlan workspace_plan(const PackedModel& m, const ReplicaOptions& o) {
     sz[kCnLogits] = logits;
     sz[kCnResized] = resized;
   }
+  if (m.family == SPI_FAMILY_SWIN) {
+    const auto v = walk_swin_gemms(m, (int)B, [&](const char*, const LinearW& L, const GemmDesc& d) { slabs(d, L.prec); });
+    const size_t H0 = m.image / 4, HL = swin_last_side(m);
+    sz.assign(kSwBufs, 0);
+    sz[kSwPatches] = B * H0 * H0 * m.sw_stem.k * es;
+    sz[kSwX0] = sz[kSwX1] = sz[kSwLn] = sz[kSwCtx] = v.amax * es;
+    sz[kSwQkv] = 3 * v.amax * es;
+    sz[kSwHidden] = std::max(v.hmax * es, B * H0 * H0 * m.sw_stem.n * 4);  // the hidden rows; the stem's fp32 rows
+    sz[kSwPooled] = pooled_fc(m, (int)(HL * HL)) ? 0 : B * m.feat * es;
+    sz[kSwLogits] = logits;
+    sz[kSwResized] = resized;
+  }
   if (m.family == SPI_FAMILY_BERT || m.family == SPI_FAMILY_VIT)
     walk_transformer_gemms(m, (int)B, m.seq, [&](const char*, const LinearW& L, const GemmDesc& d) { slabs(d, L.prec); });
   // Split-K slabs: choose_plan only splits grids of < 128 tiles into <= 512 +
@@ -514,6 +574,8 @@ int plan_check(const PackedModel& m, const ReplicaOptions& o, int B, int S) {
     walk_resnet_gemms(m, B, [&](const char* name, const GemmDesc& d, Prec prec, const GemmDesc* d1) { hold(name, d, prec, d1); });
   } else if (m.family == SPI_FAMILY_CONVNEXT) {
     walk_convnext_gemms(m, B, [&](const char* name, const LinearW& L, const GemmDesc& d) { hold(name, d, L.prec, nullptr); });
+  } else if (m.family == SPI_FAMILY_SWIN) {
+    walk_swin_gemms(m, B, [&](const char* name, const LinearW& L, const GemmDesc& d) { hold(name, d, L.prec, nullptr); });
   } else if (m.family == SPI_FAMILY_BERT || m.family == SPI_FAMILY_VIT) {
     if (m.family == SPI_FAMILY_BERT && (S < 1 || S > m.seq)) throw std::runtime_error("plan_check: sequence outside 1 .. seq");
     walk_transformer_gemms(m, B, S, [&](const char* name, const LinearW& L, const GemmDesc& d) { hold(name, d, L.prec, nullptr); });

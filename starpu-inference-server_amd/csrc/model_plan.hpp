@@ -14,6 +14,7 @@
 #include "gemm_plan.hpp"
 #include "image_src.hpp"
 #include "model_pack.hpp"
+#include "swin_pack.hpp"
 
 namespace spi {
 
@@ -46,6 +47,11 @@ enum VitBuf { kVtPatches, kVtProj, kVtX, kVtLn, kVtQkv, kVtCtx, kVtMlp, kVtCls, 
 // space-to-depth rows); the 4C hidden rows (first the stem GEMM's fp32 output); the pooled + LayerNorm'd
 // features; logits scratch and resized image as above.
 enum CnBuf { kCnPatches, kCnAct0, kCnAct1, kCnLn, kCnHidden, kCnPooled, kCnLogits, kCnResized, kCnBufs };
+// Swin: the stem's 4x4 patches; two slots of the residual stream (NHWC rows in the compute type); the
+// LayerNorm'd rows (norm1 / norm2, a merge's gathered rows, the final norm's); the QKV rows; the context rows; the
+// MLP hidden rows (first the stem GEMM's fp32 output); the pooled features (maps of more than 64 pixels only);
+// logits scratch and resized image as above.
+enum SwBuf { kSwPatches, kSwX0, kSwX1, kSwLn, kSwQkv, kSwCtx, kSwHidden, kSwPooled, kSwLogits, kSwResized, kSwBufs };
 
 // ---------------------------------------------------------------------------
 // I/O contract
@@ -192,6 +198,35 @@ void walk_convnext(const PackedModel& m, int B, V&& v) {
       v.block(B, H, m.cn_blocks[blk], cur, cur ^ (kCnAct0 ^ kCnAct1));
       cur ^= kCnAct0 ^ kCnAct1;
     }
+  }
+  v.tail(B, H, cur);
+}
+
+// ---------------------------------------------------------------------------
+// The Swin graph, walked once, as walk_convnext is: Model::body_swin launches from it, model_flops counts it,
+// workspace_plan and plan_check size and hold its GEMMs (descs: cn_gemm_desc).  H: the side of the square map.
+// ---------------------------------------------------------------------------
+inline int swin_last_side(const PackedModel& m) { return (m.image / 4) >> (m.stage_blocks.size() - 1); }
+// The visitor V sees, in launch order:
+//   v.stem(B, H, out)              stem GEMM on kSwPatches (fp32 into kSwHidden) + LayerNorm into slot out
+//   v.merge(B, H, g, in, out)      gather + LayerNorm of the H x H map in slot in (into kSwLn), Linear into out
+//   v.block(B, H, blk, shift, x, t)  norm1 (x -> kSwLn), QKV (-> kSwQkv), window attention (-> kSwCtx), proj + x -> t,
+//                                  norm2 (t -> kSwLn), Linear + GELU (-> kSwHidden), Linear + t -> x
+//   v.tail(B, H, in)               the final LayerNorm of every pixel into kSwLn (and, past 64 pixels, their mean into
+//                                  kSwPooled); the epilogue runs avgpool + FC, or the FC
+template <class V>
+void walk_swin(const PackedModel& m, int B, V&& v) {
+  int H = m.image / 4, cur = kSwX0;
+  v.stem(B, H, cur);
+  size_t blk = 0;
+  for (size_t stage = 0; stage < m.stage_blocks.size(); ++stage) {
+    if (stage > 0) {
+      v.merge(B, H, m.sw_merge[stage - 1], cur, cur ^ (kSwX0 ^ kSwX1));
+      cur ^= kSwX0 ^ kSwX1;
+      H /= 2;
+    }
+    for (int i = 0; i < m.stage_blocks[stage]; ++i, ++blk)
+      v.block(B, H, m.sw_blocks[blk], window_block_shift(i, m.sw_window, H), cur, cur ^ (kSwX0 ^ kSwX1));
   }
   v.tail(B, H, cur);
 }

@@ -9,6 +9,7 @@
 
 #include "../../include/spi_ops.h"
 #include "convnext_pack.hpp"
+#include "swin_pack.hpp"
 #include "gconv.hpp"
 #include "gemm_plan.hpp"
 #include "ln_fold_pack.hpp"
@@ -350,6 +351,37 @@ int spi_op_ln_rows(int32_t precision, const void* x, int32_t x_f32, int32_t rows
   if (!x || !gamma || !beta || !y) return fail("ln_rows: null x, gamma, beta or y");
   return guarded([&] {
     spi::ln_rows(x, x_f32 != 0, y, gamma, beta, rows, C, pool_hw, eps, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+// ---- Swin kernels (window_attn.hip, s2d_ln in dwconv_ln.hip, swin_pack.hpp) ----
+
+int spi_op_window_bias_pack(const float* table, int32_t window, int32_t heads, float* dst) {
+  if (!table || !dst || heads < 1 || heads > 65535) return fail("invalid window bias pack arguments");
+  if (!spi::window_supported(window)) return fail("window bias pack: window must be 2 .. 8");
+  spi::window_bias_pack(table, window, heads, dst);
+  return 0;
+}
+
+int spi_op_window_attention(int32_t precision, const void* qkv, const float* rel_bias, void* ctx, int32_t B, int32_t H,
+                            int32_t W, int32_t heads, int32_t head_dim, int32_t window, int32_t shift, float scale,
+                            void* stream) {
+  if (precision != 0 && precision != 1) return fail("window_attention: precision 0 (fp32) or 1 (fp16)");
+  if (!qkv || !rel_bias || !ctx) return fail("window_attention: null qkv, rel_bias or ctx");
+  return guarded([&] {
+    spi::window_attention(qkv, rel_bias, ctx, B, H, W, heads, head_dim, window, shift, scale, precision == 1,
+                          static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_s2d_ln(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* gamma,
+                  const float* beta, float eps, void* y, void* stream) {
+  if (precision != 0 && precision != 1) return fail("s2d_ln: precision 0 (fp32) or 1 (fp16)");
+  if (!x || !gamma || !beta || !y) return fail("s2d_ln: null x, gamma, beta or y");
+  return guarded([&] {
+    spi::s2d_ln(x, y, gamma, beta, B, H, W, C, eps, precision == 1, static_cast<hipStream_t>(stream));
     return check_launch();
   });
 }

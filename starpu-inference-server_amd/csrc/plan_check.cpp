@@ -3,7 +3,7 @@
 // workspace, walks the forward at every batch 1 .. max_batch against it (plan_check: the checks of each
 // launch, with no launch) and holds one accepted and one refused task against the I/O contract; prints
 // one line per model; then the BERT with task heads (SPI_BERT_HEAD_*): output counts up to five, their byte
-// sizes, the pooled vector's place in the workspace; then one ConvNeXt walk.  Built with the address and undefined-behaviour
+// sizes, the pooled vector's place in the workspace; then one ConvNeXt and one Swin walk.  Built with the address and undefined-behaviour
 // sanitizers, no HIP.
 #include <cstdio>
 #include <deque>
@@ -261,6 +261,49 @@ int main() {
     } catch (const std::runtime_error& e) {
       if (served) std::fprintf(stderr, "convnext|%s: %s\n", pr.first, e.what()), rc = 1;
       else std::printf("convnext|%s| refused: %s\n", pr.first, e.what());
+    }
+  }
+  // Swin ([2, 2, 1] blocks over 64 .. 256 channels, window 7, at 112 x 112: maps 28 / 14 / 7): both served
+  // precisions, every batch walked against the planned workspace, the image I/O contract, the two refused precisions.
+  Tensors sw;
+  sw.add("features.0.0.weight", {64, 3, 4, 4}), sw.add("features.0.0.bias", {64}), sw.norm("features.0.2", 64, false);
+  const int sdepths[3] = {2, 2, 1};
+  for (int st = 0, c = 64; st < 3; ++st, c *= 2) {
+    if (st > 0) {
+      const std::string d = "features." + std::to_string(2 * st) + ".";
+      sw.norm(d + "norm", 2 * c, false), sw.add(d + "reduction.weight", {c, 2 * c});
+    }
+    for (int i = 0; i < sdepths[st]; ++i) {
+      const std::string b = "features." + std::to_string(2 * st + 1) + "." + std::to_string(i) + ".";
+      sw.norm(b + "norm1", c, false), sw.norm(b + "norm2", c, false), sw.add(b + "attn.relative_position_bias_table", {169, c / 32});
+      sw.linear(b + "attn.qkv", 3 * c, c), sw.linear(b + "attn.proj", c, c), sw.linear(b + "mlp.0", 4 * c, c), sw.linear(b + "mlp.3", c, 4 * c);
+    }
+  }
+  sw.norm("norm", 256, false), sw.linear("head", 10, 256);
+  for (const auto& pr : {std::make_pair("fp16", (int)SPI_PREC_F16), std::make_pair("fp32", (int)SPI_PREC_F32),
+                         std::make_pair("fp16x3", (int)SPI_PREC_F16X3), std::make_pair("fp16m", (int)SPI_PREC_F16M)}) {
+    spi_model_config cfg{};
+    cfg.family = SPI_FAMILY_AUTO, cfg.precision = pr.second, cfg.max_batch = 8, cfg.image_size = 112;
+    const bool served = pr.second == SPI_PREC_F16 || pr.second == SPI_PREC_F32;
+    try {
+      const spi::PackedModel m = spi::pack_model(cfg, sw.t.data(), (int)sw.t.size());
+      spi::ReplicaOptions o;
+      o.resize_short = 2 * m.image;
+      const spi::WorkspacePlan plan = spi::workspace_plan(m, o);
+      int steps = 0;
+      for (int B = 1; B <= m.max_batch; ++B) steps += spi::plan_check(m, o, B, 0);
+      const size_t out = (size_t)2 * m.classes * 4;
+      const bool ok = served && m.family == SPI_FAMILY_SWIN && m.sw_window == 7 && plan.bytes.size() == (size_t)spi::kSwBufs &&
+                      plan.bytes[spi::kSwQkv] == 3 * plan.bytes[spi::kSwCtx] &&
+                      accepted(m, o, SPI_DTYPE_F32, 2, {3, 112, 112}, 4, out) && !accepted(m, o, SPI_DTYPE_F32, 2, {3, 111, 112}, 4, out) &&
+                      accepted(m, o, SPI_DTYPE_U8, 2, {150, 120, 3}, 1, out);
+      if (!ok) std::fprintf(stderr, "swin|%s: family, window, plan or check_io are not the expected ones\n", pr.first), rc = 1;
+      std::printf("swin|%s| flops(1) %.0f flops(3) %.0f, %zu buffers, slabs %zu (planned %zu), %d steps fit, %s\n", pr.first,
+                  spi::model_flops(m, 1), spi::model_flops(m, 3), plan.bytes.size(), plan.partial_floats, plan.partial_planned,
+                  steps, spi::replica_desc(m, o).c_str());
+    } catch (const std::runtime_error& e) {
+      if (served) std::fprintf(stderr, "swin|%s: %s\n", pr.first, e.what()), rc = 1;
+      else std::printf("swin|%s| refused: %s\n", pr.first, e.what());
     }
   }
   return rc;

@@ -92,6 +92,21 @@ void ln_rows(const void* x, bool x_f32, void* y, const float* gamma, const float
 void ln_space_to_depth(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W, int C,
                        float eps, bool f16, hipStream_t s);
 
+// Swin (window_attn.hip, s2d_ln in dwconv_ln.hip; layouts and supported sets: swin_pack.hpp).  Shifted-window
+// attention at head_dim 32: qkv [B H W][3 C] and ctx [B H W][C] in the compute type and in plain NHWC pixel
+// order, C = 32 heads; window (wy, wx), token (ty, tx) is the pixel ((wy ws + ty + shift) mod H,
+// (wx ws + tx + shift) mod W); scores (q scale) k^T + rel_bias + mask, the mask -100 between different shift
+// regions, computed from the coordinates; rel_bias fp32 [heads][16][64][4] from window_bias_pack.  fp32 bias,
+// mask, softmax and accumulation in both types.  hd 32, window 2 .. 8, H and W multiples of it, 0 <= shift < window;
+// qkv, ctx and rel_bias 16-byte aligned.  Throws std::invalid_argument outside that.
+void window_attention(const void* qkv, const float* rel_bias, void* ctx, int B, int H, int W, int heads, int hd,
+                      int window, int shift, float scale, bool f16, hipStream_t s);
+// Patch merging's rows: y [B (H/2) (W/2)][4 C] = LayerNorm over 4 C of the gathered pixels, pixel
+// (2 i + dy, 2 j + dx) of x NHWC [B][H][W][C] at columns (dx 2 + dy) C (torchvision's PatchMerging order);
+// gamma / beta fp32 [4 C].  C % 32 == 0, 4 C <= 2048, even H and W.
+void s2d_ln(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W, int C, float eps,
+            bool f16, hipStream_t s);
+
 // The kind of an image task's input buffer (SrcKind) and its 8-bit input transform (InputXf): image_src.hpp.
 // The transform of one pixel of channel c.  Contraction is switched off for the two operations:
 // HIP compiles with -ffp-contract=fast, under which __fmul_rn / __fadd_rn are a plain * and + that

@@ -248,6 +248,38 @@ def ln_rows(prec, x, rows, c, gamma, beta, eps, out, pool_hw=0, stream=None):
     return out
 
 
+# ---- Swin kernels (spi_ops.h: spi_op_window_attention, spi_op_window_bias_pack, spi_op_s2d_ln) ----
+
+
+def window_bias(table, window, device="cuda") -> torch.Tensor:
+    """relative_position_bias_table [(2 ws - 1)^2][heads] -> window_attention's packed bias, a device fp32 tensor
+    [heads][16][64][4] (spi_ops.h states the order); the relative-position index is recomputed from ws."""
+    t = np.ascontiguousarray(np.asarray(table.detach().cpu() if isinstance(table, torch.Tensor) else table, dtype=np.float32))
+    if t.ndim != 2 or t.shape[0] != (2 * window - 1) ** 2:
+        raise ValueError(f"window_bias: the table must be [(2 ws - 1)^2][heads], got {t.shape} at ws {window}")
+    host = np.empty((t.shape[1], 16, 64, 4), np.float32)
+    _check(lib.spi_op_window_bias_pack(t.ctypes.data, window, t.shape[1], host.ctypes.data))
+    return torch.from_numpy(host).to(device)
+
+
+def window_attention(prec, qkv, rel_bias, B, H, W_, heads, window, shift, scale=32 ** -0.5, stream=None, out=None,
+                     head_dim=32):
+    """ctx [B H W][32 heads] of qkv [B H W][3 C] in NHWC pixel order: attention inside window x window windows of
+    the map rolled by -shift, rel_bias from window_bias(); out: the buffer to write (default: a fresh one)."""
+    if out is None:
+        out = torch.empty((B * H * W_, heads * head_dim), dtype=qkv.dtype, device=qkv.device)
+    _check(lib.spi_op_window_attention(PREC[prec], _ptr(qkv), _ptr(rel_bias), _ptr(out), B, H, W_, heads, head_dim, window,
+                                       shift, scale, _stream(stream)))
+    return out
+
+
+def s2d_ln(prec, x_nhwc, gamma, beta, eps, out, stream=None):
+    """out [B (H/2) (W/2)][4 C] = LayerNorm over 4 C of patch merging's gathered rows (torchvision's order)."""
+    B, H, W_, c = x_nhwc.shape
+    _check(lib.spi_op_s2d_ln(PREC[prec], _ptr(x_nhwc), B, H, W_, c, _ptr(gamma), _ptr(beta), eps, _ptr(out), _stream(stream)))
+    return out
+
+
 def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None, out=None, head_dim=64):
     """ctx [B S][D] of packed qkv [B S][3 D], D = heads * head_dim (32 or 64); out: the buffer to write
     (default: a fresh one).  prec may be the integer precision code itself."""

@@ -353,6 +353,134 @@ def convnext_large(seed: int = 0, image: int = 224, **kw) -> ConvNeXt:
 
 
 # ---------------------------------------------------------------------------
+# Swin Transformer (torchvision.models.swin_transformer naming, v1 blocks)
+# ---------------------------------------------------------------------------
+class ShiftedWindowAttention(nn.Module):
+    def __init__(self, dim: int, window: int, shift: int, heads: int):
+        super().__init__()
+        self.window, self.shift, self.heads = window, shift, heads
+        self.qkv = nn.Linear(dim, 3 * dim)
+        self.proj = nn.Linear(dim, dim)
+        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * window - 1) ** 2, heads))
+        coords = torch.stack(torch.meshgrid(torch.arange(window), torch.arange(window), indexing="ij")).flatten(1)
+        rel = (coords[:, :, None] - coords[:, None, :]).permute(1, 2, 0) + (window - 1)
+        self.register_buffer("relative_position_index", (rel[:, :, 0] * (2 * window - 1) + rel[:, :, 1]).flatten())
+
+    def forward(self, x):  # [B, H, W, C]; H and W multiples of the window (torchvision pads otherwise)
+        B, H, W, C = x.shape
+        ws, N = self.window, self.window ** 2
+        sy, sx = (0 if ws >= H else self.shift), (0 if ws >= W else self.shift)
+        if sy or sx:
+            x = torch.roll(x, shifts=(-sy, -sx), dims=(1, 2))
+        nw = (H // ws) * (W // ws)
+        x = x.view(B, H // ws, ws, W // ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B * nw, N, C)
+        qkv = self.qkv(x).reshape(B * nw, N, 3, self.heads, C // self.heads).permute(2, 0, 3, 1, 4)
+        q, k, v = qkv[0] * (C // self.heads) ** -0.5, qkv[1], qkv[2]
+        attn = q @ k.transpose(-2, -1)
+        bias = self.relative_position_bias_table[self.relative_position_index].view(N, N, -1).permute(2, 0, 1)
+        attn = attn + bias.unsqueeze(0)
+        if sy or sx:
+            mask = x.new_zeros((H, W))
+            count = 0
+            for h in ((0, -ws), (-ws, -sy), (-sy, None)):
+                for w in ((0, -ws), (-ws, -sx), (-sx, None)):
+                    mask[h[0]:h[1], w[0]:w[1]] = count
+                    count += 1
+            mask = mask.view(H // ws, ws, W // ws, ws).permute(0, 2, 1, 3).reshape(nw, N)
+            mask = mask.unsqueeze(1) - mask.unsqueeze(2)
+            mask = mask.masked_fill(mask != 0, -100.0)
+            attn = attn.view(B, nw, self.heads, N, N) + mask.unsqueeze(1).unsqueeze(0)
+            attn = attn.view(-1, self.heads, N, N)
+        x = (attn.softmax(-1) @ v).transpose(1, 2).reshape(B * nw, N, C)
+        x = self.proj(x)
+        x = x.view(B, H // ws, W // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
+        if sy or sx:
+            x = torch.roll(x, shifts=(sy, sx), dims=(1, 2))
+        return x
+
+
+class SwinTransformerBlock(nn.Module):
+    def __init__(self, dim: int, heads: int, window: int, shift: int):
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim, eps=1e-5)
+        self.attn = ShiftedWindowAttention(dim, window, shift, heads)
+        self.norm2 = nn.LayerNorm(dim, eps=1e-5)
+        self.mlp = nn.Sequential(nn.Linear(dim, 4 * dim), nn.GELU(), nn.Dropout(0.0), nn.Linear(4 * dim, dim), nn.Dropout(0.0))
+
+    def forward(self, x):  # eval: stochastic depth is the identity
+        x = x + self.attn(self.norm1(x))
+        return x + self.mlp(self.norm2(x))
+
+
+class PatchMerging(nn.Module):
+    def __init__(self, dim: int):
+        super().__init__()
+        self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
+        self.norm = nn.LayerNorm(4 * dim, eps=1e-5)
+
+    def forward(self, x):  # [B, H, W, C] -> [B, H/2, W/2, 2C]
+        x = torch.cat([x[..., 0::2, 0::2, :], x[..., 1::2, 0::2, :], x[..., 0::2, 1::2, :], x[..., 1::2, 1::2, :]], -1)
+        return self.reduction(self.norm(x))
+
+
+class SwinTransformer(nn.Module):
+    def __init__(self, depths: Sequence[int], heads: Sequence[int], embed: int, window: int = 7, num_classes: int = 1000):
+        super().__init__()
+        layers = [nn.Sequential(nn.Conv2d(3, embed, 4, 4), Permute([0, 2, 3, 1]), nn.LayerNorm(embed, eps=1e-5))]
+        for i, (depth, nh) in enumerate(zip(depths, heads)):
+            dim = embed * 2 ** i
+            if i > 0:
+                layers.append(PatchMerging(dim // 2))
+            layers.append(nn.Sequential(*[SwinTransformerBlock(dim, nh, window, 0 if j % 2 == 0 else window // 2)
+                                          for j in range(depth)]))
+        self.features = nn.Sequential(*layers)
+        feat = embed * 2 ** (len(depths) - 1)
+        self.norm = nn.LayerNorm(feat, eps=1e-5)
+        self.permute = Permute([0, 3, 1, 2])
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+        self.flatten = nn.Flatten(1)
+        self.head = nn.Linear(feat, num_classes)
+
+    def forward(self, x):
+        return self.head(self.flatten(self.avgpool(self.permute(self.norm(self.features(x))))))
+
+
+def swin(depths: Sequence[int], heads: Sequence[int], embed: int, window: int = 7, image: int = 224,
+         num_classes: int = 1000, seed: int = 0) -> SwinTransformer:
+    """Swin Transformer (v1) with seeded random weights (image only documents the size the model is meant for).
+    torchvision's trunc_normal(0.02) init would leave the relative-position bias and every block's branch far
+    below the residual stream (the ConvNeXt note above): here conv and linear weights are N(0, 1 / fan_in) with
+    biases N(0, 0.05^2), LayerNorm gains and biases are re-drawn as vit() does, and the bias tables are N(0, 1),
+    the size of the scaled q k^T scores, so that a wrong bias index, mask or block shows in the logits."""
+    torch.manual_seed(seed)
+    model = SwinTransformer(depths, heads, embed, window, num_classes)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, (nn.Conv2d, nn.Linear)):
+                m.weight.normal_(std=m.weight[0].numel() ** -0.5)
+                if m.bias is not None:
+                    m.bias.normal_(std=0.05)
+            elif isinstance(m, nn.LayerNorm):
+                m.weight.copy_(1.0 + 0.1 * torch.randn_like(m.weight))
+                m.bias.copy_(0.05 * torch.randn_like(m.bias))
+            elif isinstance(m, ShiftedWindowAttention):
+                m.relative_position_bias_table.normal_()
+    return model.eval()
+
+
+def swin_t(seed: int = 0, image: int = 224, **kw) -> SwinTransformer:
+    return swin([2, 2, 6, 2], [3, 6, 12, 24], 96, image=image, seed=seed, **kw)
+
+
+def swin_s(seed: int = 0, image: int = 224, **kw) -> SwinTransformer:
+    return swin([2, 2, 18, 2], [3, 6, 12, 24], 96, image=image, seed=seed, **kw)
+
+
+def swin_b(seed: int = 0, image: int = 224, **kw) -> SwinTransformer:
+    return swin([2, 2, 18, 2], [4, 8, 16, 32], 128, image=image, seed=seed, **kw)
+
+
+# ---------------------------------------------------------------------------
 # BERT (HF transformers BertModel, wrapped like models/import_bert-base-uncased.py)
 # ---------------------------------------------------------------------------
 class BertWrapper(nn.Module):
@@ -572,6 +700,9 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
         "convnext_small": convnext_small,
         "convnext_base": convnext_base,
         "convnext_large": convnext_large,
+        "swin_t": swin_t,
+        "swin_s": swin_s,
+        "swin_b": swin_b,
         "bert-base-uncased": bert_base,
         "bert_base": bert_base,
         "minilm_l6": minilm_l6,
@@ -589,6 +720,6 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
 # name is not an identifier, so give the zoo's modules a loadable qualified name
 # (a traced/scripted model must round-trip through .pt like the reference's).
 for _cls in (BasicBlock, Bottleneck, ResNet, MLPBlock, EncoderBlock, Encoder, VisionTransformer, LayerNorm2d, Permute,
-             CNBlock, ConvNeXt, BertWrapper,
+             CNBlock, ConvNeXt, ShiftedWindowAttention, SwinTransformerBlock, PatchMerging, SwinTransformer, BertWrapper,
              BertTupleWrapper, BertSegmentsWrapper, BertHeadWrapper, AddConstant):
     _cls.__module__ = "spi_zoo"
