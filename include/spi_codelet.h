@@ -241,7 +241,9 @@ enum spi_family {
   SPI_FAMILY_VIT = 3,    /* torchvision vit_*_16 naming */
   SPI_FAMILY_AFFINE = 4, /* y = x * scale + shift (toy models of the reference tests) */
   SPI_FAMILY_CONVNEXT = 5, /* torchvision convnext_* naming; SPI_PREC_F16 and SPI_PREC_F32 */
-  SPI_FAMILY_SWIN = 6      /* torchvision swin_t / _s / _b naming (v1 blocks); SPI_PREC_F16 and SPI_PREC_F32 */
+  SPI_FAMILY_SWIN = 6      /* torchvision swin_t / _s / _b (v1) and swin_v2_t / _s / _b naming, told apart by the
+                            * names (relative_position_bias_table, or logit_scale + cpb_mlp on every attention);
+                            * windows of at most 8 x 8, maps that are multiples of it; SPI_PREC_F16 and SPI_PREC_F32 */
 };
 
 /* SPI_PREC_F16X3: split fp16 -- fp32 activations, each MFMA operand split into
@@ -273,8 +275,10 @@ typedef struct spi_model_config {
                          multiple of 64, <= 1024, so 32-wide models have an even count).  0 = hidden / 64:
                          a 32-wide model (MiniLM: 384 over 12) must state its count.  Any other width is
                          refused at creation with a message naming hidden, heads and the two widths. */
-  int32_t seq_len;    /* BERT: max sequence length (0 = from position table) */
-  int32_t image_size; /* ResNet/ViT: input H = W (0 = 224) */
+  int32_t seq_len;    /* BERT: max sequence length (0 = from position table).  Swin v2: the tokens of one window,
+                         ws^2 (64 for 8 x 8), where the parameter list lacks the buffer relative_coords_table, whose
+                         shape states ws; 0 = from that buffer */
+  int32_t image_size; /* image families: input H = W (0 = 224; Swin v2: 0 = 256) */
   float eps;          /* norm epsilon (0 = family default) */
   float affine_scale; /* AFFINE only */
   float affine_shift; /* AFFINE only */

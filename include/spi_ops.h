@@ -427,6 +427,29 @@ int spi_op_window_attention(int32_t precision, const void* qkv, const float* rel
 int spi_op_s2d_ln(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, const float* gamma,
                   const float* beta, float eps, void* y, void* stream);
 
+/* ---- Swin v2 kernels: same conventions. ---- */
+/* The v2 bias table, host fp32 [(2 ws - 1)^2][heads] (spi_op_window_bias_pack's input), from cpb_mlp's host fp32
+ * weights w0 [hidden][2], b0 [hidden], w2 [heads][hidden]: row (dy + ws - 1)(2 ws - 1) + (dx + ws - 1) holds
+ * 16 sigmoid(w2 relu(w0 (cy, cx) + b0)), c = sign(t) log2(|t| + 1) / 3 at t = 8 d / (ws - 1); double accumulation.
+ * 2 <= ws <= 8, 1 <= hidden <= 65536. */
+int spi_op_window_cpb_table(const float* w0_host, const float* b0_host, const float* w2_host, int32_t hidden,
+                            int32_t window, int32_t heads, float* table_host);
+/* spi_op_window_attention with Swin v2's score in place of (q scale) k^T:
+ *   (q . k) tau[head] / (max(|q|, 1e-12) max(|k|, 1e-12)) + rel_bias + mask,
+ * the norms taken in fp32 over the 32 head dims of the values as stored (torch's F.normalize), tau device fp32
+ * [heads] = exp(min(logit_scale, log 100)), computed by the caller.  The same supported set; tau non-null and
+ * 4-byte aligned. */
+int spi_op_window_attention_cos(int32_t precision, const void* qkv, const float* rel_bias, const float* tau, void* ctx,
+                                int32_t B, int32_t H, int32_t W, int32_t heads, int32_t head_dim, int32_t window,
+                                int32_t shift, void* stream);
+/* y[r] = res[r] + LayerNorm(x[r]) gamma + beta over C (spi_op_ln_rows' C set); x, res and y of the precision's
+ * type, two-pass fp32 statistics; y may be res.  16-byte aligned pointers. */
+int spi_op_ln_rows_add(int32_t precision, const void* x, const void* res, int32_t rows, int32_t C, const float* gamma,
+                       const float* beta, float eps, void* y, void* stream);
+/* spi_op_s2d_ln's gather alone: y [B (H/2) (W/2)][4 C], pixel (2 i + dy, 2 j + dx) of x NHWC at columns
+ * (dx 2 + dy) C, copied as it is.  The same ranges. */
+int spi_op_s2d_rows(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, void* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

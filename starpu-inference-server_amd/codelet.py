@@ -336,7 +336,7 @@ class ModelReplica:
     def __init__(self, module: torch.nn.Module | str | None, device_id: int = 0, precision: str = "fp16",
                  max_batch: int = 8, family: str | None = None, num_heads: int = 0, seq_len: int = 0,
                  image_size: int = 0, eps: float = 0.0, affine: tuple[float, float] = (1.0, 0.0),
-                 graphs: bool = False, bert_io=0, image_io=0, top_k: int = 0):
+                 graphs: bool = False, bert_io=0, image_io=0, top_k: int = 0, window_size: int = 0):
         if isinstance(module, str):
             # The reference's on-disk format: torch::jit::load + the C++ weight
             # extractor in libspi_torch.so (inference_runner.cpp:243-275).
@@ -344,7 +344,7 @@ class ModelReplica:
             ts = TorchScriptModule(module)
             rep = ts.replica(device_id, precision, max_batch, family=family, num_heads=num_heads, seq_len=seq_len,
                              image_size=image_size, eps=eps, graphs=graphs, bert_io=bert_io, image_io=image_io,
-                             top_k=top_k)
+                             top_k=top_k, window_size=window_size)
             self.__dict__.update(rep.__dict__)
             rep.handle = None  # ownership moved to self
             return
@@ -366,7 +366,7 @@ class ModelReplica:
         cfg.precision = PRECISIONS[precision]
         cfg.max_batch = max_batch
         cfg.num_heads = num_heads or (module_num_heads(module) if module is not None else 0)
-        cfg.seq_len = seq_len
+        cfg.seq_len = seq_len or window_size ** 2  # Swin v2 without its relative_coords_table buffer: a window's tokens
         cfg.image_size = image_size
         cfg.eps = eps or (module_layer_norm_eps(module) if module is not None else 0.0)
         cfg.affine_scale, cfg.affine_shift = affine

@@ -1,7 +1,8 @@
 // The ConvNeXt kernels (gfx950): depthwise 7x7 conv + bias + LayerNorm over channels in one pass over an
 // NHWC map, and the two row kernels beside it -- LayerNorm of rows of any C % 32 == 0 (optionally behind a
 // mean over a map's rows) and LayerNorm into the space-to-depth rows of a 2x2 / stride 2 conv -- and Swin's
-// patch merging row kernel s2d_ln (gather the four pixels, then LayerNorm over 4 C).
+// patch merging row kernel s2d_ln (gather the four pixels, then LayerNorm over 4 C).  Swin v2 adds ln_rows_add
+// (the residual-post-norm: res + LN(x)) and s2d_rows (the merge's gather alone; its LayerNorm follows the Linear).
 //
 // dwconv7_ln.  Every channel is its own 49-tap filter: no contraction across channels, nothing for the
 // MFMA, 49 FMAs per output on the VALU and the map read once.  A workgroup of 256 threads owns a TH x TW
@@ -272,6 +273,62 @@ __global__ __launch_bounds__(256) void s2d_ln_kernel(const T* __restrict__ x, T*
       [&](int c, const float(&o)[4]) { store4(dst + c, o); });
 }
 
+// Swin v2's residual-post-norm: y[row] = res[row] + LN(x[row]) gamma + beta, one wave per row, the row of x in
+// registers as in ln_rows_c_kernel.  y may be res (the residual stream updated in place): a lane reads the four
+// addends of a float4 and then stores the same four columns, and no other lane touches them -- hence no
+// __restrict__ on the two.
+template <typename T>
+__global__ __launch_bounds__(256) void ln_rows_add_kernel(const T* __restrict__ x, const T* res, T* y,
+                                                          const float* __restrict__ g, const float* __restrict__ b,
+                                                          int rows, int C, float eps) {
+  constexpr int NV = kDwconvMaxC / 256;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const T* xr = x + (size_t)row * C;
+  float4 v[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int c = (lane + 64 * j) * 4;
+    v[j] = c < C ? load4(xr + c) : float4{0.f, 0.f, 0.f, 0.f};
+  }
+  const T* rr = res + (size_t)row * C;
+  T* dst = y + (size_t)row * C;
+  ln_row_c(
+      C, lane, g, b, eps,
+      [&](int c) {
+        float4 r = v[0];
+#pragma unroll
+        for (int j = 1; j < NV; ++j)
+          if (c >= 256 * j) r = v[j];
+        return r;
+      },
+      [&](int c, const float(&o)[4]) {
+        const float4 a = load4(rr + c);
+        const float sum[4] = {a.x + o[0], a.y + o[1], a.z + o[2], a.w + o[3]};
+        store4(dst + c, sum);
+      });
+}
+
+// Swin v2's patch merging gathers before its Linear and normalises behind it: s2d_ln's gather alone, a copy in
+// 16-byte chunks.  Thread (row, chunk) of y [B (H/2) (W/2)][4 C]: the chunk's column c lies in pixel
+// q = c / C = dx 2 + dy of the row's 2x2 block (C % 32 == 0: a chunk never straddles two pixels).
+template <typename T>
+__global__ __launch_bounds__(256) void s2d_rows_kernel(const T* __restrict__ x, T* __restrict__ y, size_t chunks, int H,
+                                                       int W, int C) {
+  constexpr int EPC = 16 / (int)sizeof(T);
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= chunks) return;
+  const int cpr = 4 * C / EPC;  // chunks per output row
+  const size_t row = i / cpr;
+  const int c = (int)(i % cpr) * EPC, q = c / C;
+  const int W2 = W / 2, H2 = H / 2;
+  const int j2 = (int)(row % W2), i2 = (int)((row / W2) % H2);
+  const size_t img = row / ((size_t)W2 * H2);
+  const T* src = x + ((img * H + 2 * i2 + (q & 1)) * W + 2 * j2 + (q >> 1)) * C + (c - q * C);
+  *reinterpret_cast<uint4*>(y + row * 4 * C + c) = *reinterpret_cast<const uint4*>(src);
+}
+
 void check_rows(const char* what, const void* x, const void* y, const float* g, const float* b, int C) {
   if (!dwconv7_supported(C)) throw std::invalid_argument(std::string(what) + ": C must be a multiple of 32 from 32 to 1536");
   if (!aligned(x, 16) || !aligned(y, 16) || !aligned(g, 16) || !aligned(b, 16))
@@ -351,6 +408,32 @@ void s2d_ln(const void* x, void* y, const float* gamma, const float* beta, int B
     using T = decltype(t);
     SPI_LAUNCH((s2d_ln_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, static_cast<const T*>(x), static_cast<T*>(y),
                gamma, beta, rows, H, W, C, eps);
+  });
+}
+
+void ln_rows_add(const void* x, const void* res, void* y, const float* gamma, const float* beta, int rows, int C,
+                 float eps, bool f16, hipStream_t s) {
+  check_rows("ln_rows_add", x, y, gamma, beta, C);
+  if (!res || !aligned(res, 16)) throw std::invalid_argument("ln_rows_add: a 16-byte aligned res");
+  if (rows < 1) throw std::invalid_argument("ln_rows_add: rows >= 1");
+  with_type(f16, [&](auto t) {
+    using T = decltype(t);
+    SPI_LAUNCH((ln_rows_add_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, static_cast<const T*>(x),
+               static_cast<const T*>(res), static_cast<T*>(y), gamma, beta, rows, C, eps);
+  });
+}
+
+void s2d_rows(const void* x, void* y, int B, int H, int W, int C, bool f16, hipStream_t s) {
+  if (!s2d_ln_supported(C)) throw std::invalid_argument("s2d_rows: C must be a multiple of 32 with 4 C at most 2048");
+  if (!aligned(x, 16) || !aligned(y, 16)) throw std::invalid_argument("s2d_rows: 16-byte aligned x and y");
+  if (B < 1 || H < 2 || W < 2 || H % 2 || W % 2) throw std::invalid_argument("s2d_rows: B >= 1, even H and W");
+  if ((long long)B * H * W > 0x7fffffffLL) throw std::invalid_argument("s2d_rows: too many pixels");
+  const size_t chunks = (size_t)B * H * W * C / (f16 ? 8 : 4);
+  if ((chunks + 255) / 256 > 0x7fffffffULL) throw std::invalid_argument("s2d_rows: too many 16-byte chunks for one grid");
+  with_type(f16, [&](auto t) {
+    using T = decltype(t);
+    SPI_LAUNCH((s2d_rows_kernel<T>), dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, s, static_cast<const T*>(x),
+               static_cast<T*>(y), chunks, H, W, C);
   });
 }
 

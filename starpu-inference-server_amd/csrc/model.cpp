@@ -622,8 +622,20 @@ void Model::body_swin(Workspace& w, int B, hipStream_t s) {
       gemm(m.sw_stem, rows, Act::None, buf[kSwPatches], buf[kSwHidden], nullptr, true);
       ln(buf[kSwHidden], true, buf[out], m.sw_stem_ln, rows, m.sw_stem.n);
     }
+    void ln_add(const void* x, void* xres, const LnW& l, int rows, int C) {  // xres += LN(x): v2's post-norm
+      M.prof_op(s, [&] { return "ln_rows_add_c" + std::to_string(C); }, 0, 3.0 * rows * C * es, [&] {
+        ln_rows_add(x, xres, xres, M.ptr<float>(l.g), M.ptr<float>(l.b), rows, C, m.eps, m.f16, s);
+      });
+    }
     void merge(int B, int H, const SwMerge& g, int in, int out) {
       const int C = g.red.k / 4, rows = B * (H / 2) * (H / 2);
+      if (m.sw_v2) {  // gather (-> kSwLn), Linear (-> kSwCtx), LayerNorm over 2 C (-> out)
+        M.prof_op(s, [&] { return "s2d_rows_c" + std::to_string(C); }, 0, 2.0 * B * H * H * C * es, [&] {
+          s2d_rows(buf[in], buf[kSwLn], B, H, H, C, m.f16, s);
+        });
+        gemm(g.red, rows, Act::None, buf[kSwLn], buf[kSwCtx], nullptr);
+        return ln(buf[kSwCtx], false, buf[out], g.ln, rows, g.red.n);
+      }
       M.prof_op(s, [&] { return "s2d_ln_c" + std::to_string(C); }, 0, 2.0 * B * H * H * C * es, [&] {
         s2d_ln(buf[in], buf[kSwLn], M.ptr<float>(g.ln.g), M.ptr<float>(g.ln.b), B, H, H, C, m.eps, m.f16, s);
       });
@@ -631,6 +643,19 @@ void Model::body_swin(Workspace& w, int B, hipStream_t s) {
     }
     void block(int B, int H, const SwBlock& k, int shift, int x, int t) {
       const int rows = B * H * H, C = k.C, ws = m.sw_window, N = ws * ws;
+      if (m.sw_v2) {  // the residual stream stays in slot x: QKV on it, then x += norm1(proj(attn)), x += norm2(mlp(x))
+        gemm(k.qkv, rows, Act::None, buf[x], buf[kSwQkv], nullptr);
+        M.prof_op(s, [&] { return "window_attn_cos_c" + std::to_string(C) + "_h" + std::to_string(H) + "_s" + std::to_string(shift); },
+                  4.0 * N * kWinHeadDim * (double)rows * k.heads, 4.0 * rows * C * es, [&] {
+                    window_attention_cos(buf[kSwQkv], M.ptr<float>(k.bias), M.ptr<float>(k.tau), buf[kSwCtx], B, H, H, k.heads,
+                                         kWinHeadDim, ws, shift, m.f16, s);
+                  });
+        gemm(k.proj, rows, Act::None, buf[kSwCtx], buf[kSwLn], nullptr);
+        ln_add(buf[kSwLn], buf[x], k.ln1, rows, C);
+        gemm(k.fc1, rows, Act::Gelu, buf[x], buf[kSwHidden], nullptr);
+        gemm(k.fc2, rows, Act::None, buf[kSwHidden], buf[kSwLn], nullptr);
+        return ln_add(buf[kSwLn], buf[x], k.ln2, rows, C);
+      }
       ln(buf[x], false, buf[kSwLn], k.ln1, rows, C);
       gemm(k.qkv, rows, Act::None, buf[kSwLn], buf[kSwQkv], nullptr);
       M.prof_op(s, [&] { return "window_attn_c" + std::to_string(C) + "_h" + std::to_string(H) + "_s" + std::to_string(shift); },

@@ -150,6 +150,8 @@ constexpr bool kVitLnFold = true;
 struct Packer {
   PackedModel m;
   Blob blob;
+  int window_cfg = 0;  // Swin v2's window where no tensor states it: the side of spi_model_config.seq_len = ws^2 tokens
+  bool image_stated = false;  // spi_model_config.image_size > 0
 
   // Pack the [N][K] fp32 matrix at(n, k) into t.w as [npad][kpad] of t.prec (pack.hpp) and set t's
   // geometry.  hilo (F16 only): every 64-k block twice -- fp16(w), then fp16(w - fp16(w)) -- for a
@@ -284,6 +286,7 @@ struct Packer {
   void build_vit(const PMap& p);
   void build_convnext(const PMap& p);
   void build_swin(const PMap& p);
+  SwBlock pack_swin_v2_block(const PMap& p, const std::string& pre, int C, int H, int stage);
 };
 
 void Packer::build_resnet(const PMap& p) {
@@ -671,12 +674,91 @@ void Packer::build_convnext(const PMap& p) {
 // features.1, 3, 5, 7 the stages of SwinTransformerBlocks, features.2, 4, 6 the PatchMerging layers, norm, head.
 // Embed dim, depths, heads per stage and the window are read from the tensors: the bias table is
 // [(2 ws - 1)^2][heads].
+// SwinTransformer v2 (swin_v2_*) has the same layout with SwinTransformerBlockV2 / PatchMergingV2: every attention
+// carries logit_scale [heads,1,1] and cpb_mlp.0.weight [512,2], cpb_mlp.0.bias [512], cpb_mlp.2.weight [heads,512]
+// and none a bias table; the names decide the generation, for the whole model.  Heads come from logit_scale, the
+// window from the buffer relative_coords_table [1][2 ws - 1][2 ws - 1][2] or, without it, from the config.  Packed
+// per block: the bias of 16 sigmoid(cpb_mlp(coords)) (window_cpb_table), tau = exp(min(logit_scale, log 100)), and
+// attn.qkv.bias with its K third zeroed, as torchvision's v2 forward zeroes it on every call.
+SwBlock Packer::pack_swin_v2_block(const PMap& p, const std::string& pre, int C, int H, int stage) {
+  auto refuse = [](const std::string& what) { throw std::runtime_error("swin: " + what); };
+  for (const char* name : {"logit_scale", "cpb_mlp.0.weight", "cpb_mlp.0.bias", "cpb_mlp.2.weight"})
+    if (!has(p, pre + "attn." + name))
+      refuse("Swin-v2: '" + pre + "attn." + name + "' is missing (every attention needs logit_scale, cpb_mlp.0.weight, "
+             "cpb_mlp.0.bias and cpb_mlp.2.weight)");
+  const spi_named_tensor* ls = need(p, pre + "attn.logit_scale");
+  const spi_named_tensor* w0 = need(p, pre + "attn.cpb_mlp.0.weight");
+  const spi_named_tensor* b0 = need(p, pre + "attn.cpb_mlp.0.bias");
+  const spi_named_tensor* w2 = need(p, pre + "attn.cpb_mlp.2.weight");
+  const int heads = (int)numel(ls), ws = m.sw_window;
+  if (heads < 1 || C % heads || C / heads != kWinHeadDim)
+    refuse(pre + "attn: " + std::to_string(C) + " channels over " + std::to_string(heads) + " heads: head_dim must be 32");
+  if (w0->ndim != 2 || w0->shape[1] != 2 || w0->shape[0] < 1 || numel(b0) != w0->shape[0] || w2->ndim != 2 ||
+      w2->shape[0] != heads || w2->shape[1] != w0->shape[0])
+    refuse("Swin-v2: " + pre + "attn.cpb_mlp must be Linear(2, hidden) + bias and Linear(hidden, " + std::to_string(heads) +
+           ") without bias");
+  if (H % ws)
+    refuse("stage " + std::to_string(stage) + "'s map of side " + std::to_string(H) + " (image " + std::to_string(m.image) +
+           ") is no multiple of the window " + std::to_string(ws) + " (padded windows are not served)");
+  SwBlock blk;
+  blk.C = C;
+  blk.heads = heads;
+  std::vector<float> table((size_t)(2 * ws - 1) * (2 * ws - 1) * heads), tau(heads);
+  window_cpb_table(fdata(w0), fdata(b0), fdata(w2), (int)w0->shape[0], ws, heads, table.data());
+  blk.bias = blob.add(nullptr, (size_t)heads * kWinBiasHead * sizeof(float));
+  window_bias_pack(table.data(), ws, heads, reinterpret_cast<float*>(blob.data.data() + blk.bias));
+  for (int h = 0; h < heads; ++h) tau[h] = window_cos_tau(fdata(ls)[h]);
+  blk.tau = pack_vec(tau.data(), heads);
+  blk.ln1 = pack_ln(p, pre + "norm1");
+  blk.ln2 = pack_ln(p, pre + "norm2");
+  const spi_named_tensor* qw = need(p, pre + "attn.qkv.weight");
+  if (qw->ndim != 2 || qw->shape[0] != 3 * C || qw->shape[1] != C)
+    refuse(pre + "attn.qkv.weight must be [" + std::to_string(3 * C) + "][" + std::to_string(C) + "]");
+  std::vector<float> qb(3 * (size_t)C, 0.f);
+  if (has(p, pre + "attn.qkv.bias")) {
+    const spi_named_tensor* b = need(p, pre + "attn.qkv.bias");
+    if (numel(b) != (int64_t)qb.size()) refuse(pre + "attn.qkv.bias must hold " + std::to_string(3 * C) + " values");
+    std::copy(fdata(b), fdata(b) + 3 * C, qb.begin());
+    std::fill(qb.begin() + C, qb.begin() + 2 * C, 0.f);  // the K third
+  }
+  blk.qkv = pack_linear(fdata(qw), qb.data(), 3 * C, C, false);
+  blk.proj = pack_linear_named(p, pre + "attn.proj", false);
+  blk.fc1 = pack_linear_named(p, pre + "mlp.0", false);
+  blk.fc2 = pack_linear_named(p, pre + "mlp.3", false);
+  if (blk.proj.k != C || blk.proj.n != C || blk.fc1.k != C || blk.fc1.n < 1 || blk.fc2.k != blk.fc1.n || blk.fc2.n != C)
+    refuse(pre + "attn.proj / mlp.0 / mlp.3 do not chain over " + std::to_string(C) + " channels");
+  return blk;
+}
+
 void Packer::build_swin(const PMap& p) {
   auto refuse = [](const std::string& what) { throw std::runtime_error("swin: " + what); };
   auto feat = [](int i) { return "features." + std::to_string(i) + "."; };
-  for (const auto& kv : p)
-    if (kv.first.find("logit_scale") != std::string::npos || kv.first.find("cpb_mlp") != std::string::npos)
-      refuse("'" + kv.first + "' is a Swin-v2 parameter (logit_scale / cpb_mlp): only v1 blocks are served");
+  const spi_named_tensor* coords = nullptr;
+  std::string v1_name, v2_name;
+  for (const auto& kv : p) {
+    if (kv.first.find("logit_scale") != std::string::npos || kv.first.find("cpb_mlp") != std::string::npos) v2_name = kv.first;
+    if (ends_with(kv.first, "relative_position_bias_table")) v1_name = kv.first;
+    if (ends_with(kv.first, "relative_coords_table")) coords = kv.second;
+  }
+  if (!v1_name.empty() && !v2_name.empty())
+    refuse("'" + v2_name + "' is a Swin-v2 parameter (logit_scale / cpb_mlp) beside the v1 table '" + v1_name +
+           "': a model is served as one generation");
+  m.sw_v2 = !v2_name.empty();
+  if (m.sw_v2) {
+    int ws = window_cfg;
+    if (coords) {
+      if (coords->ndim != 4 || coords->shape[1] != coords->shape[2] || coords->shape[1] % 2 == 0 || coords->shape[3] != 2)
+        refuse("Swin-v2: relative_coords_table must be [1][2 ws - 1][2 ws - 1][2]");
+      ws = (int)(coords->shape[1] + 1) / 2;
+    }
+    if (ws == 0)
+      refuse("Swin-v2: no tensor states the window (no relative_coords_table buffer): set spi_model_config.seq_len to the "
+             "tokens of a window, ws^2");
+    if (ws < 0) refuse("Swin-v2: seq_len must be the tokens of a square window, ws^2 for ws of 2 .. 8");
+    if (!window_supported(ws)) refuse("Swin-v2: window " + std::to_string(ws) + ": a window ws of 2 .. 8 is served");
+    m.sw_window = ws;
+    if (!image_stated) m.image = 256;  // torchvision's swin_v2_* are trained at 256: 64 / 32 / 16 / 8 maps on 8 x 8 windows
+  }
   if (m.image % 4) refuse("image size " + std::to_string(m.image) + " must be a multiple of 4");
   const spi_named_tensor* sw = need(p, "features.0.0.weight");
   if (sw->ndim != 4 || sw->shape[1] != 3 || sw->shape[2] != 4 || sw->shape[3] != 4)
@@ -696,8 +778,8 @@ void Packer::build_swin(const PMap& p) {
       if (H % 2)
         refuse("the merge before stage " + std::to_string(stage) + " would halve a map of odd side " + std::to_string(H));
       if (!s2d_ln_supported(C))
-        refuse("the merge before stage " + std::to_string(stage) + " normalises rows of " + std::to_string(4 * C) +
-               " columns: at most 2048 (the merge row kernel's range)");
+        refuse("the merge before stage " + std::to_string(stage) + (m.sw_v2 ? " gathers rows of " : " normalises rows of ") +
+               std::to_string(4 * C) + " columns: at most 2048 (the merge row kernel's range)");
       const spi_named_tensor* rw = need(p, pre + "reduction.weight");
       if (rw->ndim != 2 || rw->shape[1] != 4 * C)
         refuse(pre + "reduction.weight must read the " + std::to_string(4 * C) + " gathered columns of stage " + std::to_string(stage - 1));
@@ -708,6 +790,8 @@ void Packer::build_swin(const PMap& p) {
       width_ok(N);
       SwMerge g;
       g.ln = pack_ln(p, pre + "norm");
+      if (m.sw_v2 && numel(need(p, pre + "norm.weight")) != N)
+        refuse(pre + "norm: Swin-v2 normalises the " + std::to_string(N) + " columns behind the reduction");
       g.red = pack_linear_named(p, pre + "reduction", false);
       m.sw_merge.push_back(g);
       C = N;
@@ -718,6 +802,10 @@ void Packer::build_swin(const PMap& p) {
     for (;; ++nb) {
       const std::string pre = feat(2 * stage + 1) + std::to_string(nb) + ".";
       if (!has(p, pre + "attn.qkv.weight")) break;
+      if (m.sw_v2) {
+        m.sw_blocks.push_back(pack_swin_v2_block(p, pre, C, H, stage));
+        continue;
+      }
       const spi_named_tensor* tb = need(p, pre + "attn.relative_position_bias_table");
       if (tb->ndim != 2 || tb->shape[1] < 1) refuse(pre + "attn.relative_position_bias_table must be [(2 ws - 1)^2][heads]");
       int ws = 0;
@@ -777,6 +865,12 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
   m.mixed = cfg.precision == SPI_PREC_F16M && cfg.family != SPI_FAMILY_AFFINE;
   m.heads = cfg.num_heads;
   if (cfg.image_size > 0) m.image = cfg.image_size;
+  for (int w = 1; w <= 256 && cfg.seq_len > 0; ++w)
+    if (w * w >= cfg.seq_len) {
+      pk.window_cfg = w * w == cfg.seq_len ? w : -1;  // -1: not a square
+      break;
+    }
+  pk.image_stated = cfg.image_size > 0;
   PMap p;
   for (int i = 0; i < n; ++i) {
     if (!params[i].name) throw std::runtime_error("parameter without a name");
@@ -789,7 +883,8 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     else if (ends_with(p, "features.0.0.weight") && ends_with(p, "features.1.0.block.0.weight") &&
              ends_with(p, "features.1.0.layer_scale"))
       m.family = SPI_FAMILY_CONVNEXT;
-    else if (ends_with(p, "features.0.0.weight") && ends_with(p, "features.1.0.attn.relative_position_bias_table"))
+    else if (ends_with(p, "features.0.0.weight") && (ends_with(p, "features.1.0.attn.relative_position_bias_table") ||
+                                                     ends_with(p, "features.1.0.attn.logit_scale")))
       m.family = SPI_FAMILY_SWIN;
     else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT/ConvNeXt/Swin parameter names");
   }
@@ -847,7 +942,7 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
           "swin: SPI_PREC_F16X3 and SPI_PREC_F16M are not served for this family; use SPI_PREC_F16 or SPI_PREC_F32");
     m.eps = cfg.eps > 0 ? cfg.eps : 1e-5f;
     pk.build_swin(strip_prefix(p, "features.0.0.weight"));
-    os << "swin[";
+    os << (m.sw_v2 ? "swin_v2[" : "swin[");
     for (size_t i = 0; i < m.stage_blocks.size(); ++i) os << (i ? "," : "") << m.stage_blocks[i];
     os << "] C" << m.sw_dims.front() << " ws" << m.sw_window << " img" << m.image << " classes" << m.classes;
   } else {

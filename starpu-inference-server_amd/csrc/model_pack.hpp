@@ -66,13 +66,16 @@ struct CnDown {  // ConvNeXt stage change: LayerNorm2d, then the 2x2 / stride 2 
 };
 
 struct SwBlock {  // Swin block: norm1, QKV, shifted-window attention (window_attn.hip), proj + x, norm2, MLP + x
+  // v2 (PackedModel::sw_v2), residual-post-norm: QKV on x, cosine attention, proj, x + norm1(.), MLP, x + norm2(.)
   int C = 0, heads = 0;
-  size_t bias = 0;  // fp32 [heads][16][64][4] (swin_pack.hpp: window_bias_pack)
+  size_t bias = 0;  // fp32 [heads][16][64][4] (swin_pack.hpp: window_bias_pack); v2: of window_cpb_table's table
+  size_t tau = 0;   // v2: fp32 [heads], exp(min(logit_scale, log 100))
   LnW ln1, ln2;
   LinearW qkv, proj, fc1, fc2;
 };
 
 struct SwMerge {  // Swin patch merging: gather 2x2 + LayerNorm over 4 C (s2d_ln), then the bias-free Linear 4 C -> 2 C
+  // v2: gather (s2d_rows), the Linear, then LayerNorm over 2 C (ln_rows)
   LnW ln;
   LinearW red;  // torch's [2 C][4 C] as it is
 };
@@ -144,6 +147,7 @@ struct PackedModel {
   std::vector<SwBlock> sw_blocks;
   std::vector<SwMerge> sw_merge;
   int sw_window = 0;
+  bool sw_v2 = false;  // torchvision's swin_v2_*: cosine attention, cpb_mlp bias, post-norm blocks, PatchMergingV2
 
   std::string desc;
   uint64_t digest = 0;  // FNV-1a 64 of the blob

@@ -376,9 +376,10 @@ struct SwGemmVisitor {
     attn_flops += 4.0 * N * N * kWinHeadDim * k.heads * (double)(rows / N);
     hmax = std::max(hmax, (size_t)rows * k.fc1.n);
     on_gemm("qkv", k.qkv, cn_gemm_desc(k.qkv, rows, Act::None, false, false));
-    on_gemm("proj", k.proj, cn_gemm_desc(k.proj, rows, Act::None, true, false));
+    const bool res = !m.sw_v2;  // v2 adds the residual behind the LayerNorm (ln_rows_add), not in the epilogue
+    on_gemm("proj", k.proj, cn_gemm_desc(k.proj, rows, Act::None, res, false));
     on_gemm("fc1", k.fc1, cn_gemm_desc(k.fc1, rows, Act::Gelu, false, false));
-    on_gemm("fc2", k.fc2, cn_gemm_desc(k.fc2, rows, Act::None, true, false));
+    on_gemm("fc2", k.fc2, cn_gemm_desc(k.fc2, rows, Act::None, res, false));
   }
   void tail(int B, int H, int) {
     if (pooled_fc(m, H * H)) on_gemm("avgpool_fc", m.fc, pooled_fc_desc(m, B, H * H));

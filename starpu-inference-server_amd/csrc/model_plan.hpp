@@ -212,6 +212,9 @@ inline int swin_last_side(const PackedModel& m) { return (m.image / 4) >> (m.sta
 //   v.merge(B, H, g, in, out)      gather + LayerNorm of the H x H map in slot in (into kSwLn), Linear into out
 //   v.block(B, H, blk, shift, x, t)  norm1 (x -> kSwLn), QKV (-> kSwQkv), window attention (-> kSwCtx), proj + x -> t,
 //                                  norm2 (t -> kSwLn), Linear + GELU (-> kSwHidden), Linear + t -> x
+//                                  v2 (PackedModel::sw_v2): QKV on x, cosine attention, proj (-> kSwLn), x += norm1(.),
+//                                  Linear + GELU on x, Linear (-> kSwLn), x += norm2(.); t stays unused, and the merge is
+//                                  gather (-> kSwLn), Linear (-> kSwCtx), LayerNorm over 2 C into out
 //   v.tail(B, H, in)               the final LayerNorm of every pixel into kSwLn (and, past 64 pixels, their mean into
 //                                  kSwPooled); the epilogue runs avgpool + FC, or the FC
 template <class V>

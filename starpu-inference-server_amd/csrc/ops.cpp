@@ -386,6 +386,49 @@ int spi_op_s2d_ln(int32_t precision, const void* x, int32_t B, int32_t H, int32_
   });
 }
 
+// ---- Swin v2 kernels (the COS instances of window_attn.hip; ln_rows_add, s2d_rows in dwconv_ln.hip) ----
+
+int spi_op_window_cpb_table(const float* w0, const float* b0, const float* w2, int32_t hidden, int32_t window, int32_t heads,
+                            float* table) {
+  if (!w0 || !b0 || !w2 || !table || heads < 1 || heads > 65535 || hidden < 1 || hidden > 65536)
+    return fail("invalid window cpb table arguments");
+  if (!spi::window_supported(window)) return fail("window cpb table: window must be 2 .. 8");
+  spi::window_cpb_table(w0, b0, w2, hidden, window, heads, table);
+  return 0;
+}
+
+int spi_op_window_attention_cos(int32_t precision, const void* qkv, const float* rel_bias, const float* tau, void* ctx,
+                                int32_t B, int32_t H, int32_t W, int32_t heads, int32_t head_dim, int32_t window,
+                                int32_t shift, void* stream) {
+  if (precision != 0 && precision != 1) return fail("window_attention_cos: precision 0 (fp32) or 1 (fp16)");
+  if (!qkv || !rel_bias || !ctx) return fail("window_attention_cos: null qkv, rel_bias or ctx");
+  if (!tau) return fail("window_attention_cos: null tau");
+  return guarded([&] {
+    spi::window_attention_cos(qkv, rel_bias, tau, ctx, B, H, W, heads, head_dim, window, shift, precision == 1,
+                              static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_ln_rows_add(int32_t precision, const void* x, const void* res, int32_t rows, int32_t C, const float* gamma,
+                       const float* beta, float eps, void* y, void* stream) {
+  if (precision != 0 && precision != 1) return fail("ln_rows_add: precision 0 (fp32) or 1 (fp16)");
+  if (!x || !res || !gamma || !beta || !y) return fail("ln_rows_add: null x, res, gamma, beta or y");
+  return guarded([&] {
+    spi::ln_rows_add(x, res, y, gamma, beta, rows, C, eps, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_s2d_rows(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, void* y, void* stream) {
+  if (precision != 0 && precision != 1) return fail("s2d_rows: precision 0 (fp32) or 1 (fp16)");
+  if (!x || !y) return fail("s2d_rows: null x or y");
+  return guarded([&] {
+    spi::s2d_rows(x, y, B, H, W, C, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
 int spi_op_avgpool_fc(int32_t precision, const void* x, int32_t B, int32_t HW, int32_t C, const void* W, int32_t N,
                       const float* bias, float* y, int32_t act, void* workspace, void* stream) {
   spi::Prec p;

@@ -106,6 +106,17 @@ void window_attention(const void* qkv, const float* rel_bias, void* ctx, int B, 
 // gamma / beta fp32 [4 C].  C % 32 == 0, 4 C <= 2048, even H and W.
 void s2d_ln(const void* x, void* y, const float* gamma, const float* beta, int B, int H, int W, int C, float eps,
             bool f16, hipStream_t s);
+// Swin v2.  window_attention with the score cos(q, k) tau_h + rel_bias + mask: (q . k) tau_h / (max(|q|, 1e-12)
+// max(|k|, 1e-12)), the norms in fp32 over the 32 head dims of the stored values (F.normalize's rule), tau fp32
+// [heads] = exp(min(logit_scale, log 100)) from the host.  Same layouts, addressing, mask and supported set.
+void window_attention_cos(const void* qkv, const float* rel_bias, const float* tau, void* ctx, int B, int H, int W,
+                          int heads, int hd, int window, int shift, bool f16, hipStream_t s);
+// The residual-post-norm: y[r] = res[r] + LN(x[r]) gamma + beta; x, res, y in the compute type, ln_rows' C set,
+// two-pass fp32 statistics.  y may be res.
+void ln_rows_add(const void* x, const void* res, void* y, const float* gamma, const float* beta, int rows, int C,
+                 float eps, bool f16, hipStream_t s);
+// s2d_ln's gather without the LayerNorm (same column order and ranges): PatchMergingV2 normalises behind its Linear.
+void s2d_rows(const void* x, void* y, int B, int H, int W, int C, bool f16, hipStream_t s);
 
 // The kind of an image task's input buffer (SrcKind) and its 8-bit input transform (InputXf): image_src.hpp.
 // The transform of one pixel of channel c.  Contraction is switched off for the two operations:

@@ -2,6 +2,7 @@
 // sizes, the relative-position bias expanded and packed for the attention kernel's accumulator layout, and
 // the shift rule of a block.  Plain C++, shared by the packer (model_pack.cpp), the plan and the op entry points.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 
@@ -38,6 +39,35 @@ inline void window_bias_pack(const float* table, int ws, int heads, float* dst) 
         dst[(((size_t)h * 16 + k / 4) * kWinSlots + q) * 4 + k % 4] = v;
       }
 }
+
+// Swin v2: the bias table is not learnt but computed, 16 sigmoid(cpb_mlp(coords)) -- torchvision's
+// relative_coords_table and cpb_mlp restated.  Row (dy + ws - 1)(2 ws - 1) + (dx + ws - 1), dy, dx in
+// -(ws - 1) .. ws - 1 (window_rel_index's rows), has the coordinates t = 8 d / (ws - 1) mapped to
+// sign(t) log2(|t| + 1) / 3; the MLP is Linear(2, hidden) + bias, ReLU, Linear(hidden, heads) without bias.
+// w0 [hidden][2], b0 [hidden], w2 [heads][hidden] -> table [(2 ws - 1)^2][heads] for window_bias_pack.  Double
+// accumulation, one rounding at the end.  ws >= 2.
+constexpr int kCpbHidden = 512;  // torchvision's cpb_mlp width
+inline void window_cpb_table(const float* w0, const float* b0, const float* w2, int hidden, int ws, int heads, float* table) {
+  const int side = 2 * ws - 1;
+  auto coord = [&](int d) {
+    const double t = 8.0 * d / (ws - 1);
+    return (t < 0 ? -1.0 : t > 0 ? 1.0 : 0.0) * std::log2(std::fabs(t) + 1.0) / 3.0;
+  };
+  for (int iy = 0; iy < side; ++iy)
+    for (int ix = 0; ix < side; ++ix) {
+      const double cy = coord(iy - (ws - 1)), cx = coord(ix - (ws - 1));
+      for (int h = 0; h < heads; ++h) {
+        double acc = 0;
+        for (int j = 0; j < hidden; ++j) {
+          const double a = (double)w0[2 * j] * cy + (double)w0[2 * j + 1] * cx + (double)b0[j];
+          if (a > 0) acc += a * (double)w2[(size_t)h * hidden + j];
+        }
+        table[((size_t)iy * side + ix) * heads + h] = (float)(16.0 / (1.0 + std::exp(-acc)));
+      }
+    }
+}
+// tau_h = exp(min(logit_scale_h, log 100)): torchvision's clamp(logit_scale, max = log 100).exp().
+inline float window_cos_tau(float logit_scale) { return std::exp(std::min(logit_scale, (float)std::log(100.0))); }
 
 // Block i of a stage over a square map of side H: shift 0 for even i, ws / 2 for odd i, forced to 0 where the
 // map equals the window (torchvision zeroes the shift of an axis no longer than the window).

@@ -26,6 +26,20 @@
 //     after the staging barrier -- both wave-uniform, EXEC full around the transposed reads; a query slot at
 //     or past N stores nothing.
 // No atomics, no workspace, one barrier; a launch's bits are fixed.
+//
+// COS (Swin v2): score = cos(q, k) tau_h + bias + mask, tau fp32 [heads] (the clamp is the host's).  K and Q go
+// to the MFMA as they are stored and the two normalisations are factors of the fp32 score epilogue, in place of
+// the scale: no operand is rounded a second time and LDS is not read twice.
+//   * 1 / max(|k|, 1e-12) per key, from the staging registers: thread t holds chunk t % CPR of key t / CPR, so
+//     the squares of its 8 (fp16) / 4 (fp32) elements are summed in fp32 and added over the CPR neighbouring
+//     lanes by xor shuffles (1, 2 and, fp32, 4); the lane of chunk 0 writes the factor to a 64-float LDS array in
+//     front of the one barrier (fp32: 32 keys per staging round).  Accumulator element r of block j is key
+//     16 j + 4 fq + r: a lane's four factors are one 16-byte LDS read, the same address over a lane group;
+//   * tau_h / max(|q|, 1e-12) per lane: the lane holds head dims 8 fq .. 8 fq + 7 of its query, so their squares
+//     plus the xor shuffles 16 and 32 are |q|^2;
+//   * both from 1.f / sqrtf, each correctly rounded (the compiler's default for HIP; no approximate rsq);
+//   * a padded key (rows N .. 63 are zero) has factor 1e12 and accumulator exactly 0, a dead query slot factor
+//     tau 1e12: the products stay finite (<= 100 * 1e24), so 0 inf never arises, and the -inf bias drops the key.
 #include <stdexcept>
 #include <string>
 
@@ -53,10 +67,11 @@ __device__ __forceinline__ int shift_region(int p, int L, int ws, int shift) {
   return p < L - ws ? 0 : p < L - shift ? 1 : 2;
 }
 
-template <typename T>
+// SP: the scale (v1), or tau [heads] (COS).
+template <typename T, bool COS, typename SP>
 __global__ __launch_bounds__(256) void window_attn_kernel(const T* __restrict__ qkv, const float* __restrict__ bias,
                                                           T* __restrict__ ctx, int H, int W, int heads, int ws,
-                                                          int shift, float scale) {
+                                                          int shift, SP scale) {
   constexpr bool F16 = sizeof(T) == 2;
   constexpr int HD = kWinHeadDim, NS = kWinSlots;
   constexpr int EPC = 16 / (int)sizeof(T);  // elements per 16-byte chunk
@@ -68,6 +83,7 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const T* __restrict__ 
   __shared__ __attribute__((aligned(16))) T Ks[NS * LD];
   __shared__ __attribute__((aligned(16))) T Vs[NS * LD];
   __shared__ __attribute__((aligned(16))) unsigned char reg[NS];
+  __shared__ __attribute__((aligned(16))) float kinv[COS ? NS : 4];  // COS: 1 / max(|k|, 1e-12) per key slot
 
   const int N = ws * ws, nwx = W / ws, nwy = H / ws;
   const int win = blockIdx.x, h = blockIdx.y;
@@ -117,6 +133,21 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const T* __restrict__ 
     const int key = c / CPR, dc = c % CPR;
     *reinterpret_cast<uint4*>(Ks + key * LD + dc * EPC) = kreg[i];
     *reinterpret_cast<uint4*>(Vs + key * LD + dc * EPC) = vreg[i];
+    if constexpr (COS) {
+      float ss = 0.f;
+      if constexpr (F16) {
+        const half8 kh = __builtin_bit_cast(half8, kreg[i]);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ss += (float)kh[e] * (float)kh[e];
+      } else {
+        const floatx4 kf = __builtin_bit_cast(floatx4, kreg[i]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ss += kf[e] * kf[e];
+      }
+#pragma unroll
+      for (int o = 1; o < CPR; o <<= 1) ss += __shfl_xor(ss, o, 64);
+      if (dc == 0) kinv[key] = 1.f / fmaxf(sqrtf(ss), 1e-12f);
+    }
   }
   if (tid < NS) {
     const int t = tid < N ? tid : 0;
@@ -129,6 +160,18 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const T* __restrict__ 
   const int nblk = (N + 15) >> 4;  // live 16-key blocks
   const float* bh = bias + (size_t)h * kWinBiasHead + (size_t)qa * 4;
   const int qreg = masked ? reg[qa] : 0;
+  float qfac = 0.f;  // COS: tau_h / max(|q|, 1e-12)
+  if constexpr (COS) {
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float v = F16 ? (float)qh[e] : qf[e >> 2][e & 3];
+      ss += v * v;
+    }
+    ss += __shfl_xor(ss, 16, 64);
+    ss += __shfl_xor(ss, 32, 64);
+    qfac = scale[h] * (1.f / fmaxf(sqrtf(ss), 1e-12f));
+  }
   float sc[4][4];
   float tmax = -INFINITY;
 #pragma unroll
@@ -154,9 +197,13 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const T* __restrict__ 
     const floatx4 bv = *reinterpret_cast<const floatx4*>(bh + (size_t)(j * 4 + fq) * (kWinSlots * 4));
     unsigned kregs = 0;
     if (masked) kregs = *reinterpret_cast<const unsigned*>(reg + j * 16 + fq * 4);
+    floatx4 kfac = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (COS) kfac = *reinterpret_cast<const floatx4*>(kinv + j * 16 + fq * 4);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float v = acc[r] * scale + bv[r];
+      float v;
+      if constexpr (COS) v = acc[r] * kfac[r] * qfac + bv[r];
+      else v = acc[r] * scale + bv[r];
       if (masked && (int)((kregs >> (8 * r)) & 0xff) != qreg) v += -100.0f;
       sc[j][r] = v;
       tmax = fmaxf(tmax, v);
@@ -225,27 +272,47 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const T* __restrict__ 
 
 }  // namespace
 
-void window_attention(const void* qkv, const float* rel_bias, void* ctx, int B, int H, int W, int heads, int hd,
-                      int window, int shift, float scale, bool f16, hipStream_t s) {
-  if (hd != kWinHeadDim)
-    throw std::invalid_argument("window_attention: head_dim " + std::to_string(hd) + " is not served (32)");
+namespace {
+
+void check_window(const std::string& what, const void* qkv, const float* rel_bias, const void* ctx, int B, int H, int W,
+                  int heads, int hd, int window, int shift) {
+  if (hd != kWinHeadDim) throw std::invalid_argument(what + ": head_dim " + std::to_string(hd) + " is not served (32)");
   if (!window_supported(window))
-    throw std::invalid_argument("window_attention: window " + std::to_string(window) + " is not served (2 .. 8: at most 64 tokens)");
+    throw std::invalid_argument(what + ": window " + std::to_string(window) + " is not served (2 .. 8: at most 64 tokens)");
   if (B < 1 || H < window || W < window || H % window || W % window)
-    throw std::invalid_argument("window_attention: H " + std::to_string(H) + " and W " + std::to_string(W) +
+    throw std::invalid_argument(what + ": H " + std::to_string(H) + " and W " + std::to_string(W) +
                                 " must be positive multiples of the window " + std::to_string(window));
   if (shift < 0 || shift >= window)
-    throw std::invalid_argument("window_attention: shift " + std::to_string(shift) + " must be in 0 .. window - 1");
+    throw std::invalid_argument(what + ": shift " + std::to_string(shift) + " must be in 0 .. window - 1");
   const long long windows = (long long)B * (H / window) * (W / window);
   if (heads < 1 || heads > 65535 || windows > 0x7fffffffLL)
-    throw std::invalid_argument("window_attention: heads (at most 65535) and B (H / ws) (W / ws) (below 2^31) are the grid");
+    throw std::invalid_argument(what + ": heads (at most 65535) and B (H / ws) (W / ws) (below 2^31) are the grid");
   if (!aligned(qkv, 16) || !aligned(ctx, 16) || !aligned(rel_bias, 16))
-    throw std::invalid_argument("window_attention: 16-byte aligned qkv, ctx and rel_bias");
-  const dim3 grid((unsigned)windows, (unsigned)heads);
+    throw std::invalid_argument(what + ": 16-byte aligned qkv, ctx and rel_bias");
+}
+
+}  // namespace
+
+void window_attention(const void* qkv, const float* rel_bias, void* ctx, int B, int H, int W, int heads, int hd,
+                      int window, int shift, float scale, bool f16, hipStream_t s) {
+  check_window("window_attention", qkv, rel_bias, ctx, B, H, W, heads, hd, window, shift);
+  const dim3 grid((unsigned)(B * (H / window) * (W / window)), (unsigned)heads);
   with_type(f16, [&](auto t) {
     using T = decltype(t);
-    SPI_LAUNCH((window_attn_kernel<T>), grid, dim3(256), 0, s, static_cast<const T*>(qkv), rel_bias, static_cast<T*>(ctx),
-               H, W, heads, window, shift, scale);
+    SPI_LAUNCH((window_attn_kernel<T, false, float>), grid, dim3(256), 0, s, static_cast<const T*>(qkv), rel_bias,
+               static_cast<T*>(ctx), H, W, heads, window, shift, scale);
+  });
+}
+
+void window_attention_cos(const void* qkv, const float* rel_bias, const float* tau, void* ctx, int B, int H, int W,
+                          int heads, int hd, int window, int shift, bool f16, hipStream_t s) {
+  check_window("window_attention_cos", qkv, rel_bias, ctx, B, H, W, heads, hd, window, shift);
+  if (!tau || !aligned(tau, 4)) throw std::invalid_argument("window_attention_cos: tau must be a 4-byte aligned fp32 [heads]");
+  const dim3 grid((unsigned)(B * (H / window) * (W / window)), (unsigned)heads);
+  with_type(f16, [&](auto t) {
+    using T = decltype(t);
+    SPI_LAUNCH((window_attn_kernel<T, true, const float*>), grid, dim3(256), 0, s, static_cast<const T*>(qkv), rel_bias,
+               static_cast<T*>(ctx), H, W, heads, window, shift, tau);
   });
 }
 

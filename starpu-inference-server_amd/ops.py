@@ -280,6 +280,51 @@ def s2d_ln(prec, x_nhwc, gamma, beta, eps, out, stream=None):
     return out
 
 
+# ---- Swin v2 kernels (spi_ops.h: spi_op_window_cpb_table, _window_attention_cos, _ln_rows_add, _s2d_rows) ----
+
+
+def window_cpb_table(w0, b0, w2, window) -> np.ndarray:
+    """cpb_mlp's weights (cpb_mlp.0.weight [hidden][2], cpb_mlp.0.bias [hidden], cpb_mlp.2.weight [heads][hidden]) ->
+    the v2 bias table [(2 ws - 1)^2][heads], host fp32: 16 sigmoid(cpb_mlp(log-spaced coordinates))."""
+    w0, b0, w2 = (np.ascontiguousarray(np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=np.float32))
+                  for t in (w0, b0, w2))
+    if w0.ndim != 2 or w0.shape[1] != 2 or b0.shape != w0.shape[:1] or w2.ndim != 2 or w2.shape[1] != w0.shape[0]:
+        raise ValueError(f"window_cpb_table: w0 [hidden][2], b0 [hidden], w2 [heads][hidden], got {w0.shape}, {b0.shape}, {w2.shape}")
+    table = np.empty(((2 * window - 1) ** 2, w2.shape[0]), np.float32)
+    _check(lib.spi_op_window_cpb_table(w0.ctypes.data, b0.ctypes.data, w2.ctypes.data, w0.shape[0], window, w2.shape[0],
+                                       table.ctypes.data))
+    return table
+
+
+def window_cpb_bias(w0, b0, w2, window, device="cuda") -> torch.Tensor:
+    """window_attention_cos's packed bias from cpb_mlp's weights: window_bias(window_cpb_table(...))."""
+    return window_bias(window_cpb_table(w0, b0, w2, window), window, device=device)
+
+
+def window_attention_cos(prec, qkv, rel_bias, tau, B, H, W_, heads, window, shift, stream=None, out=None, head_dim=32):
+    """window_attention with Swin v2's scores cos(q, k) tau[head] + bias + mask; tau: device fp32 [heads], the
+    clamped temperature exp(min(logit_scale, log 100))."""
+    if out is None:
+        out = torch.empty((B * H * W_, heads * head_dim), dtype=qkv.dtype, device=qkv.device)
+    _check(lib.spi_op_window_attention_cos(PREC[prec], _ptr(qkv), _ptr(rel_bias), _ptr(tau), _ptr(out), B, H, W_, heads,
+                                           head_dim, window, shift, _stream(stream)))
+    return out
+
+
+def ln_rows_add(prec, x, res, rows, c, gamma, beta, eps, out, stream=None):
+    """out [rows][C] = res + LayerNorm(x) gamma + beta, all of prec's type; out may be res."""
+    _check(lib.spi_op_ln_rows_add(PREC[prec], _ptr(x), _ptr(res), rows, c, _ptr(gamma), _ptr(beta), eps, _ptr(out),
+                                  _stream(stream)))
+    return out
+
+
+def s2d_rows(prec, x_nhwc, out, stream=None):
+    """out [B (H/2) (W/2)][4 C] = patch merging's gathered rows (s2d_ln's order), not normalised."""
+    B, H, W_, c = x_nhwc.shape
+    _check(lib.spi_op_s2d_rows(PREC[prec], _ptr(x_nhwc), B, H, W_, c, _ptr(out), _stream(stream)))
+    return out
+
+
 def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None, out=None, head_dim=64):
     """ctx [B S][D] of packed qkv [B S][3 D], D = heads * head_dim (32 or 64); out: the buffer to write
     (default: a fresh one).  prec may be the integer precision code itself."""

@@ -17,11 +17,13 @@ what the CPU codelet (and the test oracle) runs.
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 from typing import Sequence
 
 import torch
 from torch import nn
+from torch.nn import functional as F
 
 
 # ---------------------------------------------------------------------------
@@ -353,7 +355,7 @@ def convnext_large(seed: int = 0, image: int = 224, **kw) -> ConvNeXt:
 
 
 # ---------------------------------------------------------------------------
-# Swin Transformer (torchvision.models.swin_transformer naming, v1 blocks)
+# Swin Transformer (torchvision.models.swin_transformer naming, v1 and v2 blocks)
 # ---------------------------------------------------------------------------
 class ShiftedWindowAttention(nn.Module):
     def __init__(self, dim: int, window: int, shift: int, heads: int):
@@ -374,11 +376,9 @@ class ShiftedWindowAttention(nn.Module):
             x = torch.roll(x, shifts=(-sy, -sx), dims=(1, 2))
         nw = (H // ws) * (W // ws)
         x = x.view(B, H // ws, ws, W // ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B * nw, N, C)
-        qkv = self.qkv(x).reshape(B * nw, N, 3, self.heads, C // self.heads).permute(2, 0, 3, 1, 4)
-        q, k, v = qkv[0] * (C // self.heads) ** -0.5, qkv[1], qkv[2]
-        attn = q @ k.transpose(-2, -1)
-        bias = self.relative_position_bias_table[self.relative_position_index].view(N, N, -1).permute(2, 0, 1)
-        attn = attn + bias.unsqueeze(0)
+        qkv = self.project_qkv(x).reshape(B * nw, N, 3, self.heads, C // self.heads).permute(2, 0, 3, 1, 4)
+        v = qkv[2]
+        attn = self.logits(qkv[0], qkv[1]) + self.position_bias().unsqueeze(0)
         if sy or sx:
             mask = x.new_zeros((H, W))
             count = 0
@@ -399,17 +399,67 @@ class ShiftedWindowAttention(nn.Module):
         return x
 
 
+    def project_qkv(self, x):
+        return self.qkv(x)
+
+    def logits(self, q, k):
+        return (q * q.shape[-1] ** -0.5) @ k.transpose(-2, -1)
+
+    def position_bias(self):  # [heads, N, N]
+        N = self.window ** 2
+        return self.relative_position_bias_table[self.relative_position_index].view(N, N, -1).permute(2, 0, 1)
+
+
+class ShiftedWindowAttentionV2(ShiftedWindowAttention):
+    """torchvision's v2 attention: cosine scores under a learnt per-head temperature clamped at 100, the bias
+    16 sigmoid(cpb_mlp(log-spaced relative coordinates)), and a K projection without bias (zeroed on every call)."""
+
+    def __init__(self, dim: int, window: int, shift: int, heads: int):
+        super().__init__(dim, window, shift, heads)
+        del self.relative_position_bias_table
+        self.logit_scale = nn.Parameter(torch.log(10 * torch.ones((heads, 1, 1))))
+        self.cpb_mlp = nn.Sequential(nn.Linear(2, 512, bias=True), nn.ReLU(inplace=True), nn.Linear(512, heads, bias=False))
+        r = torch.arange(-(window - 1), window, dtype=torch.float32)
+        table = torch.stack(torch.meshgrid([r, r], indexing="ij")).permute(1, 2, 0).contiguous().unsqueeze(0)
+        table = table / (window - 1) * 8
+        self.register_buffer("relative_coords_table", torch.sign(table) * torch.log2(torch.abs(table) + 1.0) / 3.0)
+
+    def project_qkv(self, x):
+        bias, n = self.qkv.bias.clone(), self.qkv.bias.numel() // 3
+        bias[n:2 * n].zero_()
+        return F.linear(x, self.qkv.weight, bias)
+
+    def logits(self, q, k):
+        attn = F.normalize(q, dim=-1) @ F.normalize(k, dim=-1).transpose(-2, -1)
+        return attn * torch.clamp(self.logit_scale, max=math.log(100.0)).exp()
+
+    def position_bias(self):
+        N = self.window ** 2
+        table = self.cpb_mlp(self.relative_coords_table).view(-1, self.heads)
+        return 16 * torch.sigmoid(table[self.relative_position_index].view(N, N, -1).permute(2, 0, 1))
+
+
 class SwinTransformerBlock(nn.Module):
+    attention = ShiftedWindowAttention
+
     def __init__(self, dim: int, heads: int, window: int, shift: int):
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=1e-5)
-        self.attn = ShiftedWindowAttention(dim, window, shift, heads)
+        self.attn = self.attention(dim, window, shift, heads)
         self.norm2 = nn.LayerNorm(dim, eps=1e-5)
         self.mlp = nn.Sequential(nn.Linear(dim, 4 * dim), nn.GELU(), nn.Dropout(0.0), nn.Linear(4 * dim, dim), nn.Dropout(0.0))
 
     def forward(self, x):  # eval: stochastic depth is the identity
         x = x + self.attn(self.norm1(x))
         return x + self.mlp(self.norm2(x))
+
+
+class SwinTransformerBlockV2(SwinTransformerBlock):  # residual-post-norm
+    attention = ShiftedWindowAttentionV2
+
+    def forward(self, x):
+        x = x + self.norm1(self.attn(x))
+        return x + self.norm2(self.mlp(x))
 
 
 class PatchMerging(nn.Module):
@@ -423,15 +473,28 @@ class PatchMerging(nn.Module):
         return self.reduction(self.norm(x))
 
 
-class SwinTransformer(nn.Module):
-    def __init__(self, depths: Sequence[int], heads: Sequence[int], embed: int, window: int = 7, num_classes: int = 1000):
+class PatchMergingV2(nn.Module):
+    def __init__(self, dim: int):
         super().__init__()
+        self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
+        self.norm = nn.LayerNorm(2 * dim, eps=1e-5)
+
+    def forward(self, x):  # the LayerNorm behind the Linear
+        x = torch.cat([x[..., 0::2, 0::2, :], x[..., 1::2, 0::2, :], x[..., 0::2, 1::2, :], x[..., 1::2, 1::2, :]], -1)
+        return self.norm(self.reduction(x))
+
+
+class SwinTransformer(nn.Module):
+    def __init__(self, depths: Sequence[int], heads: Sequence[int], embed: int, window: int = 7, num_classes: int = 1000,
+                 v2: bool = False):
+        super().__init__()
+        block, merge = (SwinTransformerBlockV2, PatchMergingV2) if v2 else (SwinTransformerBlock, PatchMerging)
         layers = [nn.Sequential(nn.Conv2d(3, embed, 4, 4), Permute([0, 2, 3, 1]), nn.LayerNorm(embed, eps=1e-5))]
         for i, (depth, nh) in enumerate(zip(depths, heads)):
             dim = embed * 2 ** i
             if i > 0:
-                layers.append(PatchMerging(dim // 2))
-            layers.append(nn.Sequential(*[SwinTransformerBlock(dim, nh, window, 0 if j % 2 == 0 else window // 2)
+                layers.append(merge(dim // 2))
+            layers.append(nn.Sequential(*[block(dim, nh, window, 0 if j % 2 == 0 else window // 2)
                                           for j in range(depth)]))
         self.features = nn.Sequential(*layers)
         feat = embed * 2 ** (len(depths) - 1)
@@ -466,6 +529,45 @@ def swin(depths: Sequence[int], heads: Sequence[int], embed: int, window: int = 
             elif isinstance(m, ShiftedWindowAttention):
                 m.relative_position_bias_table.normal_()
     return model.eval()
+
+
+def swin_v2(depths: Sequence[int], heads: Sequence[int], embed: int, window: int = 8, image: int = 256,
+            num_classes: int = 1000, seed: int = 0) -> SwinTransformer:
+    """Swin Transformer v2 (torchvision's swin_v2_* naming and forward) with seeded random weights, initialised
+    in the spirit of swin(): N(0, 1 / fan_in) weights, re-drawn LayerNorms.  logit_scale is uniform in
+    log 3 .. log 200, so the heads' temperatures span 3 .. 100 and about a sixth of them sit at the clamp;
+    cpb_mlp's second layer is four times N(0, 1 / 512) and its first bias N(0, 0.5^2), so the bias
+    16 sigmoid(.) ranges over several units inside a window.  The post-norm branches are LayerNorm outputs
+    (unit size) beside a residual stream that starts at unit size: none is negligible."""
+    torch.manual_seed(seed)
+    model = SwinTransformer(depths, heads, embed, window, num_classes, v2=True)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, (nn.Conv2d, nn.Linear)):
+                m.weight.normal_(std=m.weight[0].numel() ** -0.5)
+                if m.bias is not None:
+                    m.bias.normal_(std=0.05)
+            elif isinstance(m, nn.LayerNorm):
+                m.weight.copy_(1.0 + 0.1 * torch.randn_like(m.weight))
+                m.bias.copy_(0.05 * torch.randn_like(m.bias))
+        for m in model.modules():
+            if isinstance(m, ShiftedWindowAttentionV2):
+                m.logit_scale.uniform_(math.log(3.0), math.log(200.0))
+                m.cpb_mlp[0].bias.normal_(std=0.5)
+                m.cpb_mlp[2].weight.mul_(4.0)
+    return model.eval()
+
+
+def swin_v2_t(seed: int = 0, image: int = 256, **kw) -> SwinTransformer:
+    return swin_v2([2, 2, 6, 2], [3, 6, 12, 24], 96, image=image, seed=seed, **kw)
+
+
+def swin_v2_s(seed: int = 0, image: int = 256, **kw) -> SwinTransformer:
+    return swin_v2([2, 2, 18, 2], [3, 6, 12, 24], 96, image=image, seed=seed, **kw)
+
+
+def swin_v2_b(seed: int = 0, image: int = 256, **kw) -> SwinTransformer:
+    return swin_v2([2, 2, 18, 2], [4, 8, 16, 32], 128, image=image, seed=seed, **kw)
 
 
 def swin_t(seed: int = 0, image: int = 224, **kw) -> SwinTransformer:
@@ -703,6 +805,9 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
         "swin_t": swin_t,
         "swin_s": swin_s,
         "swin_b": swin_b,
+        "swin_v2_t": swin_v2_t,
+        "swin_v2_s": swin_v2_s,
+        "swin_v2_b": swin_v2_b,
         "bert-base-uncased": bert_base,
         "bert_base": bert_base,
         "minilm_l6": minilm_l6,
@@ -720,6 +825,7 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
 # name is not an identifier, so give the zoo's modules a loadable qualified name
 # (a traced/scripted model must round-trip through .pt like the reference's).
 for _cls in (BasicBlock, Bottleneck, ResNet, MLPBlock, EncoderBlock, Encoder, VisionTransformer, LayerNorm2d, Permute,
-             CNBlock, ConvNeXt, ShiftedWindowAttention, SwinTransformerBlock, PatchMerging, SwinTransformer, BertWrapper,
+             CNBlock, ConvNeXt, ShiftedWindowAttention, ShiftedWindowAttentionV2, SwinTransformerBlock, SwinTransformerBlockV2,
+             PatchMerging, PatchMergingV2, SwinTransformer, BertWrapper,
              BertTupleWrapper, BertSegmentsWrapper, BertHeadWrapper, AddConstant):
     _cls.__module__ = "spi_zoo"

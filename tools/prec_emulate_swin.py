@@ -7,7 +7,8 @@ merge's gathered + normalised rows and its Linear; the stem GEMM, the relative-p
 fp32.  Prints the normalised max error against the float64 forward of the same module: the figure the fp16 parity
 bar of tests/test_swin_gpu.py is 1.5x of.  Needs torch only (zoo.py is loaded by path, not the package).
 
-  python tools/prec_emulate_swin.py [--seeds 1 2 3] [--embed 64 --heads 2 4 8]
+  python tools/prec_emulate_swin.py [--seeds 1 2 3] [--embed 64 --heads 2 4 8] [--v2 --image 128]
+--v2: zoo.swin_v2 (cosine attention with the norms in the fp32 score epilogue, post-norm blocks, PatchMergingV2).
 """
 import argparse
 import importlib.util
@@ -36,8 +37,13 @@ def window_attention(a, qkv, r, c):
     nw = (H // ws) * (W // ws)
     x = x.view(B, H // ws, ws, W // ws, ws, C3).permute(0, 1, 3, 2, 4, 5).reshape(B * nw, N, 3, a.heads, C // a.heads)
     q, k, v = x.permute(2, 0, 3, 1, 4)
-    attn = (q @ k.transpose(-2, -1)) * (C // a.heads) ** -0.5
-    attn = attn + c(a.relative_position_bias_table)[a.relative_position_index].view(N, N, -1).permute(2, 0, 1)
+    if isinstance(a, zoo.ShiftedWindowAttentionV2):  # raw operands to the MFMA, the norms and tau in the fp32 epilogue
+        qn, kn = (t.norm(dim=-1, keepdim=True).clamp_min(1e-12) for t in (q, k))
+        attn = (q @ k.transpose(-2, -1)) / kn.transpose(-2, -1) / qn * c(a.logit_scale).clamp(max=np.log(100.0)).exp()
+        attn = attn + c(a.position_bias())
+    else:
+        attn = (q @ k.transpose(-2, -1)) * (C // a.heads) ** -0.5
+        attn = attn + c(a.relative_position_bias_table)[a.relative_position_index].view(N, N, -1).permute(2, 0, 1)
     if s:
         lab = torch.zeros(H, W, dtype=attn.dtype)
         for i, hs in enumerate((slice(0, -ws), slice(-ws, -s), slice(-s, None))):
@@ -65,7 +71,18 @@ def forward(model, x, r, dt):
             g = torch.cat([y[:, 0::2, 0::2], y[:, 1::2, 0::2], y[:, 0::2, 1::2], y[:, 1::2, 1::2]], -1)
             y = r(lin(r(ln(g, layer.norm)), layer.reduction))
             continue
+        if isinstance(layer, zoo.PatchMergingV2):  # gather, Linear, then the LayerNorm
+            g = torch.cat([y[:, 0::2, 0::2], y[:, 1::2, 0::2], y[:, 0::2, 1::2], y[:, 1::2, 1::2]], -1)
+            y = r(ln(r(lin(g, layer.reduction)), layer.norm))
+            continue
         for blk in layer:
+            if isinstance(blk, zoo.SwinTransformerBlockV2):  # post-norm; the K third of the QKV bias is zero
+                kb = torch.cat([torch.ones(y.shape[-1]), torch.zeros(y.shape[-1]), torch.ones(y.shape[-1])]).to(dt)
+                qkv = r(y @ r(c(blk.attn.qkv.weight)).T + c(blk.attn.qkv.bias) * kb)
+                y = r(y + ln(r(lin(r(window_attention(blk.attn, qkv, r, c)), blk.attn.proj)), blk.norm1))
+                hid = r(F.gelu(lin(y, blk.mlp[0])))
+                y = r(y + ln(r(lin(hid, blk.mlp[3])), blk.norm2))
+                continue
             qkv = r(lin(r(ln(y, blk.norm1)), blk.attn.qkv))
             y = r(lin(r(window_attention(blk.attn, qkv, r, c)), blk.attn.proj) + y)
             hid = r(F.gelu(lin(r(ln(y, blk.norm2)), blk.mlp[0])))
@@ -83,8 +100,10 @@ def main():
     ap.add_argument("--image", type=int, default=112)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--acc", choices=["f32", "f64"], default="f32")
+    ap.add_argument("--v2", action="store_true", help="zoo.swin_v2 at window 8 (tests/test_swin_v2_gpu.py: --v2 --image 128)")
     a = ap.parse_args()
-    model = zoo.swin(a.depths, a.heads, a.embed, window=7, image=a.image, num_classes=10)
+    model = (zoo.swin_v2(a.depths, a.heads, a.embed, window=8, image=a.image, num_classes=10) if a.v2 else
+             zoo.swin(a.depths, a.heads, a.embed, window=7, image=a.image, num_classes=10))
     for seed in a.seeds:
         x = torch.from_numpy(np.random.default_rng(seed).random((a.batch, 3, a.image, a.image), dtype=np.float32))
         with torch.no_grad():
