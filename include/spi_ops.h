@@ -194,6 +194,22 @@ int spi_op_attention(int32_t precision, const void* qkv, const float* mask_bias,
  * rejected before any launch, like the above).  spi_op_attention is this with head_dim 64. */
 int spi_op_attention_hd(int32_t precision, const void* qkv, const float* mask_bias, void* ctx, int32_t B,
                         int32_t S, int32_t heads, int32_t head_dim, float scale, void* stream);
+/* Attention with a relative-position bias (MPNet): scores q k^T scale + rel_rows[head][half + key - query] + mask_bias,
+ * each term added in fp32 in that order.  rel_rows: device fp32 [heads][ld], one generator row per head, entry
+ * half + d the bias of every pair with key - query = d (a Toeplitz bias; no [S][S] matrix exists anywhere).  The
+ * same kernels, routing and rejections as spi_op_attention_hd, and also rejected before any launch: head_dim other
+ * than 64, S > 512, S - 1 > half, ld < 2 half + 1, rel_rows null or off 16-byte alignment.  Entries outside
+ * half - (S - 1) .. half + (S - 1) of a row may be read but never reach an output; they must be finite. */
+int spi_op_attention_rel(int32_t precision, const void* qkv, const float* mask_bias, const float* rel_rows, int32_t ld,
+                         int32_t half, void* ctx, int32_t B, int32_t S, int32_t heads, int32_t head_dim, float scale,
+                         void* stream);
+/* The generator rows of a bucketed bias table (host to host): table_host fp32 [nb][heads] (MPNet's
+ * encoder.relative_attention_bias.weight) -> dst_host fp32 [heads][*ld], *ld = 2 P - 1 rounded up to a multiple of
+ * 4, entry (h, d + P - 1) = table[bucket(d)][h] for d = key - query in -(P - 1) .. P - 1, the padding zero; the
+ * rows serve every S <= P with half = P - 1.  bucket is HF's MPNetEncoder.relative_position_bucket(d, nb,
+ * max_distance), the log in fp32.  nb a multiple of 4 in 4 .. 128, 1 <= P <= 512, max_distance > nb / 4. */
+int spi_op_rel_bias_rows(const float* table_host, int32_t nb, int32_t max_distance, int32_t heads, int32_t P,
+                         float* dst_host, int32_t* ld);
 
 /* Row LayerNorm: x fp32 [rows][D] -> yf fp32 and/or yt (fp16 when precision fp16). */
 int spi_op_layernorm(int32_t precision, const float* x, const float* gamma, const float* beta,

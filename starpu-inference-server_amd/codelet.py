@@ -132,7 +132,8 @@ _FAMILIES = {None: N.FAMILY_AUTO, "auto": N.FAMILY_AUTO, "resnet": N.FAMILY_RESN
 BERT_IO = {"pooler": N.BERT_OUT_POOLER, "mean": N.BERT_OUT_MEAN, "no_hidden": N.BERT_NO_HIDDEN,
            "token_types": N.BERT_TOKEN_TYPES, "seq_head": N.BERT_HEAD_SEQUENCE, "token_head": N.BERT_HEAD_TOKEN,
            "qa_head": N.BERT_HEAD_QA, "roberta_positions": N.BERT_POS_FROM_IDS}
-ROBERTA_MODEL_TYPES = ("roberta", "xlm-roberta", "camembert")  # HF config.model_type values with RoBERTa's position rule
+# HF config.model_type values with RoBERTa's position rule (an MPNet replica gets it from its names as well)
+ROBERTA_MODEL_TYPES = ("roberta", "xlm-roberta", "camembert", "mpnet")
 
 
 def bert_io_bits(bert_io) -> int:

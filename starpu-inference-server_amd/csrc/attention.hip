@@ -13,6 +13,7 @@
 // 16-key block of S^T, O^T is two 16-wide blocks (two transposed V reads per 32-key step), and a K / V row is
 // four 16-byte chunks.
 #include "lds_dma.hpp"
+#include "rel_bias_pack.hpp"
 #include "spi_kernels.hpp"
 
 #include <cstdlib>
@@ -26,11 +27,52 @@ namespace {
 constexpr int QT = 64;
 constexpr int KT = 64;
 
-template <typename T, int HD>
+// The relative-bias variant (REL instances of both kernels): every score gets
+// rows[head][half + key - query] added in fp32, after the scale and before the mask bias -- a Toeplitz bias
+// from one generator row per head (rel_bias_pack.hpp), ld floats apart.  A workgroup of Q queries from q0
+// copies the part of its head's row it can address into LDS before the key loop, under the loop's own first
+// barriers: distances -(q0 + Q - 1) .. SR - 1 - q0, SR = S rounded up to whole key tiles, i.e. also the pairs
+// whose key or query lies past S (their scores are -inf through the bias, or never stored; the copy holds 0
+// wherever the distance leaves the row, so they stay finite).  The copy starts at the 16-byte boundary at or below
+// its first float: 16-byte global loads and LDS stores, single floats only for a chunk across a row end.
+// A lane then reads lds[off + key - query]: in either orientation the 16 lanes of a group hold
+// consecutive keys (or queries) and the four groups lie 4 apart, 28 consecutive words per ds_read_b32 --
+// no two lanes on one bank with different addresses.  The other instances take the operand and ignore it.
+struct RelRows {
+  const float* rows = nullptr;
+  int ld = 0, half = 0;
+};
+// Floats of the copy for a workgroup of Q queries over sequences up to SMAX: the distances above at q0 = 0,
+// up to 3 floats of alignment slack in front, whole 16-byte chunks.
+constexpr int rel_slice_floats(int Q, int SMAX) { return ((SMAX + KT - 1) / KT * KT + Q - 1 + 3 + 3) / 4 * 4; }
+
+// Stage the copy with the first N / 4 threads; returns off, for lds[off + key - query].
+template <int N, int NT>
+__device__ __forceinline__ int rel_stage(float* lds, const RelRows& rel, int h, int q0, int Q, int tid) {
+  static_assert(N % 4 == 0 && N / 4 <= NT, "one 16-byte chunk per thread");
+  const int lo = h * rel.ld, hi = lo + 2 * rel.half;  // the head's row, as indices into rows
+  const int g0 = lo + rel.half - (q0 + Q - 1);        // the last query against key 0; below lo where S - 1 < that
+  const int ga = g0 & ~3;                             // floors negative values too
+  if (tid < N / 4) {
+    const int c = ga + 4 * tid;
+    floatx4 v = {0.f, 0.f, 0.f, 0.f};
+    if (c >= lo && c + 3 <= hi) {
+      v = *reinterpret_cast<const floatx4*>(rel.rows + c);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (c + e >= lo && c + e <= hi) v[e] = rel.rows[c + e];
+    }
+    *reinterpret_cast<floatx4*>(lds + 4 * tid) = v;
+  }
+  return g0 - ga + q0 + Q - 1;
+}
+
+template <typename T, int HD, bool REL = false>
 __global__ __launch_bounds__(256) void attn_kernel(const T* __restrict__ qkv,
                                                    const float* __restrict__ mask_bias,
                                                    T* __restrict__ ctx, int S, int H,
-                                                   float scale) {
+                                                   float scale, RelRows rel) {
   constexpr int EPC = 16 / (int)sizeof(T);
   constexpr int LD = HD + EPC;   // K row stride
   constexpr int VLD = KT + EPC;  // V^T / P row stride
@@ -97,6 +139,13 @@ __global__ __launch_bounds__(256) void attn_kernel(const T* __restrict__ qkv,
     }
   };
   fetch(0);
+  // REL: this lane's bias of key k0 + 16 j + fr for query row r is relq[k0 + 16 j - r]
+  const float* relq = nullptr;
+  if constexpr (REL) {
+    constexpr int RELN = rel_slice_floats(QT, kRelMaxSeq);
+    __shared__ __attribute__((aligned(16))) float rel_s[RELN];
+    relq = rel_s + rel_stage<RELN, 256>(rel_s, rel, h, q0, QT, tid) + fr - (q0 + wave * 16 + fq * 4);
+  }
   for (int k0 = 0; k0 < S; k0 += KT) {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the previous tile's Ks / Vt reads are done
 #pragma unroll
@@ -148,7 +197,10 @@ __global__ __launch_bounds__(256) void attn_kernel(const T* __restrict__ qkv,
       float tmax = -INFINITY;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        sc[j] = sacc[j][r] * scale + bias[j];
+        if constexpr (REL)
+          sc[j] = sacc[j][r] * scale + relq[k0 + j * 16 - r] + bias[j];
+        else
+          sc[j] = sacc[j][r] * scale + bias[j];
         tmax = fmaxf(tmax, sc[j]);
       }
 #pragma unroll
@@ -242,11 +294,11 @@ constexpr bool tr_rows_disjoint(int row_bytes) {
   return true;
 }
 
-template <int NW, int SK, int HD>
+template <int NW, int SK, int HD, bool REL = false>
 __global__ __launch_bounds__(64 * NW) void attn_f16_swapped_kernel(const _Float16* __restrict__ qkv,
                                                                const float* __restrict__ mask_bias,
                                                                _Float16* __restrict__ ctx, int S, int H,
-                                                               float scale) {
+                                                               float scale, RelRows rel) {
   typedef short short4v __attribute__((ext_vector_type(4)));
   typedef __attribute__((address_space(3))) short4v lds_s4;
   // K / V row stride in elements (16-byte rows, 8-byte tr reads).  HD 64: HD + 8, 144 B, as measured
@@ -312,6 +364,16 @@ __global__ __launch_bounds__(64 * NW) void attn_f16_swapped_kernel(const _Float1
   // head-dim block dblk: row 32 s + 16 t + 4 fq + fr / 4, columns 16 dblk + 4 (fr % 4)
   const int tr_off = ((4 * fq + (fr >> 2)) * LD + 4 * (fr & 3)) * 2;
   const bool live = q0 + wave * 16 < S;  // wave-uniform
+  // REL: this lane's bias of key k0 + 16 j + 4 fq + r is relq[k0 + 16 j + r].  Staged by every wave, live or
+  // not, behind the first K / V loads' issue and in front of the barriers below
+  const float* relq = nullptr;
+  auto stage_rel = [&] {
+    if constexpr (REL) {
+      constexpr int RELN = rel_slice_floats(16 * NW, SK ? SK : kRelMaxSeq);
+      __shared__ __attribute__((aligned(16))) float rel_s[RELN];
+      relq = rel_s + rel_stage<RELN, NT>(rel_s, rel, h, q0, 16 * NW, tid) + fq * 4 - qa;
+    }
+  };
   if constexpr (SK > 0) {
     // the whole sequence: SK * HD / 8 16-byte chunks of K and of V, rows past S zero (V's rows
     // past S meet P = 0 in the last 32-key step, so they must be finite); the last round's chunks
@@ -337,10 +399,12 @@ __global__ __launch_bounds__(64 * NW) void attn_f16_swapped_kernel(const _Float1
         *reinterpret_cast<uint4*>(Vs + key * LD + dc * 8) = vw[i];
       }
     }
+    stage_rel();
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     if (!live) return;  // no barrier follows
   } else {
     fetch(0);
+    stage_rel();
   }
   for (int k0 = 0; k0 < S; k0 += KT) {
     if constexpr (SK == 0) {
@@ -386,7 +450,10 @@ __global__ __launch_bounds__(64 * NW) void attn_f16_swapped_kernel(const _Float1
       for (int r = 0; r < 4; ++r) {
         const int key = k0 + j * 16 + fq * 4 + r;
         const float bias = key < S ? (mask_bias ? mask_bias[(size_t)b * S + key] : 0.f) : -INFINITY;
-        sc[j][r] = sacc[j][r] * scale + bias;
+        if constexpr (REL)
+          sc[j][r] = sacc[j][r] * scale + relq[k0 + j * 16 + r] + bias;
+        else
+          sc[j][r] = sacc[j][r] * scale + bias;
         tmax = fmaxf(tmax, sc[j][r]);
       }
     tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
@@ -459,10 +526,10 @@ void attention_reload_env() { g_attn_whole = -1; }
 // fp16: the swapped orientation, 8-wave workgroups of 128 queries for S > 128 (ViT-L's 197),
 // 4 waves of 64 queries otherwise; fp32: the round-2 orientation (the round-2 fp16 kernel
 // and the forced 4 / 8-wave variants were removed in round 4).  The same routing
-// at both head widths.
-template <int HD>
+// at both head widths, and for the REL instances (rel is their operand, else ignored).
+template <int HD, bool REL = false>
 static void attention_hd(const void* qkv, const float* mask_bias, void* ctx, int B, int S, int heads, float scale,
-                         bool f16, hipStream_t s) {
+                         bool f16, hipStream_t s, RelRows rel = {}) {
   const dim3 grid((S + QT - 1) / QT, B * heads);
 #ifndef SPI_ATTN_S8_MIN  // variant builds: the 8-wave kernel from this sequence length on
 #define SPI_ATTN_S8_MIN 129
@@ -472,21 +539,22 @@ static void attention_hd(const void* qkv, const float* mask_bias, void* ctx, int
     // whole-sequence staging up to 224 keys (64.5 KiB: two workgroups per CU), tiles beyond;
     // the 16-wave form stages K / V once per head instead of once per 128 queries
     const int whole = attn_knobs_whole();
-    if (whole == 2 && S <= 224)  // one 16-wave workgroup per (batch, head): K / V staged once per head
-      SPI_LAUNCH((attn_f16_swapped_kernel<16, 224, HD>), dim3((S + 255) / 256, B * heads), dim3(1024), 0, s,
-                 (const _Float16*)qkv, mask_bias, (_Float16*)ctx, S, heads, scale);
-    else if (whole && S <= 224)
-      SPI_LAUNCH((attn_f16_swapped_kernel<8, 224, HD>), g8, dim3(512), 0, s, (const _Float16*)qkv, mask_bias,
-                 (_Float16*)ctx, S, heads, scale);
-    else
-      SPI_LAUNCH((attn_f16_swapped_kernel<8, 0, HD>), g8, dim3(512), 0, s, (const _Float16*)qkv, mask_bias,
-                 (_Float16*)ctx, S, heads, scale);
+    if (whole == 2 && S <= 224) {  // one 16-wave workgroup per (batch, head): K / V staged once per head
+      SPI_LAUNCH((attn_f16_swapped_kernel<16, 224, HD, REL>), dim3((S + 255) / 256, B * heads), dim3(1024), 0, s,
+                 (const _Float16*)qkv, mask_bias, (_Float16*)ctx, S, heads, scale, rel);
+    } else if (whole && S <= 224) {
+      SPI_LAUNCH((attn_f16_swapped_kernel<8, 224, HD, REL>), g8, dim3(512), 0, s, (const _Float16*)qkv, mask_bias,
+                 (_Float16*)ctx, S, heads, scale, rel);
+    } else {
+      SPI_LAUNCH((attn_f16_swapped_kernel<8, 0, HD, REL>), g8, dim3(512), 0, s, (const _Float16*)qkv, mask_bias,
+                 (_Float16*)ctx, S, heads, scale, rel);
+    }
   } else if (f16) {
-    SPI_LAUNCH((attn_f16_swapped_kernel<4, 0, HD>), grid, dim3(256), 0, s, (const _Float16*)qkv, mask_bias,
-                       (_Float16*)ctx, S, heads, scale);
+    SPI_LAUNCH((attn_f16_swapped_kernel<4, 0, HD, REL>), grid, dim3(256), 0, s, (const _Float16*)qkv, mask_bias,
+                       (_Float16*)ctx, S, heads, scale, rel);
   } else {
-    SPI_LAUNCH((attn_kernel<float, HD>), grid, dim3(256), 0, s, (const float*)qkv,
-                       mask_bias, (float*)ctx, S, heads, scale);
+    SPI_LAUNCH((attn_kernel<float, HD, REL>), grid, dim3(256), 0, s, (const float*)qkv,
+                       mask_bias, (float*)ctx, S, heads, scale, rel);
   }
 }
 
@@ -498,6 +566,22 @@ void attention(const void* qkv, const float* mask_bias, void* ctx, int B, int S,
     attention_hd<32>(qkv, mask_bias, ctx, B, S, heads, scale, f16, s);
   else
     throw std::invalid_argument("attention: head_dim " + std::to_string(hd) + " is not served (32 or 64)");
+}
+
+void attention_rel(const void* qkv, const float* mask_bias, const float* rel_rows, int rel_ld, int rel_half, void* ctx,
+                   int B, int S, int heads, int hd, float scale, bool f16, hipStream_t s) {
+  if (hd != kRelHeadDim)
+    throw std::invalid_argument("attention_rel: head_dim " + std::to_string(hd) + " is not served (64 only)");
+  if (S > kRelMaxSeq)
+    throw std::invalid_argument("attention_rel: S " + std::to_string(S) + " is not served (at most " +
+                                std::to_string(kRelMaxSeq) + ")");
+  if (!rel_rows || (reinterpret_cast<uintptr_t>(rel_rows) & 15))
+    throw std::invalid_argument("attention_rel: rel_rows must be non-null and 16-byte aligned");
+  if (S - 1 > rel_half || rel_half >= (1 << 24) || rel_ld < 2 * rel_half + 1 || (int64_t)heads * rel_ld > INT32_MAX)
+    throw std::invalid_argument("attention_rel: rows of " + std::to_string(rel_ld) + " floats centred at " +
+                                std::to_string(rel_half) + " do not hold the distances of S " + std::to_string(S) +
+                                " (S - 1 <= half, ld >= 2 half + 1)");
+  attention_hd<kRelHeadDim, true>(qkv, mask_bias, ctx, B, S, heads, scale, f16, s, RelRows{rel_rows, rel_ld, rel_half});
 }
 
 }  // namespace spi

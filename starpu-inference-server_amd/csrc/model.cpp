@@ -199,6 +199,17 @@ void Model::run_qkv_attention(int layer, const void* x, const float* in_stats, v
   const int D = m_.D, heads = m_.heads, T = B * S, hd = D / heads;
   const float scale = 1.0f / std::sqrt((float)hd);
   const float* mask = w.has_mask ? w.mask_bias : nullptr;
+  if (m_.rel_buckets) {  // MPNet: the QKV GEMM and the relative-bias attention (the fused kernel has no such form)
+    LnPtrs ln;
+    ln.in_stats = in_stats;
+    run_tf_gemm(layer, kQkv, T, x, qkv, nullptr, w, s, ln);
+    prof_op(s, [&] { return "attention_rel_S" + std::to_string(S); }, 4.0 * B * S * S * D,
+            (double)T * 4 * D * (m_.f16 ? 2 : 4) + (double)heads * m_.rel_ld * 4, [&] {
+              attention_rel(qkv, mask, ptr<float>(m_.rel_rows), m_.rel_ld, m_.rel_half, ctx, B, S, heads, hd, scale,
+                            m_.f16, s);
+            });
+    return;
+  }
   if (qkv_fused_ > 0 && S <= (qkv_fused_ >= 2 ? 256 : 128) && m_.f16 && L.prec == Prec::F16 &&
       qkv_attention_eligible(S, heads, hd, L.k, L.kpad, L.krep, D, L.kpad) && (!in_stats || L.c1)) {
     prof_op(s, [&] { return "qkv_attention_S" + std::to_string(S); }, 2.0 * T * L.n * (double)L.k + 4.0 * B * S * S * D,

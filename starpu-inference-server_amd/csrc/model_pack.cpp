@@ -13,6 +13,7 @@
 #include <stdexcept>
 
 #include "convnext_pack.hpp"
+#include "rel_bias_pack.hpp"
 #include "swin_pack.hpp"
 #include "gconv.hpp"
 #include "ln_fold_pack.hpp"
@@ -444,6 +445,36 @@ void Packer::build_bert(const PMap& p, const PMap& all) {
   const spi_named_tensor* pe = need(p, "embeddings.position_embeddings.weight");
   m.maxpos = (int)pe->shape[0];
   check_heads();
+  auto layer = [](int i) { return "encoder.layer." + std::to_string(i) + "."; };
+  // MPNet is told apart by its names: the bucket table beside attention.attn.{q,k,v,o}.  One without the other, or
+  // either beside BERT's attention.self.query, is refused.
+  const std::string rel_name = "encoder.relative_attention_bias.weight";
+  const bool rel_tab = has(p, rel_name), mp_attn = has(p, layer(0) + "attention.attn.q.weight");
+  const bool mpnet = rel_tab && mp_attn;
+  if ((rel_tab || mp_attn) && (!mpnet || has(p, layer(0) + "attention.self.query.weight")))
+    throw std::runtime_error("bert: mixed BERT and MPNet attention names: '" + rel_name + "' and '" + layer(0) +
+                             "attention.attn.q.weight' need each other and exclude '" + layer(0) +
+                             "attention.self.query.weight'");
+  if (mpnet) {
+    const spi_named_tensor* rt = need(p, rel_name);
+    if (m.D / m.heads != kRelHeadDim)
+      throw std::runtime_error("mpnet: '" + rel_name + "': the relative-bias attention serves 64-wide heads only, hidden " +
+                               std::to_string(m.D) + " over " + std::to_string(m.heads) + " heads is " +
+                               std::to_string(m.D / m.heads));
+    if (rt->ndim != 2 || rt->shape[1] != m.heads)
+      throw std::runtime_error("mpnet: '" + rel_name + "' must be [nb][heads] with heads = " + std::to_string(m.heads));
+    if (!rel_buckets_supported((int)std::min<int64_t>(rt->shape[0], 1 << 20)))
+      throw std::runtime_error("mpnet: '" + rel_name + "' has " + std::to_string(rt->shape[0]) +
+                               " buckets; served: a multiple of 4 in 4 .. 128");
+    if (m.bert_io & SPI_BERT_TOKEN_TYPES)
+      throw std::runtime_error("bert_io: SPI_BERT_TOKEN_TYPES: an MPNet replica has no token-type table");
+    m.rel_buckets = (int)rt->shape[0];
+    m.pos_from_ids = true;  // HF's MPNet counts positions from the ids, pad id 1, as RoBERTa does
+    if (m.seq > kRelMaxSeq)
+      throw std::runtime_error("mpnet: seq_len " + std::to_string(m.seq) + ": the relative-bias attention serves at most " +
+                               std::to_string(kRelMaxSeq) + " tokens");
+    if (m.seq <= 0) m.seq = std::min(m.maxpos - 2, kRelMaxSeq);  // checked against the table below
+  }
   if (m.pos_from_ids) {
     // position ids run 2 .. S + 1 (row 1 is the pad token's, row 0 unused), so the table serves rows - 2 tokens
     const std::string rule = "position table has " + std::to_string(m.maxpos) +
@@ -457,18 +488,24 @@ void Packer::build_bert(const PMap& p, const PMap& all) {
   if (m.seq <= 0) m.seq = m.maxpos;
   m.word = pack_vec(fdata(we), (int)numel(we));
   m.pos = pack_vec(fdata(pe), (int)numel(pe));
-  const spi_named_tensor* te = need(p, "embeddings.token_type_embeddings.weight");
-  m.type0 = pack_vec(fdata(te), D);  // token_type_ids buffer is all zeros
+  const spi_named_tensor* te = mpnet ? nullptr : need(p, "embeddings.token_type_embeddings.weight");
+  m.type0 = te ? pack_vec(fdata(te), D) : blob.add(nullptr, sizeof(float) * D);  // token_type_ids buffer is all zeros
   m.emb_ln = pack_ln(p, "embeddings.LayerNorm");
-  auto layer = [](int i) { return "encoder.layer." + std::to_string(i) + "."; };
-  while (has(p, layer(m.layers) + "attention.self.query.weight")) ++m.layers;
+  // HF's names of the layer's tensors: BERT's, or MPNet's (attention.attn.{q,k,v,o}, attention.LayerNorm)
+  const char* qkv_names[3] = {mpnet ? "attention.attn.q" : "attention.self.query", mpnet ? "attention.attn.k" : "attention.self.key",
+                              mpnet ? "attention.attn.v" : "attention.self.value"};
+  const char* out_name = mpnet ? "attention.attn.o" : "attention.output.dense";
+  const char* ln1_name = mpnet ? "attention.LayerNorm" : "attention.output.LayerNorm";
+  while (has(p, layer(m.layers) + qkv_names[0] + ".weight")) ++m.layers;
   if (m.layers == 0) throw std::runtime_error("bert: no encoder layers");
+  if (const std::string other = layer(m.layers) + (mpnet ? "attention.self.query" : "attention.attn.q") + ".weight"; has(p, other))
+    throw std::runtime_error("bert: mixed BERT and MPNet attention names: '" + other + "' follows " +
+                             std::to_string(m.layers) + " layers of the other kind");
   // Q, K, V stacked into one [3D][D] projection.
   std::vector<float> qw((size_t)3 * D * D), qb((size_t)3 * D);
   auto stack_qkv = [&](const std::string& pre) {
-    const char* names[3] = {"query", "key", "value"};
     for (int j = 0; j < 3; ++j) {
-      const std::string nm = pre + "attention.self." + names[j];
+      const std::string nm = pre + qkv_names[j];
       std::memcpy(qw.data() + (size_t)j * D * D, fdata(need(p, nm + ".weight")), sizeof(float) * D * D);
       std::memcpy(qb.data() + (size_t)j * D, fdata(need(p, nm + ".bias")), sizeof(float) * D);
     }
@@ -478,8 +515,8 @@ void Packer::build_bert(const PMap& p, const PMap& all) {
     TfLayer L;
     stack_qkv(pre);
     L.qkv = pack_linear(qw.data(), qb.data(), 3 * D, D, m.mixed);
-    L.out = pack_linear_named(p, pre + "attention.output.dense", m.mixed);
-    L.ln1 = pack_ln(p, pre + "attention.output.LayerNorm");
+    L.out = pack_linear_named(p, pre + out_name, m.mixed);
+    L.ln1 = pack_ln(p, pre + ln1_name);
     L.ff1 = pack_linear_named(p, pre + "intermediate.dense", m.mixed);
     L.ff2 = pack_linear_named(p, pre + "output.dense", m.mixed);
     L.ln2 = pack_ln(p, pre + "output.LayerNorm");
@@ -492,14 +529,13 @@ void Packer::build_bert(const PMap& p, const PMap& all) {
   for (int i = 0; m.ln_fold && i < m.layers; ++i) {
     const std::string pre = layer(i);
     m.tf[i].ff1 = pack_linear_folded(fdata(need(p, pre + "intermediate.dense.weight")),
-                                     fdata(need(p, pre + "intermediate.dense.bias")), m.ffn, D, p,
-                                     pre + "attention.output.LayerNorm");
+                                     fdata(need(p, pre + "intermediate.dense.bias")), m.ffn, D, p, pre + ln1_name);
     if (i == 0) continue;
     stack_qkv(pre);
     m.tf[i].qkv = pack_linear_folded(qw.data(), qb.data(), 3 * D, D, p, layer(i - 1) + "output.LayerNorm");
   }
   // bert_io appends only: a replica without bits keeps the blob above, byte for byte
-  m.type_vocab = (int)te->shape[0];
+  m.type_vocab = te ? (int)te->shape[0] : 1;
   if (m.bert_io & SPI_BERT_TOKEN_TYPES) {
     if (te->ndim != 2 || te->shape[1] != D) throw std::runtime_error("bert: token_type_embeddings.weight must be [types][D]");
     m.type_table = pack_vec(fdata(te), (int)numel(te));
@@ -531,6 +567,13 @@ void Packer::build_bert(const PMap& p, const PMap& all) {
     m.pool_b = pack_vec(fdata(pb), D);
   }
   if (m.bert_io & (SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA)) pack_bert_head(all, two_layer);
+  if (mpnet) {  // the bias rows for the replica's longest sequence, behind everything else
+    m.rel_ld = rel_rows_ld(m.seq);
+    m.rel_half = m.seq - 1;
+    m.rel_rows = blob.add(nullptr, sizeof(float) * m.heads * m.rel_ld);
+    rel_bias_rows(fdata(need(p, rel_name)), m.rel_buckets, kMpnetMaxDistance, m.heads, m.seq,
+                  reinterpret_cast<float*>(blob.data.data() + m.rel_rows));
+  }
 }
 
 void Packer::build_vit(const PMap& p) {
@@ -965,6 +1008,7 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     os << " out[" << outs << "] in[ids,mask" << ((m.bert_io & SPI_BERT_TOKEN_TYPES) ? ",types]" : "]");
   }
   if (m.pos_from_ids) os << " pos[ids]";
+  if (m.rel_buckets) os << " relbias" << m.rel_buckets;
   m.desc = os.str();
   m.blob = std::move(pk.blob.data);
   m.blob_bytes = m.blob.size();

@@ -122,6 +122,12 @@ struct PackedModel {
   // dense as pool_w / pool_b and out_proj as the head: the same two launches compute it.
   int num_labels = 0;
   size_t head_w = 0, head_b = 0;
+  // MPNet (told by its names: encoder.relative_attention_bias.weight [nb][heads] beside attention.attn.{q,k,v,o}):
+  // post-LN BERT whose every attention adds a bucketed relative-position bias.  rel_rows: the generator rows fp32
+  // [heads][rel_ld] (rel_bias_pack.hpp) packed once for seq tokens, rel_half = seq - 1, appended last; rel_buckets
+  // = nb, 0 for every other replica.  No token-type table (type0 is a zero row); pos_from_ids is implied.
+  int rel_buckets = 0, rel_ld = 0, rel_half = 0;
+  size_t rel_rows = 0;
   LnW emb_ln, final_ln;
   std::vector<TfLayer> tf;
   // ViT

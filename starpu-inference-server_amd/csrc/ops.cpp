@@ -14,6 +14,7 @@
 #include "gemm_plan.hpp"
 #include "ln_fold_pack.hpp"
 #include "pack.hpp"
+#include "rel_bias_pack.hpp"
 #include "resample.hpp"
 #include "row_util.hpp"
 #include "spi_kernels.hpp"
@@ -598,6 +599,34 @@ int spi_op_attention_hd(int32_t precision, const void* qkv, const float* mask_bi
     return fail("attention: 16-byte aligned qkv and 8-byte aligned ctx");
   return guarded([&] {
     spi::attention(qkv, mask_bias, ctx, B, S, heads, head_dim, scale, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+// ---- The relative-bias attention variant (the REL instances of attention.hip, rel_bias_pack.hpp) ----
+
+int spi_op_rel_bias_rows(const float* table, int32_t nb, int32_t max_distance, int32_t heads, int32_t P, float* dst,
+                         int32_t* ld) {
+  if (!table || !dst || !ld || heads < 1 || heads > 65535) return fail("invalid rel_bias_rows arguments");
+  if (!spi::rel_buckets_supported(nb)) return fail("rel_bias_rows: nb must be a multiple of 4 in 4 .. 128");
+  if (P < 1 || P > spi::kRelMaxSeq) return fail("rel_bias_rows: P must be 1 .. 512");
+  if (max_distance <= nb / 4) return fail("rel_bias_rows: max_distance must exceed nb / 4");
+  spi::rel_bias_rows(table, nb, max_distance, heads, P, dst);
+  *ld = spi::rel_rows_ld(P);
+  return 0;
+}
+
+int spi_op_attention_rel(int32_t precision, const void* qkv, const float* mask_bias, const float* rel_rows, int32_t ld,
+                         int32_t half, void* ctx, int32_t B, int32_t S, int32_t heads, int32_t head_dim, float scale,
+                         void* stream) {
+  if ((precision != 0 && precision != 1) || !qkv || !ctx || B <= 0 || S <= 0 || heads <= 0 || half < 0)
+    return fail("invalid attention_rel arguments");
+  if ((int64_t)B * heads > 65535) return fail("attention_rel: B * heads is the grid's y extent, at most 65535");
+  if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (reinterpret_cast<uintptr_t>(ctx) & 7))
+    return fail("attention_rel: 16-byte aligned qkv and 8-byte aligned ctx");
+  return guarded([&] {  // head_dim, S, rel_rows, ld and half: the launcher refuses them by name before any launch
+    spi::attention_rel(qkv, mask_bias, rel_rows, ld, half, ctx, B, S, heads, head_dim, scale, precision == 1,
+                       static_cast<hipStream_t>(stream));
     return check_launch();
   });
 }

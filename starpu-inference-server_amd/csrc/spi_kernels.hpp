@@ -244,5 +244,11 @@ void affine(const float* x, float* y, size_t n, float scale, float shift,
 // mask_bias: fp32 [B, S] additive bias or nullptr.
 void attention(const void* qkv, const float* mask_bias, void* ctx, int B, int S,
                int heads, int hd, float scale, bool f16, hipStream_t s);
+// The same with a relative-position bias: softmax(q k^T * scale + rel_rows[h][rel_half + key - query] + mask_bias[b]) v,
+// the REL instances of the same kernels under the same routing.  rel_rows: device fp32 [heads][rel_ld], one
+// generator row per head (rel_bias_pack.hpp), 16-byte aligned, rel_ld >= 2 rel_half + 1, S - 1 <= rel_half.
+// hd 64 and S <= 512 only; throws std::invalid_argument outside that, before any launch.
+void attention_rel(const void* qkv, const float* mask_bias, const float* rel_rows, int rel_ld, int rel_half, void* ctx,
+                   int B, int S, int heads, int hd, float scale, bool f16, hipStream_t s);
 
 }  // namespace spi

@@ -336,6 +336,35 @@ def attention(prec, qkv, B, S, heads, mask_bias=None, scale=0.125, stream=None, 
     return ctx
 
 
+def rel_bias_rows(table, P, max_distance=128) -> np.ndarray:
+    """A bucketed relative-position table [nb][heads] (MPNet's encoder.relative_attention_bias.weight) -> the
+    generator rows attention_rel takes, host fp32 [heads][ld]: entry (h, d + P - 1) = table[bucket(d)][h] for
+    d = key - query, ld = 2 P - 1 rounded up to a multiple of 4, the padding zero.  Serves every S <= P at
+    half = P - 1."""
+    table = np.ascontiguousarray(np.asarray(table.detach().cpu() if isinstance(table, torch.Tensor) else table,
+                                            dtype=np.float32))
+    if table.ndim != 2:
+        raise ValueError(f"rel_bias_rows: table [nb][heads], got {table.shape}")
+    nb, heads = table.shape
+    rows = np.empty((heads, (2 * max(P, 1) + 2) // 4 * 4), np.float32)
+    ld = C.c_int32(0)
+    _check(lib.spi_op_rel_bias_rows(table.ctypes.data, nb, max_distance, heads, P, rows.ctypes.data, C.byref(ld)))
+    assert ld.value == rows.shape[1]
+    return rows
+
+
+def attention_rel(prec, qkv, rel_rows, half, B, S, heads, mask_bias=None, scale=0.125, stream=None, out=None,
+                  head_dim=64, ld=None):
+    """attention with rel_rows[head][half + key - query] added to every score before the mask bias; rel_rows:
+    device fp32 [heads][ld] (rel_bias_rows at P: half = P - 1; default ld the rows' length).  head_dim 64,
+    S <= 512, S - 1 <= half, ld >= 2 half + 1."""
+    ld = (2 * half + 1 if rel_rows is None else rel_rows.shape[-1]) if ld is None else ld
+    ctx = torch.empty(B * S, heads * head_dim, device=qkv.device, dtype=qkv.dtype) if out is None else out
+    _check(lib.spi_op_attention_rel(PREC.get(prec, prec), _ptr(qkv), _ptr(mask_bias), _ptr(rel_rows), ld, half,
+                                    _ptr(ctx), B, S, heads, head_dim, scale, _stream(stream)))
+    return ctx
+
+
 def layernorm(prec, x, gamma, beta, eps, stream=None):
     rows, D = x.shape
     yf = torch.empty_like(x)

@@ -640,7 +640,10 @@ class BertHeadWrapper(nn.Module):
 
     @property
     def bert(self) -> nn.Module:
-        return self.model.bert if hasattr(self.model, "bert") else self.model.roberta
+        for name in ("bert", "roberta", "mpnet"):  # HF's attribute for the encoder of a head model
+            if hasattr(self.model, name):
+                return getattr(self.model, name)
+        raise AttributeError("BertHeadWrapper: the head model has no .bert, .roberta or .mpnet")
 
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor):
         out = self.bert(input_ids=input_ids, attention_mask=attention_mask, return_dict=False)
@@ -777,6 +780,63 @@ def xlm_roberta_large(seed: int = 0, **kw) -> nn.Module:
     return roberta(**{**dict(layers=24, hidden=1024, heads=16, intermediate=4096, vocab=250002), **kw}, seed=seed)
 
 
+def mpnet(layers: int = 12, hidden: int = 768, heads: int = 12, intermediate: int = 3072,
+          vocab: int = 30527, max_position: int = 514, seed: int = 0, init_std: float = 0.02,
+          head: str | None = None, num_labels: int = 2, outputs=("hidden",), buckets: int = 32) -> nn.Module:
+    """HF MPNetModel in BertWrapper (pad_token_id 1, layer_norm_eps 1e-5: the sentence-transformers checkpoints'
+    values); with head = "sequence" | "token" | "qa" the HF head model in BertHeadWrapper.  A replica recognises it
+    by its names (encoder.relative_attention_bias.weight, attention.attn.q) and serves it through the
+    relative-bias attention kernel; positions follow RoBERTa's rule, so the longest sequence is
+    max_position - 2, at most 512.  LayerNorms, position row 1 and the heads are re-drawn as roberta() does;
+    the bucket table is re-drawn from N(0, 1.5^2): real checkpoints hold values of several units, and HF's
+    0.02 init would hide a wrong bucket.  HF's encoder looks up 32 buckets whatever the config says, so
+    `buckets` other than 32 builds a table the module itself cannot run (packer tests only)."""
+    import logging
+
+    from transformers import (MPNetConfig, MPNetForQuestionAnswering, MPNetForSequenceClassification,
+                              MPNetForTokenClassification, MPNetModel)
+    from transformers.utils import logging as hf_logging
+
+    hf_logging.set_verbosity_error()
+    logging.getLogger("transformers").setLevel(logging.ERROR)
+    torch.manual_seed(seed)
+    cfg = MPNetConfig(num_hidden_layers=layers, hidden_size=hidden, num_attention_heads=heads,
+                      intermediate_size=intermediate, vocab_size=vocab, max_position_embeddings=max_position,
+                      relative_attention_num_buckets=buckets, pad_token_id=1, bos_token_id=0, eos_token_id=2,
+                      layer_norm_eps=1e-5, initializer_range=init_std, torchscript=True)
+    if head is None:
+        model = BertWrapper(MPNetModel(cfg))
+    else:
+        cfg.num_labels = 2 if head == "qa" else num_labels
+        hf = {"sequence": MPNetForSequenceClassification, "token": MPNetForTokenClassification,
+              "qa": MPNetForQuestionAnswering}
+        if head not in hf:
+            raise ValueError(f"unknown BERT head {head!r}; known: {sorted(hf)}")
+        model = BertHeadWrapper(hf[head](cfg), head, outputs)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, nn.LayerNorm):
+                m.weight.copy_(1.0 + 0.1 * torch.randn_like(m.weight))
+                m.bias.copy_(0.05 * torch.randn_like(m.bias))
+        pos = model.bert.embeddings.position_embeddings.weight
+        pos[1].copy_(init_std * torch.randn_like(pos[1]))
+        table = model.bert.encoder.relative_attention_bias.weight
+        table.copy_(1.5 * torch.randn_like(table))
+        if head is not None:
+            inner = model.model
+            dense = [inner.qa_outputs] if head == "qa" else \
+                [inner.classifier.dense, inner.classifier.out_proj] if head == "sequence" else [inner.classifier]
+            for d in dense:
+                d.weight.copy_(torch.randn_like(d.weight) / hidden ** 0.5)
+                d.bias.copy_(0.1 * torch.randn_like(d.bias))
+    return model.eval()
+
+
+def mpnet_base(seed: int = 0, **kw) -> nn.Module:
+    """all-mpnet-base-v2's graph: 12 layers, hidden 768 over 12 heads, FFN 3072, 32 buckets."""
+    return mpnet(seed=seed, **kw)
+
+
 class AddConstant(nn.Module):
     """The reference's toy TorchScript models (tests/e2e/fixtures/simple_model.ts: x + 1)."""
 
@@ -815,6 +875,7 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
         "roberta_base": roberta_base,
         "xlm_roberta_base": xlm_roberta_base,
         "xlm_roberta_large": xlm_roberta_large,
+        "mpnet_base": mpnet_base,
     }
     if name not in table:
         raise KeyError(f"unknown model {name!r}; known: {sorted(table)}")
