@@ -241,9 +241,12 @@ enum spi_family {
   SPI_FAMILY_VIT = 3,    /* torchvision vit_*_16 naming */
   SPI_FAMILY_AFFINE = 4, /* y = x * scale + shift (toy models of the reference tests) */
   SPI_FAMILY_CONVNEXT = 5, /* torchvision convnext_* naming; SPI_PREC_F16 and SPI_PREC_F32 */
-  SPI_FAMILY_SWIN = 6      /* torchvision swin_t / _s / _b (v1) and swin_v2_t / _s / _b naming, told apart by the
+  SPI_FAMILY_SWIN = 6,     /* torchvision swin_t / _s / _b (v1) and swin_v2_t / _s / _b naming, told apart by the
                             * names (relative_position_bias_table, or logit_scale + cpb_mlp on every attention);
                             * windows of at most 8 x 8, maps that are multiples of it; SPI_PREC_F16 and SPI_PREC_F32 */
+  SPI_FAMILY_EFFICIENTNET = 7 /* torchvision efficientnet_b0 .. _b7 naming (features.S.B.block.*, classifier.1);
+                               * 3x3 / 5x5 depthwise convs, channels multiples of 8 up to 4608, squeeze at most 256,
+                               * image a multiple of 32; SPI_PREC_F16 and SPI_PREC_F32 */
 };
 
 /* SPI_PREC_F16X3: split fp16 -- fp32 activations, each MFMA operand split into

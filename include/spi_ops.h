@@ -41,7 +41,9 @@ int spi_op_pack_weight(int32_t precision, const float* w_host, int32_t N, int32_
  * and tickets).  The scratch must be zero-filled once before first use. */
 size_t spi_op_workspace_bytes(void);
 
-/* C[M,N] = act(A[M,K] . W^T + bias + residual); act: 0 none, 1 relu, 2 gelu.
+/* C[M,N] = act(A[M,K] . W^T + bias + residual); act: 0 none, 1 relu, 2 gelu, 3 silu (v / (1 + exp(-v)) in
+ * fp32; this entry point and spi_op_conv2d only -- the hilo, gemm_ln, conv_pair, avgpool_fc and grouped entry
+ * points keep 0 .. 2, resp. 0 .. 1).
  * A: fp16 (precision fp16), fp32 (fp32 / fp16x3) or split (3), row stride lda
  * (elements).  residual: same element type as A unless res_f32; C: fp32 when
  * out_f32 (not with split). */
@@ -465,6 +467,32 @@ int spi_op_ln_rows_add(int32_t precision, const void* x, const void* res, int32_
 /* spi_op_s2d_ln's gather alone: y [B (H/2) (W/2)][4 C], pixel (2 i + dy, 2 j + dx) of x NHWC at columns
  * (dx 2 + dy) C, copied as it is.  The same ranges. */
 int spi_op_s2d_rows(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, void* y, void* stream);
+
+/* ---- MBConv kernels (mbconv.hip): precision 0 (fp32) or 1 (fp16) is the type of x, w_packed and y.  C a multiple
+ * of 8 from 8 to 4608; k 3 or 5; stride 1 or 2; pad (k - 1) / 2 on all four sides, so OH = (H + 2 pad - k) / stride
+ * + 1 and OW alike; H, W >= 1; 1 <= B <= 65535; every device pointer 16-byte aligned.  A refused call returns
+ * non-zero, launches nothing and leaves its reason in spi_last_error(). ---- */
+/* torch's depthwise weight [C][1][k][k] (host fp32, BatchNorm folded in by the caller) -> [k k][C] of the
+ * precision's type (host), tap-major. */
+int spi_op_dwconv_pack_weight(int32_t precision, const float* w_host, int32_t C, int32_t k, void* dst_host);
+/* Rows per image of spi_op_dwconv_act's pool sums for an H x W map: its pixel tiles (16 x 8 outputs at stride 1,
+ * 8 x 8 at stride 2); 0 outside the supported set. */
+int32_t spi_op_dwconv_tiles(int32_t H, int32_t W, int32_t k, int32_t stride);
+/* y [B][OH][OW][C] = act(dwconv k x k(x NHWC [B][H][W][C]) + bias), bias fp32 [C], act 0 (none) or 3 (SiLU, in
+ * fp32), fp32 accumulation, one rounding at the store.  pool_part (nullable): fp32 [B][tiles][C], row t the sum of
+ * the fp32 activations over the outputs of pixel tile t -- the squeeze-and-excitation mean is their sum over t
+ * divided by OH OW.  tiles_out (host, nullable) receives spi_op_dwconv_tiles(H, W, k, stride).  Two launches
+ * give equal bits: no atomics. */
+int spi_op_dwconv_act(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                      int32_t stride, const void* w_packed, const float* bias, int32_t act, void* y, float* pool_part,
+                      int32_t* tiles_out, void* stream);
+/* gate fp32 [B][C] = sigmoid(W2 SiLU(W1 mean + b1) + b2) with mean[b][c] = (sum over t < tiles of part[b][t][c]) /
+ * hw, tiles added in index order; everything fp32, W1 [sq][C], W2 [C][sq] row-major, 1 <= sq <= 256. */
+int spi_op_se_gate(const float* part, int32_t tiles, int32_t hw, const float* W1, const float* b1, const float* W2,
+                   const float* b2, float* gate, int32_t B, int32_t C, int32_t sq, void* stream);
+/* y [B][HW][C] = x [B][HW][C] * gate [B][C]: the product in fp32, rounded once to the precision's type; y may be x. */
+int spi_op_scale_channels(int32_t precision, const void* x, const float* gate, void* y, int32_t B, int32_t HW, int32_t C,
+                          void* stream);
 
 #ifdef __cplusplus
 }

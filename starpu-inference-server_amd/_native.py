@@ -50,6 +50,7 @@ SPI_ERR_CPU_FORWARD = 7
 
 # enum spi_family / spi_precision
 FAMILY_AUTO, FAMILY_RESNET, FAMILY_BERT, FAMILY_VIT, FAMILY_AFFINE, FAMILY_CONVNEXT, FAMILY_SWIN = 0, 1, 2, 3, 4, 5, 6
+FAMILY_EFFICIENTNET = 7
 PREC_F32, PREC_F16, PREC_F16X3, PREC_F16M = 0, 1, 2, 3
 
 
@@ -273,6 +274,15 @@ _PROTOS = {
     "spi_op_ln_rows_add": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_float, C.c_void_p, C.c_void_p]),
     "spi_op_s2d_rows": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "spi_op_dwconv_pack_weight": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "spi_op_dwconv_tiles": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "spi_op_dwconv_act": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    "spi_op_se_gate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "spi_op_scale_channels": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_void_p]),
     "spi_op_avgpool_fc": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "spi_op_stem_pool_bytes": (C.c_size_t, []),

@@ -128,7 +128,7 @@ PRECISIONS = {"fp16": N.PREC_F16, "f16": N.PREC_F16, "fp32": N.PREC_F32, "f32": 
               "fp16x3": N.PREC_F16X3, "f16x3": N.PREC_F16X3, "fp16m": N.PREC_F16M, "f16m": N.PREC_F16M}
 _FAMILIES = {None: N.FAMILY_AUTO, "auto": N.FAMILY_AUTO, "resnet": N.FAMILY_RESNET, "bert": N.FAMILY_BERT,
              "vit": N.FAMILY_VIT, "affine": N.FAMILY_AFFINE, "convnext": N.FAMILY_CONVNEXT,
-             "swin": N.FAMILY_SWIN}
+             "swin": N.FAMILY_SWIN, "efficientnet": N.FAMILY_EFFICIENTNET}
 BERT_IO = {"pooler": N.BERT_OUT_POOLER, "mean": N.BERT_OUT_MEAN, "no_hidden": N.BERT_NO_HIDDEN,
            "token_types": N.BERT_TOKEN_TYPES, "seq_head": N.BERT_HEAD_SEQUENCE, "token_head": N.BERT_HEAD_TOKEN,
            "qa_head": N.BERT_HEAD_QA, "roberta_positions": N.BERT_POS_FROM_IDS}

@@ -342,7 +342,7 @@ bool conv_wres_eligible(const GemmDesc& d, Prec prec, const GemmPtrs& p) {
   return on && prec == Prec::F16 && d.conv && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad == 1 &&
          d.Cin == 64 && d.N == 64 && d.K == 576 && d.Kpad == 576 && d.krep == 1 && d.OH == d.H && d.OW == d.W &&
          !d.a_split && !d.out_split && !d.out_f32 && !d.res_f32 && !d.pool_rows && d.ldc == 64 &&
-         (!p.res || d.ldr == 64) && d.act != Act::Gelu && wres_rows(d.H, d.W) >= 1 && aligned(p.A, 16) &&
+         (!p.res || d.ldr == 64) && d.act != Act::Gelu && d.act != Act::Silu && wres_rows(d.H, d.W) >= 1 && aligned(p.A, 16) &&
          aligned(p.W, 16) && aligned(p.C, 16) && (!p.res || aligned(p.res, 16)) && (!p.bias || aligned(p.bias, 16)) &&
          p.zeros && d.w_image;
 }

@@ -18,6 +18,19 @@ void dwconv7_pack_into(T* dst, const float* w, int C) {
     for (int c = 0; c < C; ++c) dst[(size_t)tap * C + c] = static_cast<T>(w[(size_t)c * kDwconvTaps + tap]);
 }
 
+// The bank rule of the depthwise kernels' halo reads (dwconv_ln.hip states it; mbconv.hip holds its own strides
+// against it): lanes chunk-fastest, lane l reading chunk l % nch of the run l / nch, runs `run` pixels of `stride`
+// 16-byte chunks apart -- the 16 lanes one LDS pass serves must touch 16 distinct 16-byte bank groups.
+constexpr bool dw_reads_disjoint(int nch, int stride, int run) {
+  bool seen[16] = {};
+  for (int l = 0; l < 16; ++l) {
+    const int slot = ((l / nch) * run * stride + l % nch) % 16;
+    if (seen[slot]) return false;
+    seen[slot] = true;
+  }
+  return true;
+}
+
 // A 2x2 / stride 2 conv weight [N][C][2][2] -> the dense [N][4 C] matrix over ln_space_to_depth's rows:
 // column (kh * 2 + kw) * C + c, so the C channels of each of the four source pixels lie contiguous.
 inline void s2d_permute_weight(const float* w, int N, int C, float* dst) {

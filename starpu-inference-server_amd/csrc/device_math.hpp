@@ -34,6 +34,10 @@ __device__ __forceinline__ float fast_erf(float x) {
 
 __device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.f + fast_erf(v * 0.70710678118654752f)); }
 
+// SiLU (torch.nn.SiLU: v sigmoid(v)) as v / (1 + exp(-v)) in fp32: exp(-v) overflows to +inf for v < -88 and the
+// quotient is then -0, the limit.  The EfficientNet epilogues (Act::Silu) and mbconv.hip share it.
+__device__ __forceinline__ float silu(float v) { return v / (1.f + __expf(-v)); }
+
 // Two GELUs for the fp16-operand 256x256 GEMM (gemm256.hip), on the packed fp32 VALU.
 // Its epilogue has 128 GELUs per lane and no MFMA beside them, so the VALU count is the
 // cost (the 13 / 8 form took 11 us of a 41 us ViT-L FFN1 launch).  A lower-order

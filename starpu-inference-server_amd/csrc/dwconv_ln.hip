@@ -49,16 +49,7 @@ struct DwChunk<float> {
 // pixel of the window: no padding chunk is needed, and the staging stores (chunk-fastest too) are the same
 // lines.  A slab of 8 or 4 chunks would need a stride of 10 or 5 chunks by the same rule (dw_reads_disjoint).
 constexpr int kDwSlabChunks = 16;
-constexpr int kDwPixelStride = 16;
-constexpr bool dw_reads_disjoint(int nch, int stride, int run) {
-  bool seen[16] = {};
-  for (int l = 0; l < 16; ++l) {
-    const int slot = ((l / nch) * run * stride + l % nch) % 16;
-    if (seen[slot]) return false;
-    seen[slot] = true;
-  }
-  return true;
-}
+constexpr int kDwPixelStride = 16;  // (dw_reads_disjoint: convnext_pack.hpp)
 static_assert(dw_reads_disjoint(kDwSlabChunks, kDwPixelStride, 4) && dw_reads_disjoint(kDwSlabChunks, kDwPixelStride, 2) &&
                   dw_reads_disjoint(kDwSlabChunks, kDwPixelStride, 1),
               "a 16-lane group of the window reads must cover 16 distinct 16-byte bank groups");

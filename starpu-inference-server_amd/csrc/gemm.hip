@@ -75,6 +75,7 @@ __device__ __forceinline__ size_t split_idx(int m, int n, int ld) {
 __device__ __forceinline__ float apply_act(float v, Act act) {
   if (act == Act::Relu) return v > 0.f ? v : 0.f;
   if (act == Act::Gelu) return gelu(v);
+  if (act == Act::Silu) return silu(v);
   return v;
 }
 
@@ -658,6 +659,8 @@ __device__ __forceinline__ void gemm_body(const KArgs& a, const int kslice_in, c
           }
       } else if (d.act == Act::Gelu) {
         apply(std::integral_constant<Act, Act::Gelu>{});
+      } else if (d.act == Act::Silu) {
+        apply(std::integral_constant<Act, Act::Silu>{});
       } else {
         apply(std::integral_constant<Act, Act::None>{});
       }

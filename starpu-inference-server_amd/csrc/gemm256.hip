@@ -569,6 +569,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const G256Args g) {
   auto finish = [&](float y) {
     if (act == Act::Relu) return y > 0.f ? y : 0.f;
     if (act == Act::Gelu) return gelu(y);
+    if (act == Act::Silu) return silu(y);
     return y;
   };
   if (!g.vec_ok) {
@@ -769,6 +770,10 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const G256Args g) {
               y[e + 1] = g2.y;
             }
           }
+          if constexpr (ACT == (int)Act::Silu) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) y[e] = silu(y[e]);
+          }
           // Rows past M exist only in tiles that cross M (GUARD, the last tile row): their stores
           // are skipped.  (Storing them as duplicates of row M - 1, as full tiles' branch-free walk
           // could, races with the real row M - 1 when C is the residual buffer itself -- the
@@ -832,6 +837,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const G256Args g) {
       by_guard(std::integral_constant<int, (int)Act::Gelu>{}, f32_c, lnc_c, lno_c);
     else if (act == Act::Relu)
       by_guard(std::integral_constant<int, (int)Act::Relu>{}, f32_c, lnc_c, lno_c);
+    else if (act == Act::Silu)
+      by_guard(std::integral_constant<int, (int)Act::Silu>{}, f32_c, lnc_c, lno_c);
     else
       by_guard(std::integral_constant<int, (int)Act::None>{}, f32_c, lnc_c, lno_c);
   };

@@ -7,7 +7,7 @@
 
 namespace spi {
 
-enum class Act : int { None = 0, Relu = 1, Gelu = 2 };
+enum class Act : int { None = 0, Relu = 1, Gelu = 2, Silu = 3 };
 
 // Contraction precision.  F16X3 = split fp16 (fp32 activations, hi/lo fp16
 // operands, three MFMAs per fragment): fp32-grade results at the fp16 rate.

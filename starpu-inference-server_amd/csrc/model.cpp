@@ -4,6 +4,7 @@
 // forward that LibTorch runs inside the codelet (src/core/starpu_setup.cpp:610).
 #include "convnext_pack.hpp"
 #include "gconv.hpp"
+#include "mbconv_pack.hpp"
 #include "model.hpp"
 #include "swin_pack.hpp"
 
@@ -690,6 +691,59 @@ void Model::body_swin(Workspace& w, int B, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------
+// EfficientNet plan: the launching visitor of walk_efficientnet (model_plan.hpp)
+// ---------------------------------------------------------------------------
+void Model::body_efficientnet(Workspace& w, int B, hipStream_t s) {
+  struct Launch {
+    Model& M;
+    Workspace& w;
+    hipStream_t s;
+    const PackedModel& m = M.m_;
+    void* const* buf = w.bufs.data();
+    const size_t es = m.f16 ? 2 : 4;
+    void gemm(const LinearW& L, int rows, Act act, const void* A, void* C, const void* res) {
+      M.run_gemm(L, cn_gemm_desc(L, rows, act, res != nullptr, false), A, C, res, LnPtrs{}, w, s);
+    }
+    void stem(int B, int out) {
+      M.run_conv(m.stem, conv_layer_desc(m, m.stem, B, m.image, m.image, Act::Silu), buf[kEnIngest], buf[out], nullptr, w, s);
+    }
+    void block(int B, int H, const MbBlock& k, int in, int out) {
+      const int OH = dwconv_out(H, k.k, k.stride), tiles = dwconv_tiles(H, H, k.k, k.stride), C = k.mid;
+      const int rows = B * OH * OH;
+      const void* x = buf[in];
+      if (k.has_expand) {
+        gemm(k.expand, B * H * H, Act::Silu, buf[in], buf[kEnExp], nullptr);
+        x = buf[kEnExp];
+      }
+      float* part = static_cast<float*>(buf[kEnPart]);
+      float* gate = static_cast<float*>(buf[kEnGate]);
+      M.prof_op(s, [&] { return "dwconv" + std::to_string(k.k) + "s" + std::to_string(k.stride) + "_c" + std::to_string(C) +
+                                "_h" + std::to_string(H); },
+                2.0 * k.k * k.k * (double)rows * C,
+                ((double)B * H * H + rows) * C * es + (double)k.k * k.k * C * es + (double)B * tiles * C * 4, [&] {
+                  dwconv_act(x, M.ptr<void>(k.dw_w), M.ptr<float>(k.dw_b), buf[kEnDw], part, B, H, H, C, k.k, k.stride,
+                             (int)Act::Silu, m.f16, s);
+                });
+      M.prof_op(s, [&] { return "se_gate_c" + std::to_string(C); }, 4.0 * B * (double)k.sq * C,
+                ((double)B * tiles * C + 2.0 * k.sq * C + B * C) * 4, [&] {
+                  se_gate(part, tiles, OH * OH, M.ptr<float>(k.se_w1), M.ptr<float>(k.se_b1), M.ptr<float>(k.se_w2),
+                          M.ptr<float>(k.se_b2), gate, B, C, k.sq, s);
+                });
+      M.prof_op(s, [&] { return "se_scale_c" + std::to_string(C); }, (double)rows * C, 2.0 * rows * C * es + (double)B * C * 4,
+                [&] { scale_channels(buf[kEnDw], gate, buf[kEnDw], B, OH * OH, C, m.f16, s); });
+      gemm(k.project, rows, Act::None, buf[kEnDw], buf[out], k.residual ? buf[in] : nullptr);
+    }
+    void head(int B, int H, int in) { gemm(m.mb_head, B * H * H, Act::Silu, buf[in], buf[kEnExp], nullptr); }
+    void tail(int B, int hw, bool fused) {
+      if (fused) return;  // avgpool + fc run as one GEMM in the epilogue
+      M.prof_op(s, "avgpool", 0, (double)B * hw * m.feat * es,
+                [&] { avgpool_nhwc(buf[kEnExp], buf[kEnPooled], B, hw, m.feat, m.f16, s); });
+    }
+  };
+  walk_efficientnet(m_, B, Launch{*this, w, s});
+}
+
+// ---------------------------------------------------------------------------
 // Forward: prologue -> body (graph-capturable) -> epilogue, each dispatched by family (model.hpp)
 // ---------------------------------------------------------------------------
 void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStream_t s, ImageSrc isrc) {
@@ -704,6 +758,7 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
     float* y = static_cast<float*>(w.bufs[m_.family == SPI_FAMILY_RESNET     ? (int)kRnResized
                                           : m_.family == SPI_FAMILY_CONVNEXT ? (int)kCnResized
                                           : m_.family == SPI_FAMILY_SWIN     ? (int)kSwResized
+                                          : m_.family == SPI_FAMILY_EFFICIENTNET ? (int)kEnResized
                                                                              : (int)kVtResized]);
     prof_op(s, "resize_crop_u8", 0, (double)B * 3 * ((double)isrc.H * isrc.W + (double)image * image * 4), [&] {
       resize_crop_u8(in[0], src == kSrcU8Nhwc, B, isrc.H, isrc.W, opt_.resize_short, image, input_xf_, y, s);
@@ -744,6 +799,10 @@ void Model::prologue(Workspace& w, int B, int S, const void* const* in, hipStrea
       return prof_op(s, "patchify", 0, (double)B * 3 * image * image * (4 + (f16 ? 2 : 4)), [&] {
         patchify(image_in, w.bufs[kSwPatches], B, 3, image, image, 4, f16, s, src, input_xf_);
       });
+    case SPI_FAMILY_EFFICIENTNET:  // the 3x3 / stride 2 stem reads the padded NHWC image, as ResNet's unfused stem
+      return prof_op(s, "ingest_nchw", 0, (double)B * 3 * image * image * 4 * 2, [&] {
+        ingest_nchw(image_in, w.bufs[kEnIngest], B, 3, image, image, m_.stem.cin_pad, f16, s, src, input_xf_);
+      });
   }
 }
 
@@ -754,6 +813,7 @@ void Model::body(Workspace& w, int B, int S, hipStream_t s) {
     case SPI_FAMILY_VIT: return body_vit(w, B, s);
     case SPI_FAMILY_CONVNEXT: return body_convnext(w, B, s);
     case SPI_FAMILY_SWIN: return body_swin(w, B, s);
+    case SPI_FAMILY_EFFICIENTNET: return body_efficientnet(w, B, s);
   }
 }
 
@@ -787,6 +847,15 @@ void Model::epilogue(Workspace& w, int B, int S, void* const* out, hipStream_t s
         run_pooled_fc(w.bufs[kSwLn], B, hw, logits, w, s);
       else
         run_gemm(m_.fc, linear_layer_desc(m_.fc, B), w.bufs[kSwPooled], logits, nullptr, LnPtrs{}, w, s);
+      return run_image_outputs(logits, B, out, s);
+    }
+    case SPI_FAMILY_EFFICIENTNET: {  // the mean of the head conv's map, then classifier.1
+      float* logits = logits_dst(w.bufs[kEnLogits], out);
+      const int hw = efficientnet_last_side(m_) * efficientnet_last_side(m_);
+      if (pooled_fc(m_, hw))
+        run_pooled_fc(w.bufs[kEnExp], B, hw, logits, w, s);
+      else
+        run_gemm(m_.fc, linear_layer_desc(m_.fc, B), w.bufs[kEnPooled], logits, nullptr, LnPtrs{}, w, s);
       return run_image_outputs(logits, B, out, s);
     }
   }

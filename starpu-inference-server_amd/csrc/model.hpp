@@ -115,6 +115,7 @@ class Model {
   void body_vit_folded(Workspace& w, int B, hipStream_t s);
   void body_convnext(Workspace& w, int B, hipStream_t s);
   void body_swin(Workspace& w, int B, hipStream_t s);
+  void body_efficientnet(Workspace& w, int B, hipStream_t s);
   void epilogue_bert(Workspace& w, int B, int S, void* const* out, hipStream_t s);
   // ResNet / ViT with image outputs: where the classifier writes its logits (the first output, or the
   // workspace scratch under SPI_IMAGE_NO_LOGITS), and the launch that derives the other outputs from them

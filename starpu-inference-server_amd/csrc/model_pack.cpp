@@ -17,6 +17,7 @@
 #include "swin_pack.hpp"
 #include "gconv.hpp"
 #include "ln_fold_pack.hpp"
+#include "mbconv_pack.hpp"
 #include "pack.hpp"
 
 // F16M: plain fp16 FC weights since round 5 (hi + lo kept the logits 0.06e-3 closer on 8 emulated
@@ -287,6 +288,7 @@ struct Packer {
   void build_vit(const PMap& p);
   void build_convnext(const PMap& p);
   void build_swin(const PMap& p);
+  void build_efficientnet(const PMap& p);
   SwBlock pack_swin_v2_block(const PMap& p, const std::string& pre, int C, int H, int stage);
 };
 
@@ -892,6 +894,89 @@ void Packer::build_swin(const PMap& p) {
   m.feat = m.fc.k;
 }
 
+// torchvision's EfficientNet (b0 .. b7): features.0 the stem (3x3 / stride 2 conv, BatchNorm, SiLU), features.1 .. 7
+// the stages of MBConv blocks, features.8 the 1x1 head conv, classifier.1 the Linear.  A block's `block` holds
+// [expand 1x1 (absent at expand ratio 1)], depthwise k x k, squeeze-excitation (fc1, fc2), project 1x1.  The
+// strides are not in the parameters: torchvision's stages open with strides 1, 2, 2, 2, 1, 2, 1.
+void Packer::build_efficientnet(const PMap& p) {
+  auto refuse = [](const std::string& what) { throw std::runtime_error("efficientnet: " + what); };
+  static const int kStageStride[7] = {1, 2, 2, 2, 1, 2, 1};
+  if (m.image % 32) refuse("image size " + std::to_string(m.image) + " must be a multiple of 32");
+  auto channels_ok = [&](const std::string& what, int C) {
+    if (!mbconv_channels_ok(C)) refuse(what + " has " + std::to_string(C) + " channels: a multiple of 8 from 8 to 4608 is served");
+  };
+  // a 1x1 conv + BatchNorm as a dense layer over NHWC rows
+  auto pointwise = [&](const std::string& pre, int cin) {
+    const FoldedConv f = fold_conv(p, pre + "0", pre + "1", m.eps);
+    if (f.kh != 1 || f.kw != 1 || f.cin != cin)
+      refuse(pre + "0.weight must be a 1x1 conv over " + std::to_string(cin) + " channels");
+    return pack_linear(f.w.data(), f.b.data(), f.cout, f.cin, false);
+  };
+  const FoldedConv sf = fold_conv(p, "features.0.0", "features.0.1", m.eps);
+  if (sf.cin != 3 || sf.kh != 3 || sf.kw != 3) refuse("features.0.0.weight must be a 3x3 conv over 3 channels");
+  channels_ok("the stem", sf.cout);
+  m.stem = pack_conv(sf, 2, m.f16 ? 8 : 4, m.prec);
+  const size_t es = m.f16 ? 2 : 4;
+  int C = sf.cout, stage = 0;
+  for (; has(p, "features." + std::to_string(stage + 1) + ".0.block.0.0.weight"); ++stage) {
+    if (stage >= 7) refuse("more than 7 MBConv stages: their strides are torchvision's 1, 2, 2, 2, 1, 2, 1");
+    int nb = 0;
+    for (;; ++nb) {
+      const std::string pre = "features." + std::to_string(stage + 1) + "." + std::to_string(nb) + ".block.";
+      if (!has(p, pre + "0.0.weight")) break;
+      MbBlock b;
+      b.cin = C;
+      b.stride = nb == 0 ? kStageStride[stage] : 1;
+      b.has_expand = has(p, pre + "3.0.weight");
+      const int e = b.has_expand ? 1 : 0;
+      const std::string dw = pre + std::to_string(e) + ".", se = pre + std::to_string(e + 1) + ".", pj = pre + std::to_string(e + 2) + ".";
+      if (b.has_expand) b.expand = pointwise(pre + "0.", C);
+      b.mid = b.has_expand ? b.expand.n : C;
+      channels_ok(pre + "'s expanded map", b.mid);
+      const FoldedConv df = fold_conv(p, dw + "0", dw + "1", m.eps);
+      if (df.cin != 1 && df.cin == C && df.kh == 3)
+        refuse(dw + "0.weight is a dense 3x3 conv over " + std::to_string(C) +
+               " channels where the depthwise conv belongs: EfficientNetV2's fused-MBConv blocks are not served");
+      if (df.cout != b.mid || df.cin != 1 || df.kh != df.kw || (df.kh != 3 && df.kh != 5))
+        refuse(dw + "0.weight must be a depthwise [C][1][3|5][3|5] weight with C = " + std::to_string(b.mid) +
+               (b.has_expand ? "" : " (a block without an expand conv: expand ratio 1)"));
+      b.k = df.kh;
+      b.dw_w = blob.add(nullptr, (size_t)b.k * b.k * b.mid * es);
+      if (m.f16)
+        dwconv_pack_into(reinterpret_cast<_Float16*>(blob.data.data() + b.dw_w), df.w.data(), b.mid, b.k);
+      else
+        dwconv_pack_into(reinterpret_cast<float*>(blob.data.data() + b.dw_w), df.w.data(), b.mid, b.k);
+      b.dw_b = pack_vec(df.b.data(), b.mid);
+      if (!has(p, se + "fc1.weight") || !has(p, se + "fc2.weight"))
+        refuse(se + "fc1 / fc2 are missing: an MBConv block without squeeze-and-excitation is not an EfficientNet's");
+      const spi_named_tensor *w1 = need(p, se + "fc1.weight"), *w2 = need(p, se + "fc2.weight");
+      const spi_named_tensor *b1 = need(p, se + "fc1.bias"), *b2 = need(p, se + "fc2.bias");
+      b.sq = w1->ndim == 4 ? (int)w1->shape[0] : 0;
+      if (b.sq < 1 || numel(w1) != (int64_t)b.sq * b.mid || w2->ndim != 4 || w2->shape[0] != b.mid ||
+          numel(w2) != (int64_t)b.sq * b.mid || numel(b1) != b.sq || numel(b2) != b.mid)
+        refuse(se + "fc1 / fc2 must be 1x1 convs " + std::to_string(b.mid) + " -> squeeze -> " + std::to_string(b.mid));
+      if (b.sq > kSeMaxSq) refuse(se + "fc1 squeezes to " + std::to_string(b.sq) + " channels: at most 256 are served");
+      b.se_w1 = pack_vec(fdata(w1), b.sq * b.mid), b.se_b1 = pack_vec(fdata(b1), b.sq);
+      b.se_w2 = pack_vec(fdata(w2), b.sq * b.mid), b.se_b2 = pack_vec(fdata(b2), b.mid);
+      b.project = pointwise(pj, b.mid);
+      b.cout = b.project.n;
+      channels_ok(pj + "0", b.cout);
+      b.residual = b.stride == 1 && b.cin == b.cout;
+      m.mb_blocks.push_back(b);
+      C = b.cout;
+    }
+    m.stage_blocks.push_back(nb);
+  }
+  if (m.mb_blocks.empty()) refuse("no blocks (features.1.0.block.0.0.weight)");
+  const std::string head = "features." + std::to_string(stage + 1) + ".";
+  m.mb_head = pointwise(head, C);
+  m.fc = pack_linear_named(p, "classifier.1", false);
+  if (m.fc.k != m.mb_head.n)
+    refuse("classifier.1 reads " + std::to_string(m.fc.k) + " of " + std::to_string(m.mb_head.n) + " features");
+  m.classes = m.fc.n;
+  m.feat = m.fc.k;
+}
+
 }  // namespace
 
 PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* params, int n) {
@@ -929,7 +1014,10 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     else if (ends_with(p, "features.0.0.weight") && (ends_with(p, "features.1.0.attn.relative_position_bias_table") ||
                                                      ends_with(p, "features.1.0.attn.logit_scale")))
       m.family = SPI_FAMILY_SWIN;
-    else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT/ConvNeXt/Swin parameter names");
+    else if (ends_with(p, "features.0.0.weight") && ends_with(p, "features.1.0.block.0.0.weight") &&
+             ends_with(p, "classifier.1.weight"))
+      m.family = SPI_FAMILY_EFFICIENTNET;
+    else throw std::runtime_error("unrecognised model: no ResNet/BERT/ViT/ConvNeXt/Swin/EfficientNet parameter names");
   }
   if (const int io = cfg.bert_io) {  // spi_codelet.h: enum spi_bert_io
     constexpr int heads = SPI_BERT_HEAD_SEQUENCE | SPI_BERT_HEAD_TOKEN | SPI_BERT_HEAD_QA;
@@ -988,6 +1076,15 @@ PackedModel pack_model(const spi_model_config& cfg, const spi_named_tensor* para
     os << (m.sw_v2 ? "swin_v2[" : "swin[");
     for (size_t i = 0; i < m.stage_blocks.size(); ++i) os << (i ? "," : "") << m.stage_blocks[i];
     os << "] C" << m.sw_dims.front() << " ws" << m.sw_window << " img" << m.image << " classes" << m.classes;
+  } else if (m.family == SPI_FAMILY_EFFICIENTNET) {
+    if (cfg.precision != SPI_PREC_F16 && cfg.precision != SPI_PREC_F32)
+      throw std::runtime_error(
+          "efficientnet: SPI_PREC_F16X3 and SPI_PREC_F16M are not served for this family; use SPI_PREC_F16 or SPI_PREC_F32");
+    m.eps = cfg.eps > 0 ? cfg.eps : 1e-5f;
+    pk.build_efficientnet(strip_prefix(p, "features.0.0.weight"));
+    os << "efficientnet[";
+    for (size_t i = 0; i < m.stage_blocks.size(); ++i) os << (i ? "," : "") << m.stage_blocks[i];
+    os << "] C" << m.stem.cout << " img" << m.image << " classes" << m.classes;
   } else {
     throw std::runtime_error("unsupported model family");
   }

@@ -80,6 +80,14 @@ struct SwMerge {  // Swin patch merging: gather 2x2 + LayerNorm over 4 C (s2d_ln
   LinearW red;  // torch's [2 C][4 C] as it is
 };
 
+struct MbBlock {  // EfficientNet MBConv: [1x1 expand + SiLU], depthwise k x k + SiLU, squeeze-excite, 1x1 project [+ x]
+  int cin = 0, mid = 0, cout = 0, k = 3, stride = 1, sq = 0;
+  bool has_expand = false, residual = false;  // expand ratio 1 has no expand conv; stride 1 and cin == cout add x
+  LinearW expand, project;     // the 1x1 convs as dense layers over NHWC rows, BatchNorm folded in
+  size_t dw_w = 0, dw_b = 0;   // [k k][mid] in the compute type (BatchNorm folded in fp32, rounded once), fp32 [mid]
+  size_t se_w1 = 0, se_b1 = 0, se_w2 = 0, se_b2 = 0;  // fp32 [sq][mid], [sq], [mid][sq], [mid]
+};
+
 struct PackedModel {
   int family = 0;
   Prec prec = Prec::F16;
@@ -154,6 +162,11 @@ struct PackedModel {
   std::vector<SwMerge> sw_merge;
   int sw_window = 0;
   bool sw_v2 = false;  // torchvision's swin_v2_*: cosine attention, cpb_mlp bias, post-norm blocks, PatchMergingV2
+
+  // EfficientNet: the 3x3 / stride 2 stem is `stem` (a ConvW over the ingested image, SiLU); the MBConv blocks in
+  // order (stage_blocks per stage); features.8 (mb_head, 1x1 + SiLU) and classifier.1 (fc; classes, feat)
+  std::vector<MbBlock> mb_blocks;
+  LinearW mb_head;
 
   std::string desc;
   uint64_t digest = 0;  // FNV-1a 64 of the blob

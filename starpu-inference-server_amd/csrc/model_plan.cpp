@@ -6,6 +6,7 @@
 #include <utility>
 
 #include "convnext_pack.hpp"
+#include "mbconv_pack.hpp"
 #include "resample.hpp"
 #include "swin_pack.hpp"
 
@@ -14,7 +15,7 @@ namespace spi {
 namespace {
 bool image_family(const PackedModel& m) {
   return m.family == SPI_FAMILY_RESNET || m.family == SPI_FAMILY_VIT || m.family == SPI_FAMILY_CONVNEXT ||
-         m.family == SPI_FAMILY_SWIN;
+         m.family == SPI_FAMILY_SWIN || m.family == SPI_FAMILY_EFFICIENTNET;
 }
 }  // namespace
 
@@ -393,9 +394,62 @@ SwGemmVisitor<F> walk_swin_gemms(const PackedModel& m, int B, F&& f) {
   walk_swin(m, B, v);
   return v;
 }
+
+// The conv and the GEMMs of the EfficientNet graph, each as the desc Model::body_efficientnet (and the epilogue)
+// builds for it: on_gemm(step name, desc, prec).  Also the largest map in an activation slot, the largest expanded
+// map, depthwise output, pool sums and gate, in elements, and the FLOPs outside the GEMMs: 2 k k per depthwise
+// output; 2 sq C for each of the two squeeze-excitation layers of a block and image, 1x1 convs on a 1x1 map.
+template <class F>
+struct EnGemmVisitor {
+  const PackedModel& m;
+  F on_gemm;
+  size_t amax = 0, emax = 0, dmax = 0, pmax = 0, gmax = 0;
+  double other_flops = 0;
+  void stem(int B, int) {
+    const GemmDesc d = conv_layer_desc(m, m.stem, B, m.image, m.image, Act::Silu);
+    amax = std::max(amax, (size_t)d.M * d.N);
+    on_gemm("stem", d, m.stem.prec);
+  }
+  void block(int B, int H, const MbBlock& k, int, int) {
+    const int OH = dwconv_out(H, k.k, k.stride);
+    const size_t rows_in = (size_t)B * H * H, rows = (size_t)B * OH * OH;
+    if (k.has_expand) {
+      emax = std::max(emax, rows_in * k.mid);
+      on_gemm("expand", cn_gemm_desc(k.expand, (int)rows_in, Act::Silu, false, false), k.expand.prec);
+    }
+    dmax = std::max(dmax, rows * k.mid);
+    pmax = std::max(pmax, (size_t)B * dwconv_tiles(H, H, k.k, k.stride) * k.mid);
+    gmax = std::max(gmax, (size_t)B * k.mid);
+    other_flops += 2.0 * k.k * k.k * (double)rows * k.mid + 4.0 * B * (double)k.sq * k.mid;
+    amax = std::max(amax, rows * k.cout);
+    on_gemm("project", cn_gemm_desc(k.project, (int)rows, Act::None, k.residual, false), k.project.prec);
+  }
+  void head(int B, int H, int) {
+    emax = std::max(emax, (size_t)B * H * H * m.mb_head.n);
+    on_gemm("head", cn_gemm_desc(m.mb_head, B * H * H, Act::Silu, false, false), m.mb_head.prec);
+  }
+  void tail(int B, int hw, bool fused) {
+    if (fused) on_gemm("avgpool_fc", pooled_fc_desc(m, B, hw), m.fc.prec);
+    else on_gemm("fc", linear_layer_desc(m.fc, B), m.fc.prec);
+  }
+};
+
+template <class F>
+EnGemmVisitor<F> walk_efficientnet_gemms(const PackedModel& m, int B, F&& f) {
+  EnGemmVisitor<F> v{m, std::forward<F>(f)};
+  walk_efficientnet(m, B, v);
+  return v;
+}
 }  // namespace
 
 double model_flops(const PackedModel& m, int64_t B) {
+  if (m.family == SPI_FAMILY_EFFICIENTNET) {
+    double f = 0;
+    const auto v = walk_efficientnet_gemms(m, (int)B, [&](const char*, const GemmDesc& d, Prec) {
+      f += 2.0 * (d.pool_rows ? d.M / d.pool_rows : d.M) * d.N * (double)(d.conv ? d.KH * d.KW * m.stem.cin : d.K);
+    });
+    return f + v.other_flops;
+  }
   if (m.family == SPI_FAMILY_SWIN) {
     double f = 0;
     const auto v = walk_swin_gemms(m, (int)B, [&](const char*, const LinearW&, const GemmDesc& d) {
@@ -552,6 +606,20 @@ WorkspacePlan workspace_plan(const PackedModel& m, const ReplicaOptions& o) {
     sz[kSwLogits] = logits;
     sz[kSwResized] = resized;
   }
+  if (m.family == SPI_FAMILY_EFFICIENTNET) {
+    const auto v = walk_efficientnet_gemms(m, (int)B, [&](const char*, const GemmDesc& d, Prec prec) { slabs(d, prec); });
+    const size_t HL = efficientnet_last_side(m);
+    sz.assign(kEnBufs, 0);
+    sz[kEnIngest] = B * m.image * m.image * m.stem.cin_pad * es;
+    sz[kEnAct0] = sz[kEnAct1] = v.amax * es;
+    sz[kEnExp] = v.emax * es;
+    sz[kEnDw] = v.dmax * es;
+    sz[kEnPart] = v.pmax * 4;
+    sz[kEnGate] = v.gmax * 4;
+    sz[kEnPooled] = pooled_fc(m, (int)(HL * HL)) ? 0 : B * m.feat * es;
+    sz[kEnLogits] = logits;
+    sz[kEnResized] = resized;
+  }
   if (m.family == SPI_FAMILY_BERT || m.family == SPI_FAMILY_VIT)
     walk_transformer_gemms(m, (int)B, m.seq, [&](const char*, const LinearW& L, const GemmDesc& d) { slabs(d, L.prec); });
   // Split-K slabs: choose_plan only splits grids of < 128 tiles into <= 512 +
@@ -577,6 +645,8 @@ int plan_check(const PackedModel& m, const ReplicaOptions& o, int B, int S) {
     walk_convnext_gemms(m, B, [&](const char* name, const LinearW& L, const GemmDesc& d) { hold(name, d, L.prec, nullptr); });
   } else if (m.family == SPI_FAMILY_SWIN) {
     walk_swin_gemms(m, B, [&](const char* name, const LinearW& L, const GemmDesc& d) { hold(name, d, L.prec, nullptr); });
+  } else if (m.family == SPI_FAMILY_EFFICIENTNET) {
+    walk_efficientnet_gemms(m, B, [&](const char* name, const GemmDesc& d, Prec prec) { hold(name, d, prec, nullptr); });
   } else if (m.family == SPI_FAMILY_BERT || m.family == SPI_FAMILY_VIT) {
     if (m.family == SPI_FAMILY_BERT && (S < 1 || S > m.seq)) throw std::runtime_error("plan_check: sequence outside 1 .. seq");
     walk_transformer_gemms(m, B, S, [&](const char* name, const LinearW& L, const GemmDesc& d) { hold(name, d, L.prec, nullptr); });

@@ -13,6 +13,7 @@
 
 #include "gemm_plan.hpp"
 #include "image_src.hpp"
+#include "mbconv_pack.hpp"
 #include "model_pack.hpp"
 #include "swin_pack.hpp"
 
@@ -52,6 +53,11 @@ enum CnBuf { kCnPatches, kCnAct0, kCnAct1, kCnLn, kCnHidden, kCnPooled, kCnLogit
 // MLP hidden rows (first the stem GEMM's fp32 output); the pooled features (maps of more than 64 pixels only);
 // logits scratch and resized image as above.
 enum SwBuf { kSwPatches, kSwX0, kSwX1, kSwLn, kSwQkv, kSwCtx, kSwHidden, kSwPooled, kSwLogits, kSwResized, kSwBufs };
+// EfficientNet: the padded NHWC image; two activation slots the blocks alternate between (NHWC maps in the compute
+// type); the expanded map (an expand conv's output, at the end the head conv's); the depthwise conv's output, scaled
+// in place by the gate; the pool sums fp32 [B][tiles][C] and the gate fp32 [B][C]; the pooled features (last maps of
+// more than 64 pixels only); logits scratch and resized image as above.
+enum EnBuf { kEnIngest, kEnAct0, kEnAct1, kEnExp, kEnDw, kEnPart, kEnGate, kEnPooled, kEnLogits, kEnResized, kEnBufs };
 
 // ---------------------------------------------------------------------------
 // I/O contract
@@ -232,6 +238,35 @@ void walk_swin(const PackedModel& m, int B, V&& v) {
       v.block(B, H, m.sw_blocks[blk], window_block_shift(i, m.sw_window, H), cur, cur ^ (kSwX0 ^ kSwX1));
   }
   v.tail(B, H, cur);
+}
+
+// ---------------------------------------------------------------------------
+// The EfficientNet graph, walked once, as walk_convnext is: Model::body_efficientnet launches from it, model_flops
+// counts it, workspace_plan and plan_check size and hold its conv and GEMMs (descs: conv_layer_desc, cn_gemm_desc).
+// H: the side of the square map a step reads; in / out: EnBuf slots.
+// ---------------------------------------------------------------------------
+inline int efficientnet_last_side(const PackedModel& m) {
+  int H = conv_out(m.image, m.stem);
+  for (const MbBlock& b : m.mb_blocks) H = dwconv_out(H, b.k, b.stride);
+  return H;
+}
+// The visitor V sees, in launch order:
+//   v.stem(B, out)               the 3x3 / stride 2 conv + SiLU on kEnIngest into slot out
+//   v.block(B, H, blk, in, out)  [expand GEMM + SiLU in -> kEnExp], dwconv + SiLU + pool sums (-> kEnDw, kEnPart), gate
+//                                (-> kEnGate), scale (kEnDw in place), project GEMM [+ in] -> out
+//   v.head(B, H, in)             the head GEMM + SiLU into kEnExp
+//   v.tail(B, hw, fused)         mean over the map into kEnPooled, unless (fused) the epilogue's pooled FC reads kEnExp
+template <class V>
+void walk_efficientnet(const PackedModel& m, int B, V&& v) {
+  int H = conv_out(m.image, m.stem), cur = kEnAct0;
+  v.stem(B, cur);
+  for (const MbBlock& b : m.mb_blocks) {
+    v.block(B, H, b, cur, cur ^ (kEnAct0 ^ kEnAct1));
+    cur ^= kEnAct0 ^ kEnAct1;
+    H = dwconv_out(H, b.k, b.stride);
+  }
+  v.head(B, H, cur);
+  v.tail(B, H * H, pooled_fc(m, H * H));
 }
 
 // ---------------------------------------------------------------------------

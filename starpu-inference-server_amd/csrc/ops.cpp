@@ -13,6 +13,7 @@
 #include "gconv.hpp"
 #include "gemm_plan.hpp"
 #include "ln_fold_pack.hpp"
+#include "mbconv_pack.hpp"
 #include "pack.hpp"
 #include "rel_bias_pack.hpp"
 #include "resample.hpp"
@@ -116,7 +117,7 @@ int spi_op_gemm(int32_t precision, const void* A, int32_t M, int32_t K, int32_t 
                 int32_t ldc, int32_t act, void* workspace, void* stream) {
   spi::Prec p;
   if (!prec_of(precision, &p) || !A || !W || !C || !workspace || M <= 0 || N <= 0 || K <= 0 || lda < K ||
-      ldc < N || act < 0 || act > 2)
+      ldc < N || act < 0 || act > 3)
     return fail("invalid gemm arguments");
   spi::GemmDesc d = spi::dense_desc(M, N, K, lda, ldc, ldr, 1);
   d.act = static_cast<spi::Act>(act);
@@ -133,13 +134,13 @@ int spi_op_gemm(int32_t precision, const void* A, int32_t M, int32_t K, int32_t 
 namespace {
 
 // The descriptor of one op-level conv, as Model::conv_call builds a layer's; hilo: hi + lo weights.
-// Returns an error message, or null.
+// max_act: 3 where the entry point takes SiLU (spi_op_conv2d), else 2.  Returns an error message, or null.
 const char* op_conv_desc(int32_t precision, spi::Prec p, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                          int32_t KH, int32_t KW, int32_t stride, int32_t pad, int32_t act, bool hilo, bool out_f32,
-                         bool res_f32, spi::GemmDesc* out) {
+                         bool res_f32, spi::GemmDesc* out, int32_t max_act = 2) {
   const int min_cin = precision == 1 ? 8 : 4;  // one 16-byte chunk: 8 fp16 or 4 fp32
   if (B <= 0 || H <= 0 || W <= 0 || Cin < min_cin || (Cin & (Cin - 1)) || Cout <= 0 || KH <= 0 || KW <= 0 ||
-      stride <= 0 || pad < 0 || act < 0 || act > 2)
+      stride <= 0 || pad < 0 || act < 0 || act > max_act)
     return "invalid conv arguments";
   spi::GemmDesc d = spi::conv_desc(B, H, W, Cin, Cout, KH, KW, stride, pad, hilo ? 2 : 1);
   if (H + 2 * pad < KH || W + 2 * pad < KW || d.OH <= 0 || d.OW <= 0) return "empty conv output";
@@ -171,7 +172,7 @@ int spi_op_conv2d(int32_t precision, const void* x, int32_t B, int32_t H, int32_
   spi::Prec p;
   if (!prec_of(precision, &p) || !x || !Wp || !y || !workspace) return fail("invalid conv arguments");
   spi::GemmDesc d;
-  if (const char* e = op_conv_desc(precision, p, B, H, W, Cin, Cout, KH, KW, stride, pad, act, false, false, false, &d))
+  if (const char* e = op_conv_desc(precision, p, B, H, W, Cin, Cout, KH, KW, stride, pad, act, false, false, false, &d, 3))
     return fail(e);
   return run_gemm(d, p, x, Wp, bias, residual, y, {}, workspace, stream, "conv too large for the op workspace");
 }
@@ -426,6 +427,54 @@ int spi_op_s2d_rows(int32_t precision, const void* x, int32_t B, int32_t H, int3
   if (!x || !y) return fail("s2d_rows: null x or y");
   return guarded([&] {
     spi::s2d_rows(x, y, B, H, W, C, precision == 1, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+// ---- MBConv kernels (mbconv.hip, mbconv_pack.hpp) ----
+
+int spi_op_dwconv_pack_weight(int32_t precision, const float* w, int32_t C, int32_t k, void* dst) {
+  if ((precision != 0 && precision != 1) || !w || !dst) return fail("invalid dwconv pack arguments");
+  if (!spi::dwconv_supported(C, k, 1)) return fail("dwconv: C a multiple of 8 from 8 to 4608, k 3 or 5");
+  if (precision == 1)
+    spi::dwconv_pack_into(static_cast<_Float16*>(dst), w, C, k);
+  else
+    spi::dwconv_pack_into(static_cast<float*>(dst), w, C, k);
+  return 0;
+}
+
+int32_t spi_op_dwconv_tiles(int32_t H, int32_t W, int32_t k, int32_t stride) {
+  if (H < 1 || W < 1 || !spi::dwconv_supported(spi::kMbMinC, k, stride)) return 0;
+  return spi::dwconv_tiles(H, W, k, stride);
+}
+
+int spi_op_dwconv_act(int32_t precision, const void* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                      int32_t stride, const void* Wp, const float* bias, int32_t act, void* y, float* pool_part,
+                      int32_t* tiles_out, void* stream) {
+  if (precision != 0 && precision != 1) return fail("dwconv_act: precision 0 (fp32) or 1 (fp16)");
+  if (!x || !Wp || !bias || !y) return fail("dwconv_act: null x, w_packed, bias or y");
+  return guarded([&] {
+    spi::dwconv_act(x, Wp, bias, y, pool_part, B, H, W, C, k, stride, act, precision == 1, static_cast<hipStream_t>(stream));
+    if (tiles_out) *tiles_out = spi::dwconv_tiles(H, W, k, stride);
+    return check_launch();
+  });
+}
+
+int spi_op_se_gate(const float* part, int32_t tiles, int32_t hw, const float* W1, const float* b1, const float* W2,
+                   const float* b2, float* gate, int32_t B, int32_t C, int32_t sq, void* stream) {
+  if (!part || !W1 || !b1 || !W2 || !b2 || !gate) return fail("se_gate: null part, W1, b1, W2, b2 or gate");
+  return guarded([&] {
+    spi::se_gate(part, tiles, hw, W1, b1, W2, b2, gate, B, C, sq, static_cast<hipStream_t>(stream));
+    return check_launch();
+  });
+}
+
+int spi_op_scale_channels(int32_t precision, const void* x, const float* gate, void* y, int32_t B, int32_t HW, int32_t C,
+                          void* stream) {
+  if (precision != 0 && precision != 1) return fail("scale_channels: precision 0 (fp32) or 1 (fp16)");
+  if (!x || !gate || !y) return fail("scale_channels: null x, gate or y");
+  return guarded([&] {
+    spi::scale_channels(x, gate, y, B, HW, C, precision == 1, static_cast<hipStream_t>(stream));
     return check_launch();
   });
 }

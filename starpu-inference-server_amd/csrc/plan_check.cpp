@@ -306,5 +306,49 @@ int main() {
       else std::printf("swin|%s| refused: %s\n", pr.first, e.what());
     }
   }
+  // EfficientNet (three stages of the b0 settings: an expand-less 3x3 block, a 3x3 / stride 2 and a 5x5 / stride 2
+  // block with a residual block behind it, at 64 x 64): the same walk, contract and refusals.
+  Tensors en;
+  auto cba = [&](const std::string& p, int64_t co, int64_t ci, int64_t k) { en.add(p + "0.weight", {co, ci, k, k}), en.norm(p + "1", co, true); };
+  cba("features.0.", 32, 3, 3);
+  const int64_t mb[4][5] = {{1, 0, 3, 32, 16}, {2, 0, 3, 16, 24}, {3, 0, 5, 24, 40}, {3, 1, 5, 40, 40}};  // stage, block, k, in, out
+  for (const auto& b : mb) {
+    const std::string p = "features." + std::to_string(b[0]) + "." + std::to_string(b[1]) + ".block.";
+    const int64_t mid = b[0] == 1 ? b[3] : 6 * b[3];
+    int e = 0;
+    if (mid != b[3]) cba(p + "0.", mid, b[3], 1), e = 1;
+    cba(p + std::to_string(e) + ".", mid, 1, b[2]);
+    const std::string se = p + std::to_string(e + 1) + ".";
+    en.add(se + "fc1.weight", {b[3] / 4, mid, 1, 1}), en.add(se + "fc1.bias", {b[3] / 4});
+    en.add(se + "fc2.weight", {mid, b[3] / 4, 1, 1}), en.add(se + "fc2.bias", {mid});
+    cba(p + std::to_string(e + 2) + ".", b[4], mid, 1);
+  }
+  cba("features.4.", 160, 40, 1), en.linear("classifier.1", 10, 160);
+  for (const auto& pr : {std::make_pair("fp16", (int)SPI_PREC_F16), std::make_pair("fp32", (int)SPI_PREC_F32),
+                         std::make_pair("fp16x3", (int)SPI_PREC_F16X3), std::make_pair("fp16m", (int)SPI_PREC_F16M)}) {
+    spi_model_config cfg{};
+    cfg.family = SPI_FAMILY_AUTO, cfg.precision = pr.second, cfg.max_batch = 8, cfg.image_size = 64;
+    const bool served = pr.second == SPI_PREC_F16 || pr.second == SPI_PREC_F32;
+    try {
+      const spi::PackedModel m = spi::pack_model(cfg, en.t.data(), (int)en.t.size());
+      spi::ReplicaOptions o;
+      o.resize_short = 2 * m.image;
+      const spi::WorkspacePlan plan = spi::workspace_plan(m, o);
+      int steps = 0;
+      for (int B = 1; B <= m.max_batch; ++B) steps += spi::plan_check(m, o, B, 0);
+      const size_t out = (size_t)2 * m.classes * 4;
+      const bool ok = served && m.family == SPI_FAMILY_EFFICIENTNET && plan.bytes.size() == (size_t)spi::kEnBufs &&
+                      m.mb_blocks.size() == 4 && !m.mb_blocks[0].has_expand && m.mb_blocks[3].residual &&
+                      accepted(m, o, SPI_DTYPE_F32, 2, {3, 64, 64}, 4, out) && !accepted(m, o, SPI_DTYPE_F32, 2, {3, 63, 64}, 4, out) &&
+                      accepted(m, o, SPI_DTYPE_U8, 2, {100, 75, 3}, 1, out);
+      if (!ok) std::fprintf(stderr, "efficientnet|%s: family, blocks, plan or check_io are not the expected ones\n", pr.first), rc = 1;
+      std::printf("efficientnet|%s| flops(1) %.0f flops(3) %.0f, %zu buffers, slabs %zu (planned %zu), %d steps fit, %s\n", pr.first,
+                  spi::model_flops(m, 1), spi::model_flops(m, 3), plan.bytes.size(), plan.partial_floats, plan.partial_planned,
+                  steps, spi::replica_desc(m, o).c_str());
+    } catch (const std::runtime_error& e) {
+      if (served) std::fprintf(stderr, "efficientnet|%s: %s\n", pr.first, e.what()), rc = 1;
+      else std::printf("efficientnet|%s| refused: %s\n", pr.first, e.what());
+    }
+  }
   return rc;
 }

@@ -118,6 +118,20 @@ void ln_rows_add(const void* x, const void* res, void* y, const float* gamma, co
 // s2d_ln's gather without the LayerNorm (same column order and ranges): PatchMergingV2 normalises behind its Linear.
 void s2d_rows(const void* x, void* y, int B, int H, int W, int C, bool f16, hipStream_t s);
 
+// MBConv (mbconv.hip; supported sets, tile geometry and the weight layout: mbconv_pack.hpp).  Depthwise k x k conv
+// (k 3 or 5, stride 1 or 2, pad (k - 1) / 2) + bias + activation (0 none, 3 SiLU): x NHWC [B][H][W][C] ->
+// y [B][OH][OW][C], x / w / y in the compute type, w [k k][C] from dwconv_pack_into, bias fp32 [C].  pool_part, when
+// not null: fp32 [B][dwconv_tiles(H, W, k, stride)][C], the per-tile sums of the fp32 activations.  Throws
+// std::invalid_argument outside the set.
+void dwconv_act(const void* x, const void* w, const float* bias, void* y, float* pool_part, int B, int H, int W, int C,
+                int k, int stride, int act, bool f16, hipStream_t s);
+// gate [B][C] = sigmoid(W2 SiLU(W1 mean + b1) + b2), mean[c] = sum over `tiles` rows of part [B][tiles][C] / hw;
+// all fp32, W1 [sq][C], W2 [C][sq], 1 <= sq <= 256.
+void se_gate(const float* part, int tiles, int hw, const float* W1, const float* b1, const float* W2, const float* b2,
+             float* gate, int B, int C, int sq, hipStream_t s);
+// y [B][HW][C] = x * gate [B][C] (fp32 product, one rounding); y may be x.
+void scale_channels(const void* x, const float* gate, void* y, int B, int HW, int C, bool f16, hipStream_t s);
+
 // The kind of an image task's input buffer (SrcKind) and its 8-bit input transform (InputXf): image_src.hpp.
 // The transform of one pixel of channel c.  Contraction is switched off for the two operations:
 // HIP compiles with -ffp-contract=fast, under which __fmul_rn / __fadd_rn are a plain * and + that

@@ -14,7 +14,7 @@ from . import _native as N
 from ._native import lib
 
 PREC = {"fp32": 0, "fp16": 1, "fp16x3": 2, "fp16x3s": 3}  # fp16x3s: split activation layout
-ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2}
+ACT = {None: 0, "none": 0, "relu": 1, "gelu": 2, "silu": 3}  # silu: gemm, conv2d and dwconv_act only
 
 
 class OpError(RuntimeError):
@@ -322,6 +322,53 @@ def s2d_rows(prec, x_nhwc, out, stream=None):
     """out [B (H/2) (W/2)][4 C] = patch merging's gathered rows (s2d_ln's order), not normalised."""
     B, H, W_, c = x_nhwc.shape
     _check(lib.spi_op_s2d_rows(PREC[prec], _ptr(x_nhwc), B, H, W_, c, _ptr(out), _stream(stream)))
+    return out
+
+
+# ---- MBConv kernels (spi_ops.h: spi_op_dwconv_act, spi_op_se_gate, spi_op_scale_channels) ----
+
+
+def pack_weight_dwconv(prec, w, device="cuda") -> torch.Tensor:
+    """torch depthwise weight [C][1][k][k] fp32 (BatchNorm folded in) -> [k k][C] device tensor of prec's type."""
+    w = np.ascontiguousarray(np.asarray(w.cpu() if isinstance(w, torch.Tensor) else w, dtype=np.float32))
+    c, k = w.shape[0], w.shape[-1]
+    host = np.empty((k * k, c), dtype=np.float16 if prec == "fp16" else np.float32)
+    _check(lib.spi_op_dwconv_pack_weight(PREC[prec], w.ctypes.data, c, k, host.ctypes.data))
+    return torch.from_numpy(host).to(device)
+
+
+def dwconv_tiles(H, W_, k, stride) -> int:
+    """Rows per image of dwconv_act's pool sums for an H x W map (0: k or stride outside the supported set)."""
+    return lib.spi_op_dwconv_tiles(H, W_, k, stride)
+
+
+def dwconv_act(prec, x_nhwc, w_packed, bias, k, stride, out, act="silu", pool_part=None, stream=None):
+    """out [B][OH][OW][C] = act(depthwise k x k conv(x_nhwc, pad (k - 1) / 2, stride) + bias); pool_part: fp32
+    [B][dwconv_tiles(H, W, k, stride)][C] to receive the per-tile sums of the fp32 activations, or None."""
+    B, H, W_, c = x_nhwc.shape
+    rows = dwconv_tiles(H, W_, k, stride)
+    if pool_part is not None and (rows == 0 or tuple(pool_part.shape) != (B, rows, c)):
+        raise ValueError(f"dwconv_act: pool_part must be [{B}][{rows}][{c}], got {tuple(pool_part.shape)}")
+    tiles = C.c_int32(-1)
+    _check(lib.spi_op_dwconv_act(PREC[prec], _ptr(x_nhwc), B, H, W_, c, k, stride, _ptr(w_packed), _ptr(bias), ACT[act],
+                                 _ptr(out), _ptr(pool_part), C.byref(tiles), _stream(stream)))
+    if tiles.value != rows:  # the launch's own count of pool_part's rows against the size query's
+        raise RuntimeError(f"dwconv_act wrote {tiles.value} tile rows, spi_op_dwconv_tiles says {rows}")
+    return out
+
+
+def se_gate(part, hw, W1, b1, W2, b2, out, stream=None):
+    """out fp32 [B][C] = sigmoid(W2 silu(W1 mean + b1) + b2), mean = part [B][tiles][C] summed over tiles / hw."""
+    B, tiles, c = part.shape
+    _check(lib.spi_op_se_gate(_ptr(part), tiles, hw, _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(out), B, c,
+                              W1.shape[0], _stream(stream)))
+    return out
+
+
+def scale_channels(prec, x, gate, out, stream=None):
+    """out [B][HW][C] = x * gate [B][C] (fp32 product, one rounding); out may be x."""
+    B, hw, c = x.shape
+    _check(lib.spi_op_scale_channels(PREC[prec], _ptr(x), _ptr(gate), _ptr(out), B, hw, c, _stream(stream)))
     return out
 
 

@@ -119,7 +119,8 @@ class ResNet(nn.Module):
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
 
-def _randomize_bn_and_calibrate(model: nn.Module, image: int, seed: int, calib_batch: int = 4) -> None:
+def _randomize_bn_and_calibrate(model: nn.Module, image: int, seed: int, calib_batch: int = 4,
+                                normalised_half: bool = False) -> None:
     g = torch.Generator().manual_seed(seed + 1)
     # The last BN of each residual branch gets a small gamma, as in trained
     # ResNets (torchvision's zero_init_residual idea, kept non-zero): with unit
@@ -131,6 +132,8 @@ def _randomize_bn_and_calibrate(model: nn.Module, image: int, seed: int, calib_b
             last_bn.add(id(blk.bn3))
         elif isinstance(blk, BasicBlock):
             last_bn.add(id(blk.bn2))
+        elif isinstance(blk, MBConv) and blk.use_res:
+            last_bn.add(id(blk.block[-1][1]))
     for m in model.modules():
         if isinstance(m, nn.BatchNorm2d):
             with torch.no_grad():
@@ -142,6 +145,9 @@ def _randomize_bn_and_calibrate(model: nn.Module, image: int, seed: int, calib_b
             m.momentum = None  # cumulative average: one pass = that batch's statistics
             m.reset_running_stats()
     x = torch.rand(calib_batch, 3, image, image, generator=g)
+    if normalised_half:  # the second half under the ImageNet mean / std: pixels in -2.1 .. 2.6
+        mean, std = torch.tensor([0.485, 0.456, 0.406]).view(3, 1, 1), torch.tensor([0.229, 0.224, 0.225]).view(3, 1, 1)
+        x[calib_batch // 2:] = (x[calib_batch // 2:] - mean) / std
     model.train()
     with torch.no_grad():
         model(x)
@@ -583,6 +589,107 @@ def swin_b(seed: int = 0, image: int = 224, **kw) -> SwinTransformer:
 
 
 # ---------------------------------------------------------------------------
+# EfficientNet (torchvision.models.efficientnet naming, b0 .. b7)
+# ---------------------------------------------------------------------------
+def _make_divisible(v: float, divisor: int = 8) -> int:
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    return new_v + divisor if new_v < 0.9 * v else new_v
+
+
+def _conv_bn_act(cin: int, cout: int, k: int, stride: int = 1, groups: int = 1, act: bool = True) -> nn.Sequential:
+    layers = [nn.Conv2d(cin, cout, k, stride, (k - 1) // 2, groups=groups, bias=False), nn.BatchNorm2d(cout, eps=1e-5)]
+    return nn.Sequential(*layers, nn.SiLU()) if act else nn.Sequential(*layers)
+
+
+class SqueezeExcitation(nn.Module):
+    def __init__(self, channels: int, squeeze: int):
+        super().__init__()
+        self.fc1 = nn.Conv2d(channels, squeeze, 1)
+        self.fc2 = nn.Conv2d(squeeze, channels, 1)
+
+    def forward(self, x):
+        s = nn.functional.silu(self.fc1(x.mean((2, 3), keepdim=True)))
+        return x * torch.sigmoid(self.fc2(s))
+
+
+class MBConv(nn.Module):
+    def __init__(self, expand: int, k: int, stride: int, cin: int, cout: int):
+        super().__init__()
+        self.use_res = stride == 1 and cin == cout
+        mid = _make_divisible(cin * expand)
+        layers = [_conv_bn_act(cin, mid, 1)] if mid != cin else []
+        layers += [_conv_bn_act(mid, mid, k, stride, groups=mid), SqueezeExcitation(mid, max(1, cin // 4)),
+                   _conv_bn_act(mid, cout, 1, act=False)]
+        self.block = nn.Sequential(*layers)
+
+    def forward(self, x):  # eval: stochastic depth is the identity
+        return x + self.block(x) if self.use_res else self.block(x)
+
+
+# (expand, kernel, stride, in, out, layers) of efficientnet_b0; width_mult scales in / out, depth_mult the layers
+_MBCONV_SETTINGS = [(1, 3, 1, 32, 16, 1), (6, 3, 2, 16, 24, 2), (6, 5, 2, 24, 40, 2), (6, 3, 2, 40, 80, 3),
+                    (6, 5, 1, 80, 112, 3), (6, 5, 2, 112, 192, 4), (6, 3, 1, 192, 320, 1)]
+
+
+class EfficientNet(nn.Module):
+    def __init__(self, width_mult: float, depth_mult: float, num_classes: int = 1000):
+        super().__init__()
+        ch = lambda c: _make_divisible(c * width_mult)  # noqa: E731
+        layers = [_conv_bn_act(3, ch(_MBCONV_SETTINGS[0][3]), 3, 2)]
+        for expand, k, stride, cin, cout, n in _MBCONV_SETTINGS:
+            stage = [MBConv(expand, k, stride if i == 0 else 1, ch(cin) if i == 0 else ch(cout), ch(cout))
+                     for i in range(int(math.ceil(n * depth_mult)))]
+            layers.append(nn.Sequential(*stage))
+        last = ch(_MBCONV_SETTINGS[-1][4])
+        layers.append(_conv_bn_act(last, 4 * last, 1))
+        self.features = nn.Sequential(*layers)
+        self.avgpool = nn.AdaptiveAvgPool2d(1)
+        self.classifier = nn.Sequential(nn.Dropout(0.2), nn.Linear(4 * last, num_classes))
+
+    def forward(self, x):
+        return self.classifier(torch.flatten(self.avgpool(self.features(x)), 1))
+
+
+def efficientnet(width_mult: float = 1.0, depth_mult: float = 1.0, image: int = 224, num_classes: int = 1000,
+                 seed: int = 0) -> EfficientNet:
+    """EfficientNet with seeded random weights: conv and linear weights N(0, 1 / fan_in), the squeeze-and-
+    excitation biases N(0, 0.5^2) so that the gates spread over (0, 1), BatchNorm gains and biases as resnet() sets
+    them: a wrong block, gate or stride shows in the logits.  The running statistics come from one calibration pass
+    over 32 images at 64 pixels (fewer as the image grows, 4 at the least), half of them uniform in [0, 1] and half
+    under the ImageNet mean / std, so that the net stays inside its calibrated range for both kinds of input.
+    Calibrated on 4 uniform images alone, the BatchNorms behind near-constant SiLU channels amplified a rounding
+    60-fold (fp32 against float64: 3.5e-6, and 4.2e-5 on a normalised image); this recipe gives 5e-7 and 2e-6."""
+    torch.manual_seed(seed)
+    model = EfficientNet(width_mult, depth_mult, num_classes)
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, (nn.Conv2d, nn.Linear)):
+                m.weight.normal_(std=m.weight[0].numel() ** -0.5)
+                if m.bias is not None:
+                    m.bias.normal_(std=0.5 if isinstance(m, nn.Conv2d) else 0.05)
+    calib = max(4, min(32, 32 * 64 * 64 // (image * image) // 2 * 2))
+    _randomize_bn_and_calibrate(model, image, seed, calib_batch=calib, normalised_half=True)
+    return model.eval()
+
+
+# (width_mult, depth_mult, image) of torchvision's efficientnet_b0 .. _b7
+_EFFICIENTNETS = {"efficientnet_b0": (1.0, 1.0, 224), "efficientnet_b1": (1.0, 1.1, 240), "efficientnet_b2": (1.1, 1.2, 288),
+                  "efficientnet_b3": (1.2, 1.4, 320), "efficientnet_b4": (1.4, 1.8, 384), "efficientnet_b5": (1.6, 2.2, 456),
+                  "efficientnet_b6": (1.8, 2.6, 528), "efficientnet_b7": (2.0, 3.1, 600)}
+
+
+def _efficientnet_named(name: str):
+    def make(seed: int = 0, image: int | None = None, **kw) -> EfficientNet:
+        w, d, size = _EFFICIENTNETS[name]
+        return efficientnet(w, d, size if image is None else image, seed=seed, **kw)
+    return make
+
+
+(efficientnet_b0, efficientnet_b1, efficientnet_b2, efficientnet_b3, efficientnet_b4, efficientnet_b5, efficientnet_b6,
+ efficientnet_b7) = (_efficientnet_named(_n) for _n in sorted(_EFFICIENTNETS))
+
+
+# ---------------------------------------------------------------------------
 # BERT (HF transformers BertModel, wrapped like models/import_bert-base-uncased.py)
 # ---------------------------------------------------------------------------
 class BertWrapper(nn.Module):
@@ -876,6 +983,7 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
         "xlm_roberta_base": xlm_roberta_base,
         "xlm_roberta_large": xlm_roberta_large,
         "mpnet_base": mpnet_base,
+        **{name: _efficientnet_named(name) for name in _EFFICIENTNETS},
     }
     if name not in table:
         raise KeyError(f"unknown model {name!r}; known: {sorted(table)}")
@@ -887,6 +995,6 @@ def build(name: str, seed: int = 0, **kw) -> nn.Module:
 # (a traced/scripted model must round-trip through .pt like the reference's).
 for _cls in (BasicBlock, Bottleneck, ResNet, MLPBlock, EncoderBlock, Encoder, VisionTransformer, LayerNorm2d, Permute,
              CNBlock, ConvNeXt, ShiftedWindowAttention, ShiftedWindowAttentionV2, SwinTransformerBlock, SwinTransformerBlockV2,
-             PatchMerging, PatchMergingV2, SwinTransformer, BertWrapper,
+             PatchMerging, PatchMergingV2, SwinTransformer, SqueezeExcitation, MBConv, EfficientNet, BertWrapper,
              BertTupleWrapper, BertSegmentsWrapper, BertHeadWrapper, AddConstant):
     _cls.__module__ = "spi_zoo"
