@@ -1521,7 +1521,7 @@ void gemm(const GemmDesc& d, const GemmPtrs& p, Prec prec, hipStream_t s) {
 extern "C" int spi_debug_conv_route(int precision, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                                     int pad, int has_residual, int act) {
   if (precision < 0 || precision > 3 || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || KH < 1 || KW < 1 ||
-      stride < 1 || pad < 0 || act < 0 || act > 2)
+      stride < 1 || pad < 0 || act < 0 || act > 3)
     return -1;
   const Prec prec = case_prec(precision);
   GemmDesc d = case_conv_desc(precision, B, H, W, Cin, Cout, KH, KW, stride, pad);

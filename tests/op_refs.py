@@ -1,6 +1,7 @@
 """Plain float64 / bit-exact references of the ops behind include/spi_ops.h that the GPU op tests
 (test_qkv_attention_ops_gpu.py, test_attention_ops_gpu.py, test_elementwise_ops_gpu.py, test_conv_pair_ops_gpu.py,
-test_hilo_weight_ops_gpu.py, test_conv_kinds_ops_gpu.py, test_stem_ops_gpu.py, test_fc_ops_gpu.py, the hi + lo
+test_hilo_weight_ops_gpu.py, test_conv_kinds_ops_gpu.py, test_stem_ops_gpu.py, test_fc_ops_gpu.py,
+test_silu_routes_ops_gpu.py, the hi + lo
 consumer of test_ln_fold_ops_gpu.py) compare the HIP kernels with,
 plus the inputs and case lists those tests share.  Nothing here touches a GPU; test_op_refs.py checks every reference
 against the torch op it restates, so the GPU bars rest on checked ground.
@@ -311,13 +312,26 @@ def gelu64(x):
     return (0.5 * t * (1 + torch.erf(t / 2 ** 0.5))).numpy()
 
 
-def epilogue64(acc, bias=None, res=None, act=None):
+def silu64(x):
+    """y / (1 + exp(-y)) in float64; exp overflows to +inf below -709 and the quotient is then -0, the limit."""
+    y = np.asarray(x, np.float64)
+    with np.errstate(over="ignore"):
+        return y / (1 + np.exp(-y))
+
+
+def preact64(acc, bias=None, res=None):
+    """float64 acc + bias + residual: what the activation is applied to."""
     y = np.asarray(acc, np.float64)
     if bias is not None:
         y = y + np.asarray(bias, np.float64)
     if res is not None:
         y = y + np.asarray(res, np.float64)
-    return {None: y, "relu": np.maximum(y, 0), "gelu": gelu64(y)}[act]
+    return y
+
+
+def epilogue64(acc, bias=None, res=None, act=None):
+    y = preact64(acc, bias, res)
+    return {None: lambda: y, "relu": lambda: np.maximum(y, 0), "gelu": lambda: gelu64(y), "silu": lambda: silu64(y)}[act]()
 
 
 def dense_acc64(A, Wv):
@@ -576,7 +590,8 @@ def query_conv_plan(lib, prec, shape):
 
 def query_conv_route(lib, prec, shape, res, act):
     """spi_debug_conv_route: 1 when the weight-resident kernel would run (aligned operands, a whole pack)."""
-    return int(lib.spi_debug_conv_route(PREC_ID[prec], *shape, int(bool(res)), {None: 0, "relu": 1}[act]))
+    return int(lib.spi_debug_conv_route(PREC_ID[prec], *shape, int(bool(res)),
+                                         {None: 0, "relu": 1, "gelu": 2, "silu": 3}[act]))
 
 
 class kind_knobs:
@@ -997,3 +1012,214 @@ def forced_splits(ksteps, splits, max_split=8):
     s = max(1, min(splits, max_split, ksteps))
     kt = -(-ksteps // s)
     return -(-ksteps // kt), kt
+
+
+# ---------------------------------------------------------------------------------------------
+# the SiLU epilogue (Act::Silu: act 3 of spi_op_gemm and spi_op_conv2d) on every GEMM and conv route
+# (test_silu_routes_ops_gpu.py), and the second error figure of a SiLU output
+
+SILU_LOBE = 0.2785  # depth of SiLU's negative lobe: min of y sigmoid(y) is -0.27846, at y = -1.27846
+SILU_BAR32, SILU_BAR16 = 1e-5, 2e-3  # fp32 / split outputs and fp16 operands into fp32; fp16 outputs
+
+
+def silu_lobe_err(got, ref, pre):
+    """max|got - ref| over the entries whose float64 pre-activation is <= 0, over the depth of the lobe.  The
+    normalised max error divides by max|ref|, several units on the positive side, where the whole negative lobe
+    is 0.2785 deep: a wrong negative branch can pass it.  Held to the same bar as nerr."""
+    neg = np.asarray(pre, np.float64) <= 0
+    if not neg.any():
+        return 0.0
+    return float(np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64))[neg].max() / SILU_LOBE)
+
+
+def silu_bar(prec, out_f32):
+    return SILU_BAR16 if prec == "fp16" and not out_f32 else SILU_BAR32
+
+
+# dense (M, N, K), EfficientNet's: expand shapes with K below one k-step and N across a 64- and a 128-wide tile,
+# project shapes with N below a tile, two long-K shapes (the rule splits 100 x 320 x 1152; 70 x 1152 x 192 has too
+# few k-steps for it and splits under a forced plan), the head's (gemm256-eligible)
+SILU_DENSE = [(200, 96, 16), (197, 144, 24), (130, 240, 40), (129, 40, 240), (300, 16, 96), (300, 24, 144),
+              (70, 1152, 192), (100, 320, 1152), (50, 1280, 320), (300, 1280, 320)]
+# form -> (activation, residual); every form has a bias.  "res" is the project form
+SILU_FORMS = {"silu": ("silu", False), "silu-res": ("silu", True), "res": (None, True)}
+SILU_OUTS = [("fp32", True), ("fp16", False), ("fp16", True)]  # (precision, fp32 output)
+SILU_FORCED = ["128,128,2,1", "128,64,2,1", "128,64,3,1", "64,64,2,1", "64,64,3,2", "64,64,2,5"]
+# two with a ragged last tile column (N = 144, 24), two of whole tiles (1152; 320 at 64 columns)
+SILU_FORCED_SHAPES = [(197, 144, 24), (300, 24, 144), (70, 1152, 192), (100, 320, 1152)]
+SILU_X3 = (100, 96, 160)
+SILU_X3_PLANS = [None, "64,64,3,2"]
+SILU_G256_MIN = ["1", "0,1,3", "0,1,2"]  # test_ops_gpu.gemm256_everywhere's values
+SILU_G256_SHAPES = [(50, 1280, 320), (300, 1280, 320)]
+SILU_G256_SPLIT = (257, 256, 2048)
+SILU_G256_SPLIT_ENV = [{"SPI_GEMM_256_LONGK": "48,1024,4", "SPI_GEMM_MAXSPLIT": m} for m in ("2", "0")]
+SILU_SAT_BIAS = [100.0, 20.0, 0.0, -0.0, -20.0, -88.0, -89.0, -104.0, -1e4]
+SILU_SAT_SHAPES = {"gemm": (64, 64, 64), "gemm256": (50, 256, 64)}
+GEMM_KNOBS = KIND_KNOBS + ("SPI_GEMM_256_MIN", "SPI_GEMM_256_LONGK", "SPI_GEMM_256_ORDER")
+F_ACT, F_RES_F32, F_OUT_F32 = 1, 2, 32  # flag word of spi_debug_gemm_plan
+
+
+class gemm_knobs(kind_knobs):
+    """with gemm_knobs(lib, env): every planner knob unset but for env's, re-read; put back on the way out."""
+
+    def __init__(self, lib, env):
+        self.lib, self.env = lib, dict(env)
+
+    def __enter__(self):
+        import os
+        self.saved = {k: os.environ.pop(k, None) for k in GEMM_KNOBS}
+        os.environ.update(self.env)
+        self.lib.spi_debug_gemm_reload_env()
+
+
+def silu_dense_case(M, N, K):
+    """fp32 A of N(0, 1) (a precision multiplies operand_values of it), W of N(0, 1 / K), a bias of N(0, 1) -- the
+    pre-activation has sigma sqrt(2) around 0, so both lobes of SiLU are populated -- and a residual at a quarter
+    of that sigma."""
+    rng = np.random.default_rng(M * 7 + N * 3 + K + 2)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    W = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    b = rng.standard_normal(N).astype(np.float32)
+    return A, W, b, (0.25 * np.sqrt(2.0) * rng.standard_normal((M, N))).astype(np.float32)
+
+
+def silu_res_kind(prec, out_f32):
+    """The residual is of the output's type: "f16", "f32" or "split"."""
+    return "split" if prec == "fp16x3s" else "f16" if prec == "fp16" and not out_f32 else "f32"
+
+
+def silu_res_values(kind, r):
+    """float64 values of the fp32 residual r as a tensor of the kind holds them."""
+    return {"f16": hi_values, "split": split_values, "f32": lambda a: np.asarray(a, np.float32).astype(np.float64)}[kind](r)
+
+
+def silu_gemm_runs():
+    """Every spi_op_gemm launch of test_silu_routes_ops_gpu.py but the saturation cases, as dicts: group, env (the
+    knobs), prec, shape, form, out_f32, res (the residual's kind, or None), c_kind ("strided", or "unaligned": C
+    one element off 16 bytes), refused (gemm256 must refuse the desc).  The GPU file launches exactly this list;
+    test_op_refs.py derives SILU_GEMM_ROUTES from it."""
+    runs = []
+
+    def add(group, env, prec, shape, form, out_f32, **kw):
+        res = silu_res_kind(prec, out_f32) if SILU_FORMS[form][1] else None
+        runs.append({"group": group, "env": env, "prec": prec, "shape": shape, "form": form, "out_f32": out_f32,
+                     "res": res, "c_kind": "strided", "refused": False, **kw})
+
+    for prec, out_f32 in SILU_OUTS:
+        for shape in SILU_DENSE:
+            for form in SILU_FORMS:
+                add("rule", {}, prec, shape, form, out_f32)
+        for plan in SILU_FORCED:
+            for shape in SILU_FORCED_SHAPES:
+                for form in SILU_FORMS:
+                    add("forced", {"SPI_GEMM_PLAN": plan}, prec, shape, form, out_f32)
+    for prec in ("fp16x3", "fp16x3s"):
+        for plan in SILU_X3_PLANS:
+            add("x3", {"SPI_GEMM_PLAN": plan} if plan else {}, prec, SILU_X3, "silu-res", prec == "fp16x3")
+    for tiles in SILU_G256_MIN:
+        env = {"SPI_GEMM_256_MIN": tiles}
+        for shape in SILU_G256_SHAPES:
+            for out_f32 in (False, True):
+                add("g256", env, "fp16", shape, "silu", out_f32)
+                add("g256", env, "fp16", shape, "silu-res", out_f32, res="f16")
+                add("g256", env, "fp16", shape, "silu", out_f32, c_kind="unaligned")
+            add("g256", env, "fp16", shape, "silu-res", True, res="f32", refused=True)
+        for extra in SILU_G256_SPLIT_ENV:
+            add("g256split", {**env, **extra}, "fp16", SILU_G256_SPLIT, "silu", True)
+    return runs
+
+
+def silu_run_id(r):
+    knobs = "+".join(v for v in r["env"].values()) or "rule"
+    return "-".join([r["group"], knobs, r["prec"], "x".join(map(str, r["shape"])), r["form"], "f32" if r["out_f32"] else "out",
+                     r["res"] or "nores", r["c_kind"]])
+
+
+def silu_run_lda(r):
+    """A's row stride: K + 8 (the split layout: + 32), the slack NaN."""
+    return r["shape"][2] + (32 if r["prec"] == "fp16x3s" else 8)
+
+
+def silu_run_flags(r):
+    """spi_debug_gemm_plan's flag word of a run, as ops.gemm passes the operands' types."""
+    split = r["prec"] == "fp16x3s"
+    return (F_ACT if SILU_FORMS[r["form"]][0] else 0) | (F_RES_F32 if r["res"] == "f32" else 0) | \
+        (F_OUT_F32 if r["out_f32"] and not split else 0)
+
+
+def query_gemm_plan(lib, prec, M, N, K, lda, flags):
+    """spi_debug_gemm_plan's 14 integers under the knobs in force."""
+    import ctypes as C
+    out = (C.c_longlong * 14)()
+    assert lib.spi_debug_gemm_plan(PREC_ID[prec], M, N, K, lda, 1, 0, C.c_uint(flags), out) == 0
+    return [int(v) for v in out]
+
+
+def gemm_route(v):
+    """(kernel, tile rows, tile columns, split-K or not) of spi_debug_gemm_plan's answer."""
+    return ("gemm256", v[0], 256, v[1] > 1) if v[0] else ("gemm", v[4], v[5], v[7] > 1)
+
+
+def silu_run_route(lib, r):
+    """The plan and the route of a run under its knobs."""
+    with gemm_knobs(lib, r["env"]):
+        v = query_gemm_plan(lib, r["prec"], *r["shape"], silu_run_lda(r), silu_run_flags(r))
+    return v, gemm_route(v)
+
+
+# The routes silu_gemm_runs() launches with act 3 (test_op_refs.test_silu_routes_constant_is_what_the_runs_launch)
+# and the saturation cases repeat; tests/test_efficientnet.py holds every GEMM of efficientnet_b0 at batch 1, 8 and
+# 32 to this set.
+SILU_GEMM_ROUTES = frozenset({
+    ("gemm", 64, 64, False), ("gemm", 64, 64, True), ("gemm", 128, 64, False), ("gemm", 128, 128, False),
+    ("gemm256", 256, 256, False), ("gemm256", 256, 256, True), ("gemm256", 128, 256, False),
+    ("gemm256", 128, 256, True),
+})
+
+# convs, all "silu" with bias.  A 3x3 / s1 kind: the knob setting -> (the precisions conv_kind_runs launches the
+# kind at, what its plan must say); the GPU test takes the smallest CONV3_SHAPES entry whose plan says so
+_WIN, _HALO = ("fp16", "fp16x3s"), ("fp32", "fp16", "fp16x3s")
+SILU_CONV_KINDS = {
+    "win1": (_WIN, lambda p: p["win"] and p["nw"] == 4 and not p["halo"]),
+    "win2": (_WIN, lambda p: p["win"] and p["nw"] == 8 and not p["halo"]),
+    "halo64a": (_HALO, lambda p: p["halo"] and p["bm"] == 64),
+    "halo128s": (_HALO, lambda p: p["halo"] and p["bm"] == 128),
+    "halo256a": (_HALO, lambda p: p["halo"] and p["bm"] == 256),
+    "rule-max3": (_HALO, lambda p: p["halo"] and 1 < p["splits"] <= 3),  # the default rule's halo, slices capped (S9)
+}
+SILU_CONV_TAP = (2, 9, 13, 64, 64, 3, 3, 2, 1)                                       # fp16 and fp32
+SILU_CONV_GATHER = {"fp16": (3, 33, 31, 8, 40, 3, 3, 2, 1), "fp32": (3, 33, 31, 4, 40, 3, 3, 2, 1)}  # the stem form
+SILU_CONV_WRES = (2, 16, 8)  # of WRES_SHAPES
+
+
+def silu_conv_pick(lib, setting, prec):
+    """(name, 9-tuple, plan) of the smallest CONV3_SHAPES entry that conv_kind_runs launches under the setting at
+    the precision and whose plan takes the setting's kind."""
+    s3 = {k: shape9(v) for k, v in CONV3_SHAPES.items()}
+    launched = {shape for _, st, p, shape in conv_kind_runs() if (st, p) == (setting, prec)}
+    with kind_knobs(lib, setting):
+        for name in sorted(s3, key=lambda n: s3[n][0] * s3[n][1] * s3[n][2] * s3[n][3]):
+            if s3[name] in launched:
+                plan = query_conv_plan(lib, prec, s3[name])
+                if SILU_CONV_KINDS[setting][1](dict(zip(PLAN_FIELDS, plan))):
+                    return name, s3[name], plan
+    return None
+
+
+# efficientnet_b0 (torchvision's block table): (expand, kernel, stride, in, out, layers); image 224
+EFFNET_B0_BLOCKS = [(1, 3, 1, 32, 16, 1), (6, 3, 2, 16, 24, 2), (6, 5, 2, 24, 40, 2), (6, 3, 2, 40, 80, 3),
+                    (6, 5, 1, 80, 112, 3), (6, 5, 2, 112, 192, 4), (6, 3, 1, 192, 320, 1)]
+
+
+def effnet_b0_gemms(B, image=224):
+    """(M, N, K, activation, residual) of efficientnet_b0's GEMMs in forward order: each block's expand (none at
+    expansion 1: SiLU) and project (no activation; the residual where stride 1 keeps the width), then the head."""
+    out, H = [], image // 2
+    for expand, _, stride, cin, cout, n in EFFNET_B0_BLOCKS:
+        for i in range(n):
+            c, s = (cin, stride) if i == 0 else (cout, 1)
+            if expand != 1:
+                out.append((B * H * H, c * expand, c, "silu", False))
+            H = (H - 1) // s + 1
+            out.append((B * H * H, cout, c * expand, None, s == 1 and c == cout))
+    return out + [(B * H * H, 1280, 320, "silu", False)]

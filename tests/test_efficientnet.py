@@ -74,6 +74,36 @@ def test_depthwise_weight_is_bn_folded_tap_major(spi, zoo, prec):
     assert a.weight_bytes == b.weight_bytes and a.weight_digest == b.weight_digest
 
 
+def test_efficientnet_routes_are_covered(spi, zoo):
+    """Every GEMM of efficientnet_b0 at image 224 and batch 1, 8 and 32 -- listed from torchvision's block table,
+    its (N, K) sequence checked against the zoo's module -- plans, at fp16 and fp32, onto a route that
+    test_silu_routes_ops_gpu.py launches with the SiLU epilogue (op_refs.SILU_GEMM_ROUTES)."""
+    import op_refs as R
+
+    net = zoo.EfficientNet(1.0, 1.0)
+    convs = []
+    for stage in list(net.features)[1:-1]:
+        for blk in stage:
+            seq = list(blk.block)
+            convs += [seq[0][0]] * (len(seq) == 4) + [seq[-1][0]]
+    convs.append(net.features[-1][0])
+    gemms = R.effnet_b0_gemms(1)
+    assert [(c.out_channels, c.in_channels) for c in convs] == [(N, K) for _, N, K, _, _ in gemms]
+    assert all(c.kernel_size == (1, 1) and c.groups == 1 for c in convs)
+    assert len(gemms) == 15 + 16 + 1 and sum(res for *_, res in gemms) == 9 and gemms[-1][0] == 49
+    ks = {K for _, _, K, _, _ in gemms}
+    assert ks == {16, 24, 32, 40, 80, 96, 112, 144, 192, 240, 320, 480, 672, 1152}
+    found = set()
+    with R.gemm_knobs(spi.lib, {}):
+        for B in (1, 8, 32):
+            for M, N, K, act, _ in R.effnet_b0_gemms(B):
+                for prec in ("fp16", "fp32"):  # the model's descs: outputs and residuals of the compute type
+                    route = R.gemm_route(R.query_gemm_plan(spi.lib, prec, M, N, K, K, R.F_ACT if act else 0))
+                    assert route in R.SILU_GEMM_ROUTES, (B, prec, M, N, K, act, route)
+                    found.add(route)
+    assert ("gemm256", 128, 256, False) in found and ("gemm", 64, 64, True) in found  # the head at batch 32; split-K
+
+
 def test_refusals(spi, zoo):
     m = small(zoo)
 

@@ -686,3 +686,106 @@ def test_forced_splits_restates_finish_plan(spi):
     finally:
         os.environ.pop("SPI_GEMM_PLAN", None)
         spi.lib.spi_debug_gemm_reload_env()
+
+
+# ---- the SiLU epilogue's references and cases (test_silu_routes_ops_gpu.py) ----
+
+
+def test_silu64_equals_torch_float64():
+    y = np.random.default_rng(0).standard_normal(4096) * 3
+    assert R.nerr(R.silu64(y), F.silu(torch.from_numpy(y)).numpy()) < TOL64
+    assert R.nerr(R.epilogue64(y[:64], y[64:128], y[128:192], "silu"),
+                  F.silu(torch.from_numpy(y[:64] + y[64:128] + y[128:192])).numpy()) < TOL64
+    sat = R.silu64(np.array(R.SILU_SAT_BIAS))
+    assert np.isfinite(sat).all() and sat[-1] == 0 and np.signbit(sat[-1]) and (np.abs(sat[5:]) < 1e-30).all()
+    assert -R.SILU_LOBE < R.silu64(np.linspace(-20, 0, 200001)).min() < -0.2784
+
+
+def test_silu_lobe_err_sees_what_nerr_hides():
+    """A ReLU in SiLU's place moves the negative lobe by up to 0.2785: 1.0 on the lobe figure, and under any
+    normalised bar once the positive side is large enough."""
+    pre = np.array([-1.2785, -0.5, 0.0, 3.0, 2000.0])
+    ref = R.silu64(pre)
+    relu = np.maximum(pre, 0)
+    assert R.nerr(relu, ref) < 2e-4 and 0.99 < R.silu_lobe_err(relu, ref, pre) < 1.01
+    assert R.silu_lobe_err(ref, ref, pre) == 0 and R.silu_lobe_err(relu, ref, np.abs(pre) + 1) == 0
+
+
+def _silu_distinct_runs(lib):
+    """silu_gemm_runs() without the repeats that share inputs, reference and slices: (run, plan)."""
+    seen, out = set(), []
+    for r in R.silu_gemm_runs():
+        v, route = R.silu_run_route(lib, r)
+        slices = (v[1], -(-(r["shape"][2] // 64) // v[1]) * 64) if v[0] else (v[7], v[11])
+        key = (r["prec"], r["shape"], r["form"], r["res"], r["out_f32"], slices if slices[0] > 1 else None)
+        if key not in seen:
+            seen.add(key)
+            out.append((r, slices))
+    return out
+
+
+def test_silu_routes_constant_is_what_the_runs_launch(spi):
+    """SILU_GEMM_ROUTES is exactly the set of routes the planner gives the GPU file's launches; gemm256 takes
+    every run of its groups but the fp32-residual ones, which it must refuse; the split groups split."""
+    routes = set()
+    for r in R.silu_gemm_runs():
+        v, route = R.silu_run_route(spi.lib, r)
+        routes.add(route)
+        if r["group"] in ("g256", "g256split"):
+            assert (v[0] == 0) == r["refused"], (R.silu_run_id(r), v)
+        if r["group"] == "g256split":
+            assert v[1] > 1, (R.silu_run_id(r), v)
+    assert routes == R.SILU_GEMM_ROUTES
+    ids = [R.silu_run_id(r) for r in R.silu_gemm_runs()]
+    assert len(set(ids)) == len(ids)
+
+
+def test_silu_conv_kinds_all_have_a_shape(spi):
+    for setting, (precs, _) in R.SILU_CONV_KINDS.items():
+        for prec in precs:
+            assert R.silu_conv_pick(spi.lib, setting, prec) is not None, (setting, prec)
+    sh = R.shape9(R.SILU_CONV_WRES)
+    with R.kind_knobs(spi.lib, "wres2"):
+        assert [R.query_conv_route(spi.lib, "fp16", sh, False, a) for a in (None, "relu", "gelu", "silu")] == [1, 1, 0, 0]
+    with R.kind_knobs(spi.lib, "wres0"):
+        assert R.query_conv_route(spi.lib, "fp16", sh, False, "relu") == 0
+
+
+def test_silu_cases_discriminate(spi):
+    """On the GPU file's own inputs: at least a quarter of every case's pre-activations are negative, and each
+    wrong epilogue sits above 10x the case's bar on one of the two figures -- (a) GELU for SiLU, (b) the sigmoid
+    without the product, (c) SiLU before the residual is added, (d) SiLU of each split-K slice, summed, (e) ReLU
+    on the negative lobe."""
+    acc_cache = {}
+    for r, (splits, kps) in _silu_distinct_runs(spi.lib):
+        act, has_res = R.SILU_FORMS[r["form"]]
+        M, N, K = r["shape"]
+        A, W, b, Rr = R.silu_dense_case(M, N, K)
+        key = (r["prec"], r["shape"])
+        if key not in acc_cache:
+            av, wv = R.operand_values(r["prec"], A, W)
+            acc_cache[key] = (av, wv, R.dense_acc64(av, wv))
+        av, wv, acc = acc_cache[key]
+        rv = R.silu_res_values(r["res"], Rr) if has_res else None
+        pre = R.preact64(acc, b, rv)
+        what = R.silu_run_id(r)
+        assert (pre < 0).mean() >= 0.25, what
+        if act != "silu":
+            continue
+        ref = R.silu64(pre)
+        bar = 10 * R.silu_bar(r["prec"], r["out_f32"])
+        worst = lambda m: max(R.nerr(m, ref), R.silu_lobe_err(m, ref, pre))  # noqa: E731
+        assert np.abs(ref).max() > 1 and ref.min() < -0.27, what
+        assert worst(R.gelu64(pre)) > bar, what
+        with np.errstate(over="ignore"):
+            assert worst(1 / (1 + np.exp(-pre))) > bar, what
+        if has_res:
+            assert worst(R.silu64(R.preact64(acc, b)) + rv) > bar, what
+        if splits > 1:
+            # slices of the packed K (padded to 64): one past K holds zeros only
+            parts = [R.dense_acc64(av[:, k0:k0 + kps], wv[:, k0:k0 + kps]) for k0 in range(0, -(-K // 64) * 64, kps)]
+            assert len(parts) == splits and R.nerr(sum(parts), acc) < TOL64, what
+            per_slice = sum(R.silu64(p + (pre - acc if z == 0 else 0)) for z, p in enumerate(parts))
+            if K > kps:  # (K = 24 in two fp32 steps: the second slice is all padding, and SiLU(0) = 0)
+                assert worst(per_slice) > bar, what
+        assert worst(np.where(pre > 0, ref, 0)) > bar, what
